@@ -11,8 +11,10 @@
     python bench.py --gpus 2 --share-gpu                 functional run of the multi-rank path on a 1-GPU box (all ranks on cuda:0, gloo)
 
 Prints ONE JSON line (rank 0): metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline /
-dtype / data / config + roofline + cpu_baseline.  A "step" is one pass of the hot path over one batch of synthetic input; inputs are
-resident in HBM before the timed region (the per-step host input is the 165-float pose).
+dtype / data / config + the roofline's headline numbers as flat scalars.  A "step" is one pass of the hot path over one batch of synthetic
+input; inputs are resident in HBM before the timed region (the per-step host input is the 165-float pose).  --steps K is the number of
+timed steps: the default c3 run times those K steps and nothing else, and ms_per_step is one of them (c4 times 3 x K and reports the
+median; c5 times its side measurements after its K frames).
 
   c3 (default, the headline)  full SDS step, 100k Gaussians, 512^2, SD-1.5 + ControlNet, one view per GPU       -> SDS steps/s
   c4   multi-view SDS: V = 8 views per step, view v on GPU v mod N, ONE all-reduce of the flat gradient buffer  -> steps/s and views/s
@@ -20,10 +22,11 @@ resident in HBM before the timed region (the per-step host input is the 165-floa
   c5   300k Gaussians, 1024^2, per-frame animate + raster forward (inference)                                   -> frames/s
   c1   10k Gaussians, canonical pose, 256^2 raster forward only (the plumbing case; BASELINE.md's primary CPU number) -> frames/s
 
-The default single-GPU invocation also runs c1 / c2 / c4 (8 views on the one GPU) / c5 after the headline and attaches their lines under
-"configs", and the same step at the other plan precisions under "by_dtype" (each with its own roofline peak; their steps/s also sit
-right behind "dtype" as "steps_per_s_by_dtype"): everything the judge compares is in the one line the driver records.  --headline-only
-skips the attachments.
+--headline-only keeps the per-kernel blocks ("roofline", "kernel_ms_per_step") in the line.  --all-configs (single GPU) adds the full
+report: the CPU baseline, and for c3 the runs of c1 / c2 / c4 (8 views on the one GPU) / c5 attached under "configs" and the same step at
+the other plan precisions under "by_dtype" (each with its own roofline peak; their steps/s also sit right behind "dtype" as
+"steps_per_s_by_dtype") -- a line of some 20 KB, and timed steps beyond the K asked for.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import hashlib
@@ -62,7 +65,8 @@ def parse():
     ap.add_argument("--dtype", choices=["bf16", "f32", "f16", "f32x"], default=HEADLINE_DTYPE, help="storage type of the denoiser / VAE plans")
     ap.add_argument("--gaussians", type=int, default=None)
     ap.add_argument("--res", type=int, default=None)
-    ap.add_argument("--headline-only", action="store_true", help="skip the attached configs / by_dtype / cpu_baseline legs")
+    ap.add_argument("--headline-only", action="store_true", help="keep the per-kernel roofline / kernel_ms_per_step blocks in the line")
+    ap.add_argument("--all-configs", action="store_true", help="the full report: CPU baseline, and for c3 the attached configs / by_dtype legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-guidance", action="store_true", help="raster+LBS sub-path only (not the headline workload)")
     ap.add_argument("--frames-per-launch", type=int, default=4, help="config c5: pose frames per launch chain of the `batched_frames` side measurement (the value is always frame by frame)")
@@ -82,6 +86,9 @@ def parse():
                                                                     "batched VAE / denoiser pass for all the views of a rank")
     ap.add_argument("--share-gpu", action="store_true", help="every rank on cuda:0 over gloo: a functional run of the N > 1 path on a 1-GPU box, "
                                                              "NOT a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the measured workload's LAST timed "
+                    "step returned (and, for a training step, the parameter and gradient buffers it left) as DIR/<name>.npy, float32 or float64, "
+                    "at most 64 MB in all: arrays of more than 2^20 elements as a fixed seeded sample of at most 2^20 (rank 0; see dump_outputs)")
     return ap.parse_args()
 
 
@@ -384,17 +391,21 @@ class Ctx:
         return self.guidance[key]
 
 
-def _timed(ctx, fn, steps, warmup):
-    """W untimed + EXACTLY K timed calls bracketed by barrier + synchronize on both sides; MAX over ranks."""
+def _timed(ctx, fn, steps, warmup, keep=None):
+    """W untimed + EXACTLY K timed calls bracketed by barrier + synchronize on both sides; MAX over ranks.  `keep` (a list): receives what
+    the LAST timed call returned (no other call's result is held on to)."""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
     if ctx.dist is not None:
         ctx.dist.barrier()
     torch.cuda.synchronize()
+    last = steps > 0 and keep is not None
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1 if last else steps):
         fn()
+    if last:
+        keep[:] = [fn()]
     torch.cuda.synchronize()
     if ctx.dist is not None:
         ctx.dist.barrier()
@@ -406,9 +417,56 @@ def _timed(ctx, fn, steps, warmup):
     return dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20         # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20               # an array of more elements is dumped as (at most) this many of them, at fixed seeded positions
+
+
+def snapshot_outputs(named):
+    """{name: host array} of every tensor inside `named` ({name: tensor / dict / list / tuple}, nested; other values are skipped), copied
+    off the device at once -- the next step or a graph replay overwrites them.  Floating tensors stay float32 (float64 if they are),
+    integer and boolean ones become float64 (exact)."""
+    import numpy as np
+    out = {}
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            t = v.detach()
+            out[name] = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 or not t.is_floating_point() else np.float32)
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                walk("%s.%s" % (name, k), x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk("%s.%d" % (name, i), x)
+    for k, v in named.items():
+        walk(k, v)
+    return out
+
+
+def dump_outputs(arrays, path):
+    """Writes the snapshot as path/<name>.npy, DUMP_LIMIT_BYTES at most.  An array of more than `cap` elements is written flattened, as the
+    elements at np.sort(RandomState(0).choice(size, cap, replace=False)); `cap` starts at DUMP_SAMPLE and is halved until everything fits.
+    The positions depend only on the shapes, so that two builds are compared element for element.  Returns a summary for the result line."""
+    import numpy as np
+    cap = DUMP_SAMPLE
+    while sum(a.itemsize * min(a.size, cap) for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        cap //= 2
+    os.makedirs(path, exist_ok=True)
+    total, sampled = 0, []
+    for name, a in sorted(arrays.items()):
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, cap, replace=False))]
+            sampled.append(name)
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": path, "arrays": len(arrays), "bytes": total, "sampled": sampled, "sample_elements": cap}
+
+
 def run_sds(ctx, config, dtype=HEADLINE_DTYPE, views=None, steps=None, warmup=None, profile=True, batch_views=None, repeats=None, step_graph=None,
-            moving_camera=False, bound_loop=None):
+            moving_camera=False, bound_loop=None, dump=None):
     """c2 / c3 / c4: SDSStep-based workloads.  Returns the JSON line as a dict (rank 0) or None.
+    `dump` (a directory): what the last timed step returned -- loss, render outputs, guidance outputs -- and the flat parameter / gradient
+    buffers it left, written there (dump_outputs).
     `bound_loop`: the step as the reference's OWN loop drives it through the binding (dropin/dwg_bind.py; /root/reference/core/trainer.py:840-896):
     zero_grad -> update_learning_rate -> render -> guidance -> backward -> every optimizer's step, launch by launch from Python (no captured
     step), a NEW camera every step, the pair workspace sized by the 16-byte read-back per frame (the binding builds its Scene with
@@ -459,7 +517,8 @@ def run_sds(ctx, config, dtype=HEADLINE_DTYPE, views=None, steps=None, warmup=No
     if whole_graph:
         runner = step.graphed()
         run = runner.step
-    dts = [_timed(ctx, run, steps, warmup if r == 0 else 0) for r in range(max(1, repeats))]       # each: barrier + sync on both sides, max over ranks
+    keep = [] if dump is not None and ctx.rank == 0 else None
+    dts = [_timed(ctx, run, steps, warmup if r == 0 else 0, keep) for r in range(max(1, repeats))]       # each: barrier + sync on both sides, max over ranks
     recaptures = 0
     while whole_graph and runner.graph.check():
         # a replay needed more (Gaussian, block) pairs than the capacity frozen into the graph and was truncated by the kernels: the timed
@@ -468,8 +527,15 @@ def run_sds(ctx, config, dtype=HEADLINE_DTYPE, views=None, steps=None, warmup=No
         if recaptures > 3:
             raise SystemExit("bench.py: captured steps kept being truncated by the frozen pair capacity")
         runner.graph.recapture()
-        dts = [_timed(ctx, run, steps, 2) for r in range(max(1, repeats))]
+        dts = [_timed(ctx, run, steps, 2, keep) for r in range(max(1, repeats))]
     dt = sorted(dts)[len(dts) // 2]
+    dumped = None
+    if keep:
+        # before the eager profiling steps below move the parameters on: the step's (loss, render outputs[, guidance outputs]) and the
+        # flat parameter / gradient buffers it left
+        bufs = step.optimizers.buffers
+        dumped = dump_outputs(snapshot_outputs(dict(zip(("loss", "render", "guidance"), keep[0]), params=bufs.flat, grads=bufs.grad)), dump)
+        keep.clear()
     prof_steps, prof, prof_sym = steps, {}, {}
     if profile and not args.eager:
         # Per-kernel durations (HIP events on the launch stream) cannot be bracketed inside a graph replay: the same steps
@@ -537,6 +603,8 @@ def run_sds(ctx, config, dtype=HEADLINE_DTYPE, views=None, steps=None, warmup=No
                              "16-byte pair-count read-back per frame, loader-side condition image")
     out["launch_mode"] = ("eager" if args.eager else "the WHOLE step (zero_grad, animate, raster fwd + bwd, Adam) replayed as one captured HIP graph per pose"
                           if whole_graph else "hipGraph replay of denoiser/VAE plans; kernel timers from an eager replay after the timed region")
+    if dumped:
+        out["dumped_outputs"] = dumped
     return out
 
 
@@ -565,8 +633,9 @@ def _scene(ctx, G):
     return sc.Scene(cfg, avatar, async_pair_count=not ctx.args.sync_pairs).to(ctx.dev).eval(), N, M
 
 
-def run_c5(ctx, steps=None, warmup=None):
-    """Config c5: 300k-Gaussian avatar, per-frame animate (LBS + encoder + MLPs + mesh binding) + raster forward at 1024^2, inference."""
+def run_c5(ctx, steps=None, warmup=None, dump=None):
+    """Config c5: 300k-Gaussian avatar, per-frame animate (LBS + encoder + MLPs + mesh binding) + raster forward at 1024^2, inference.
+    `dump` (a directory): the last timed frame's outputs written there (dump_outputs)."""
     args = ctx.args
     steps, warmup = defaults("c5", steps, warmup)
     G, res = args.gaussians or 300000, args.res or 1024
@@ -596,7 +665,9 @@ def run_c5(ctx, steps=None, warmup=None):
             return scene.forward_frames(data, [poses[(i + f) % 240] for f in range(F)], bg_mode=None, frozen_avatar=frozen[0])
     # `value` is the reference's loop: ONE frame per call (/root/reference/core/trainer.py:1019-1150).  The batched form (F pose frames per
     # rasterizer launch chain, bit-identical images) and the frozen-avatar form are measured right after it and reported in side fields.
-    dt = _timed(ctx, frame, steps, warmup)
+    keep = [] if dump is not None else None
+    dt = _timed(ctx, frame, steps, warmup, keep)
+    dumped = dump_outputs(snapshot_outputs({"render": keep[0]}), dump) if keep else None
     dt_batched = dt_frozen = None
     bsteps = (steps + F - 1) // F * F
     if F > 1:
@@ -645,12 +716,13 @@ def run_c5(ctx, steps=None, warmup=None):
                 "what": "the batched frames with Scene.forward_frames(frozen_avatar=True): canonical positions, grid encoding and the colour / opacity "
                         "network computed once and kept while no parameter changes (bit-identical images); NOT the c5 value -- there every frame "
                         "recomputes them, as the reference's evaluation loop does"},
-            "kernel_ms_per_step": {k: round(v[1] / ps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[:20]}}
+            "kernel_ms_per_step": {k: round(v[1] / ps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[:20]}} | ({"dumped_outputs": dumped} if dumped else {})
 
 
-def run_c1(ctx, steps=None, warmup=None):
+def run_c1(ctx, steps=None, warmup=None, dump=None):
     """Config c1 (the plumbing case; BASELINE.md's primary CPU number): 10k Gaussians, canonical neutral pose, 256^2, raster forward only
-    -- Scene.forward without observed pose (avatar.forward(): canonical LBS + encoder + MLPs) under inference mode."""
+    -- Scene.forward without observed pose (avatar.forward(): canonical LBS + encoder + MLPs) under inference mode.  `dump` (a directory):
+    the last timed frame's outputs written there (dump_outputs)."""
     args = ctx.args
     steps, warmup = defaults("c1", steps, warmup)
     G, res = args.gaussians or 10000, args.res or 256
@@ -665,7 +737,9 @@ def run_c1(ctx, steps=None, warmup=None):
     if not args.eager:          # the frame as ONE captured graph (player.GraphedAnimation, canonical pose: no per-frame input)
         from dreamwaltz_g_amd import player as pl
         player = pl.GraphedAnimation(scene, data, None)
-    dt = _timed(ctx, player.replay if player is not None else frame, steps, warmup)
+    keep = [] if dump is not None else None
+    dt = _timed(ctx, player.replay if player is not None else frame, steps, warmup, keep)
+    dumped = dump_outputs(snapshot_outputs({"render": keep[0]}), dump) if keep else None
     if player is not None:
         assert player.check(), "a replayed frame was truncated by the frozen pair capacity"
         player.close()
@@ -683,7 +757,7 @@ def run_c1(ctx, steps=None, warmup=None):
                                    "inference_mode" % (N, M, res, res), "gaussians": G, "resolution": res},
             "roofline": raster_report(prof, G, Kref, K, res * res, ps),
             "launch_mode": "eager" if args.eager else "one hipGraph per frame (player.GraphedAnimation); kernel timers from eager frames after the timed region",
-            "kernel_ms_per_step": {k: round(v[1] / ps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[:12]}}
+            "kernel_ms_per_step": {k: round(v[1] / ps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[:12]}} | ({"dumped_outputs": dumped} if dumped else {})
 
 
 def _brief(line, keys=("value", "unit", "ms_per_step", "steps", "warmup", "repeats", "launch_mode", "camera", "dtype", "views_per_s", "views_per_step", "config",
@@ -736,18 +810,18 @@ def main():
     ctx = Ctx(args)
     if ctx.world != args.gpus and ctx.rank == 0:
         sys.stderr.write("bench.py: --gpus %d but the launcher started %d rank(s); reporting n_gpus=%d\n" % (args.gpus, ctx.world, ctx.world))
-    cpu_ok = not args.no_cpu_baseline and not args.headline_only and ctx.world == 1
+    cpu_ok = args.all_configs and not args.no_cpu_baseline and not args.headline_only and ctx.world == 1
     if args.config == "c5":
-        out = run_c5(ctx, args.steps, args.warmup)
+        out = run_c5(ctx, args.steps, args.warmup, dump=args.dump_outputs)
         if cpu_ok:
             out["cpu_baseline"] = cpu_baseline(out["config"]["gaussians"], out["config"]["resolution"], backward=False, budget_s=6.0, unit="frames/s")
     elif args.config == "c1":
-        out = run_c1(ctx, args.steps, args.warmup)
+        out = run_c1(ctx, args.steps, args.warmup, dump=args.dump_outputs)
         if cpu_ok:
             out["cpu_baseline"] = cpu_baseline(out["config"]["gaussians"], out["config"]["resolution"], backward=False, canonical=True, budget_s=4.0,
                                                unit="frames/s")
     else:
-        full = (args.config == "c3" and ctx.world == 1 and not args.headline_only and not args.no_guidance and args.dtype == HEADLINE_DTYPE
+        full = (args.all_configs and args.config == "c3" and ctx.world == 1 and not args.headline_only and not args.no_guidance and args.dtype == HEADLINE_DTYPE
                 and args.gaussians is None and args.res is None and not args.eager)
         pre_cfgs = {}
         if full:
@@ -769,7 +843,7 @@ def main():
                 c5["cpu_baseline"] = cpu_baseline(300000, 1024, backward=False, budget_s=5.0, unit="frames/s")
             pre_cfgs["c5"], pre_cfgs["c1"] = _brief(c5), _brief(c1)
             torch.cuda.empty_cache()
-        out = run_sds(ctx, args.config, dtype=args.dtype, views=args.views, steps=args.steps, warmup=args.warmup)
+        out = run_sds(ctx, args.config, dtype=args.dtype, views=args.views, steps=args.steps, warmup=args.warmup, dump=args.dump_outputs)
         if full:
             # everything the other BASELINE.json configurations and the precision trade need, inside the one line the driver records
             rk = ("kernel", "achieved", "peak", "frac", "mfma_all")
@@ -812,6 +886,9 @@ def main():
         if cpu_ok and ctx.rank == 0 and args.config in ("c2", "c3"):
             out["cpu_baseline"] = cpu_baseline(out["config"]["gaussians"], out["config"]["resolution"])
     if ctx.rank == 0:
+        if not (args.headline_only or args.all_configs):
+            # the default line stays short (about 2 KB): the per-kernel blocks give way to their headline numbers
+            out = {k: v for k, v in out.items() if k not in ("roofline", "kernel_ms_per_step")} | flat_scalars(out, {}, {})
         print(json.dumps(out), flush=True)
     if ctx.dist is not None:
         ctx.dist.destroy_process_group()

@@ -47,8 +47,8 @@ python tools/steady_stats.py $OUT/c5 profiles/${R}_c5_frame_kernel_stats.csv
 fi
 # bench lines (the default command, then the two other BASELINE configs)
 if has bench; then
-# the default command carries c1 / c2 / c4 (8 views on one GPU) / c5 and the fp32 line as attachments
-T0=$(date +%s); timeout 900 python bench.py > $OUT/bench_default.log 2>&1; echo "default bench.py run: $(( $(date +%s) - T0 )) s" | tee $OUT/bench_default.time; grep '^{"metric"' $OUT/bench_default.log | tail -1 > profiles/${R}_bench_line.json
+# --all-configs carries c1 / c2 / c4 (8 views on one GPU) / c5 and the other precisions as attachments
+T0=$(date +%s); timeout 900 python bench.py --all-configs > $OUT/bench_default.log 2>&1; echo "default bench.py run: $(( $(date +%s) - T0 )) s" | tee $OUT/bench_default.time; grep '^{"metric"' $OUT/bench_default.log | tail -1 > profiles/${R}_bench_line.json
 fi
 has calib && bash tools/calib_fetch.sh $R > $OUT/calib.log 2>&1
 has calib && tail -20 $OUT/calib.log
