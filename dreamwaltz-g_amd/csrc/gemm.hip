@@ -16,6 +16,7 @@
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_gemm.h"
 #include <cstdlib>
+#include <type_traits>
 
 // The 16-bit operand type of this translation unit.  gemm.hip itself is the bf16 (+ exact-f32) unit; gemm_f16.hip re-includes it with
 // DWG_GEMM_F16_TU defined: the same kernels on _Float16 operands (v_mfma_f32_32x32x16_f16) for the fp16-storage plans -- the reference's
@@ -62,9 +63,6 @@ struct GemmP {
     int act; float alpha;
     int out_bf16, res_bf16, bias_per_row, splitk, accumulate;
     float* ws;          // split-K slab workspace [splitk][M][N] (nullptr: atomicAdd into C)
-    int* cnt;           // per-tile arrival counters (workspace header, zero between launches): the LAST slice of a tile sums the slabs and
-                        // stores C inside the GEMM kernel -- no k_splitk_epilogue launch (nullptr: the separate reduce launch)
-    int dbg;            // DWG_GEMM_DEBUG (timing experiments, results are garbage): 1 = k_gemm_glds skips LDS reads + MFMAs, 2 = skips the tile loads
     int bias_row_div;   // > 0: bias index = (row / bias_row_div) * bias_ld + col  (per-image channel bias: conv bias + time embedding)
     long long bias_ld;
     ConvP conv;
@@ -374,91 +372,9 @@ template <int BN, int BM = 128> struct EpiLds {
 
 // RowFn: tile-local row (0..BM-1) -> global output row, or -1 (outside the problem).  BM rows, NT threads (128 / 256 for the four-wave
 // kernels; 256 x 128 and 128 x 256 tiles on eight waves: round 6)
-// 16-byte accesses at DEVICE scope (relaxed agent-scope atomics on the two 8-byte halves: sc1 -- written through / fetched past the
-// XCD-private L2): what lets slabs cross XCDs inside one kernel WITHOUT release / acquire fences -- a fence writes back and invalidates
-// the whole L2 (measured: the step went from 24 to 42 ms with __threadfence() here).
-__device__ __forceinline__ void st_agent4(float* ptr, const float4& v) {
-    unsigned long long* u = reinterpret_cast<unsigned long long*>(ptr);
-    const unsigned long long lo = (unsigned long long)__float_as_uint(v.x) | ((unsigned long long)__float_as_uint(v.y) << 32);
-    const unsigned long long hi = (unsigned long long)__float_as_uint(v.z) | ((unsigned long long)__float_as_uint(v.w) << 32);
-    __hip_atomic_store(u, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(u + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float4 ld_agent4(const float4* ptr) {
-    const unsigned long long* u = reinterpret_cast<const unsigned long long*>(ptr);
-    const unsigned long long lo = __hip_atomic_load(u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long hi = __hip_atomic_load(u + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float4(__uint_as_float((unsigned)lo), __uint_as_float((unsigned)(lo >> 32)), __uint_as_float((unsigned)hi),
-                       __uint_as_float((unsigned)(hi >> 32)));
-}
-
-// Split-K without a reduce launch: every slice of a tile has written its slab (above); the workgroup that arrives LAST at the tile's counter
-// sums the slabs in slice order and stores C through the same epilogue_store4 as k_splitk_epilogue -- the same additions in the same order,
-// so the result does not depend on which slice arrives last (bit-identical to the two-launch path).  The slabs of the other slices were
-// written on other XCDs: they are stored and loaded at device scope (st_agent4 / ld_agent4) and every store has completed (vmcnt(0)) before
-// the workgroup's arrival is counted.  The counter goes back to zero for the next launch that uses this workspace.
-template <int BN, int BM, int NT, typename RowFn>
-__device__ __forceinline__ void splitk_reduce_in_kernel(const GemmP& p, float* sC, int n0, int tid, long long coff, long long roff, bool vec_ok,
-                                                     RowFn row_of, int tile_id) {
-    constexpr int C4 = BN / 4;
-    __builtin_amdgcn_s_waitcnt(0x0F70);             // vmcnt(0): this thread's slab stores have completed at device scope
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(sC);
-    if (tid == 0) {
-        const int arrived = atomicAdd(p.cnt + tile_id, 1);
-        const int last = arrived == p.splitk - 1;
-        if (last) atomicExch(p.cnt + tile_id, 0);
-        *flag = last;
-    }
-    __syncthreads();
-    if (!*flag) return;
-    // PB pieces x four slices in flight per round: one workgroup sums the whole tile, so the round count (memory latencies in a row) is its time
-    const long long n4 = ((long long)p.M * p.N) >> 2;
-    constexpr int PIECES = BM * C4 / NT, PB = PIECES % 4 == 0 ? 4 : 1;   // (8 x 4 float4 in flight spills the 256-register kernels)
-    static_assert(BM * C4 % NT == 0, "whole pieces per thread");
-#pragma unroll 1
-    for (int k0 = 0; k0 < PIECES; k0 += PB) {
-        const float4* src[PB];
-        int row[PB], col[PB];
-        float4 a[PB];
-#pragma unroll
-        for (int j = 0; j < PB; j++) {
-            const int idx = tid + (k0 + j) * NT, rl = idx / C4, c4 = idx - rl * C4;
-            row[j] = row_of(rl); col[j] = n0 + c4 * 4;
-            if (col[j] >= p.N) row[j] = -1;
-            src[j] = reinterpret_cast<const float4*>(p.ws + (row[j] < 0 ? 0LL : (long long)row[j] * p.N + col[j]));     // (not stored: any valid piece)
-        }
-#pragma unroll 1
-        for (int s0 = 0; s0 < p.splitk; s0 += 4) {
-            float4 u[PB][4];
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-                if (s0 + t < p.splitk) {
-#pragma unroll
-                    for (int j = 0; j < PB; j++) u[j][t] = ld_agent4(src[j] + (long long)(s0 + t) * n4);
-                }
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-                if (s0 + t < p.splitk) {
-#pragma unroll
-                    for (int j = 0; j < PB; j++) {
-                        if (s0 + t == 0) a[j] = u[j][0];
-                        else { a[j].x += u[j][t].x; a[j].y += u[j][t].y; a[j].z += u[j][t].z; a[j].w += u[j][t].w; }
-                    }
-                }
-        }
-#pragma unroll
-        for (int j = 0; j < PB; j++) {
-            if (row[j] < 0) continue;
-            float v[4] = {a[j].x, a[j].y, a[j].z, a[j].w};
-            epilogue_store4(p, v, row[j], col[j], coff, roff, vec_ok);
-        }
-    }
-}
-
 template <int BN, int NPASS, int TM, int TN, bool LIGHT, int BM = 128, int NT = 256, typename RowFn>
 __device__ __forceinline__ void tile_epilogue_lds(const GemmP& p, f32x16 (&acc)[TM][TN], float* sC, int n0, int wm, int wn, int lane, int tid,
-                                                  int ks_id, long long coff, long long roff, RowFn row_of, int tile_id = 0) {
+                                                  int ks_id, long long coff, long long roff, RowFn row_of) {
     constexpr int LDC = EpiLds<BN, BM>::LDC, C4 = BN / 4, PR = BM / NPASS;      // PR rows per pass
     constexpr int BPP = BM / 32 / NPASS;                                         // 32-row blocks per pass
     static_assert(NT % C4 == 0 && (C4 & (C4 - 1)) == 0, "a thread keeps one column group");
@@ -552,9 +468,7 @@ __device__ __forceinline__ void tile_epilogue_lds(const GemmP& p, f32x16 (&acc)[
                     const float4 a = *reinterpret_cast<const float4*>(sC + rl * LDC + c4 * 4);
                     float v[4] = {a.x * p.alpha, a.y * p.alpha, a.z * p.alpha, a.w * p.alpha};
                     if (slab) {
-                        float* dst = p.ws + ((long long)ks_id * p.M + row) * p.N + col;
-                        if (p.cnt) st_agent4(dst, make_float4(v[0], v[1], v[2], v[3]));
-                        else *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+                        *reinterpret_cast<float4*>(p.ws + ((long long)ks_id * p.M + row) * p.N + col) = make_float4(v[0], v[1], v[2], v[3]);
                         continue;
                     }
                     if (col_bias) { v[0] += bc.x; v[1] += bc.y; v[2] += bc.z; v[3] += bc.w; }
@@ -601,8 +515,7 @@ __device__ __forceinline__ void tile_epilogue_lds(const GemmP& p, f32x16 (&acc)[
             if (p.splitk > 1) {
                 if (p.ws) {                              // slab, reduced by k_splitk_epilogue
                     float* dst = p.ws + ((long long)ks_id * p.M + row) * p.N + col;
-                    if (p.cnt) st_agent4(dst, make_float4(v[0], v[1], v[2], v[3]));       // (counters: N % 4 == 0, host-checked)
-                    else if ((p.N & 3) == 0) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+                    if ((p.N & 3) == 0) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
                     else {
 #pragma unroll
                         for (int e = 0; e < 4; e++) if (col + e < p.N) dst[e] = v[e];
@@ -616,9 +529,6 @@ __device__ __forceinline__ void tile_epilogue_lds(const GemmP& p, f32x16 (&acc)[
             }
             epilogue_store4<LIGHT>(p, v, row, col, coff, roff, vec_ok);
         }
-    }
-    if constexpr (!LIGHT) {
-        if (p.splitk > 1 && p.cnt) splitk_reduce_in_kernel<BN, BM, NT>(p, sC, n0, tid, coff, roff, vec_ok, row_of, tile_id);
     }
 }
 
@@ -671,21 +581,14 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue(GemmP p) {
     }
 }
 
-// the reduce launch of a split-K product whose kernel did not reduce in place (no counters: GemmP::cnt)
+// the reduce launch of a split-K product with slabs
 static void launch_splitk_epilogue(const GemmP& p, hipStream_t stream) {
-    if (!(p.splitk > 1 && p.ws) || p.cnt) return;
+    if (!(p.splitk > 1 && p.ws)) return;
     long long n = (long long)p.M * p.N;
     if ((p.N & 3) == 0) n >>= 2;                 // four columns per thread
     int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
     DWG_LAUNCH("splitk_epilogue", k_splitk_epilogue, dim3(blocks), dim3(256), 0, stream, p);
 }
-// the in-kernel reduce needs one counter per output tile (the workspace header holds DWG_GEMM_WS_COUNTERS) and four-column pieces
-static GemmP with_counters(const GemmP& p, long long tiles) {
-    GemmP q = p;
-    if (!(q.cnt && q.splitk > 1 && q.ws && (q.N & 3) == 0 && tiles <= DWG_GEMM_WS_COUNTERS)) q.cnt = nullptr;
-    return q;
-}
-
 template <typename T, int BN, int AMODE, int BMODE>
 __global__ __launch_bounds__(256, (sizeof(T) == 4 || BN == 64) ? 2 : 1) void k_gemm(GemmP p) {   // <= 256 registers where they suffice: accumulators
                                                      // in arch VGPRs (see k_gemm_glds); the register-staged 16-bit 128 x 128 tile needs more
@@ -748,8 +651,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 || BN == 64) ? 2 : 1) void k_g
     constexpr int NPASS = EpiLds<BN>::passes((size_t)2 * (BM + BN) * LDT * sizeof(T));
     static_assert((size_t)2 * (BM + BN) * LDT * sizeof(T) >= EpiLds<BN>::bytes(NPASS), "epilogue staging fits in the operand stages");
     tile_epilogue_lds<BN, NPASS, TM, TN, false>(p, acc, reinterpret_cast<float*>(smem_raw), n0, wm, wn, lane, tid, ks_id, z1 * p.bC1 + z2 * p.bC2,
-                                         z1 * p.bR1 + z2 * p.bR2, [&](int rl) { const int r = m0 + rl; return r < p.M ? r : -1; },
-                                         (int)blockIdx.x * ntn + (int)(blockIdx.y % ntn));
+                                         z1 * p.bR1 + z2 * p.bR2, [&](int rl) { const int r = m0 + rl; return r < p.M ? r : -1; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -947,9 +849,7 @@ template <int BM, int BN> struct GldsGeom {
     static constexpr int WN = BN / 64, WM = (BM == 128 && BN == 64) ? 4 : BM / 64, NW = WM * WN, NT = NW * 64, TM = BM / WM / 32, TN = 2;
 };
 
-// DBG (timing experiments only, results are garbage; DWG_GEMM_DEBUG=n routes the conv-fast 128 x 64 and 256 x 128 launches here):
-//   1 = no fragment reads, no MFMAs (loads + barriers only)   2 = no tile loads (LDS reads + MFMAs + barriers)   3 = MFMAs only
-template <int BM, int BN, int AKIND, int S, int DBG = 0>
+template <int BM, int BN, int AKIND, int S>
 __device__ __forceinline__ void gemm_glds_body(const GemmP& p) {
     typedef GldsGeom<BM, BN> Geo;
     constexpr int WN = Geo::WN, WM = Geo::WM, NW = Geo::NW, NT = Geo::NT, TM = Geo::TM, TN = Geo::TN;
@@ -997,11 +897,10 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p) {
     GldsLoader<BN, false, NW> lb;
     la.init(A, p.sam, p.M, m0, kbeg, kend, p.conv);
     lb.init(B, p.sbn, p.N, n0, kbeg, kend, p.conv);
-    const int nk = DBG == 6 || DBG == 7 ? 0 : (kend > kbeg ? (kend - kbeg + 63) / 64 : 0);
+    const int nk = kend > kbeg ? (kend - kbeg + 63) / 64 : 0;
     constexpr int LPT = (BM + BN) * 128 / (NT * 16);    // direct-to-LDS loads per thread per stage
 #pragma unroll
     for (int s = 0; s < S - 1; s++) {
-        if (DBG == 7) break;
         la.issue(smem_raw + s * STAGE, p.conv); lb.issue(smem_raw + s * STAGE + ABYTES, p.conv);
         la.advance(p.conv); lb.advance(p.conv);
     }
@@ -1091,19 +990,19 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p) {
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) {
             if (ks + 1 < KS) {
-                if (DBG != 1 && DBG != 3) load_frags(cur, ks + 1, F[(ks + 1) & 1]);
+                load_frags(cur, ks + 1, F[(ks + 1) & 1]);
             } else {
                 wait_tile_and_lds();
                 __builtin_amdgcn_s_barrier();       // tile kt + 1 is in LDS for everybody; everybody is done reading tile kt
-                if (DBG != 1 && DBG != 3) load_frags(cnext, 0, F[0]);         // (past the last tile: a stage of zero-page / stale rows, never multiplied)
+                load_frags(cnext, 0, F[0]);         // (past the last tile: a stage of zero-page / stale rows, never multiplied)
             }
             __builtin_amdgcn_sched_barrier(0);      // the fragment reads stay AHEAD of the MFMAs that hide their latency
             if (ks == 0) {
                 // tile kt + S - 1 goes into the stage every wave finished reading before the barrier inside the PREVIOUS k-step
-                if (DBG != 2 && DBG != 3) { la.issue(smem_raw + nxt * STAGE, p.conv); lb.issue(smem_raw + nxt * STAGE + ABYTES, p.conv); }
+                la.issue(smem_raw + nxt * STAGE, p.conv); lb.issue(smem_raw + nxt * STAGE + ABYTES, p.conv);
                 la.advance(p.conv); lb.advance(p.conv);
             }
-            if (DBG != 1) mma(F[ks & 1]);
+            mma(F[ks & 1]);
             if (ks == 0) {
 #pragma unroll
                 for (int m = 0; m < MPS; m++) {
@@ -1130,9 +1029,8 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p) {
 #endif
     constexpr int NPASS = EpiLds<BN, BM>::passes((size_t)S * STAGE);
     static_assert((size_t)S * STAGE >= EpiLds<BN, BM>::bytes(NPASS), "epilogue staging fits in the operand stages");
-    if (DBG == 5) { if (acc[0][0][0] == 12345.f) reinterpret_cast<float*>(p.C)[0] = 1.f; return; }      // timing: no epilogue
     tile_epilogue_lds<BN, NPASS, TM, TN, false, BM, NT>(p, acc, reinterpret_cast<float*>(smem_raw), n0, wm, wn, lane, tid, ks_id, z1 * p.bC1 + z2 * p.bC2,
-                                         z1 * p.bR1 + z2 * p.bR2, [&](int rl) { const int r = m0 + rl; return r < p.M ? r : -1; }, tile);
+                                         z1 * p.bR1 + z2 * p.bR2, [&](int rl) { const int r = m0 + rl; return r < p.M ? r : -1; });
 }
 
 template <int BN, int AKIND, int S>
@@ -1147,23 +1045,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm_glds8(GemmP p) {
     static_assert(GldsGeom<BM, BN>::NT == 512, "eight waves");
     gemm_glds_body<BM, BN, AKIND, S>(p);
 }
-#ifdef DWG_GEMM_X_TU
-template <int DBG> __global__ __launch_bounds__(256, 2) void k_gemm_dbg4(GemmP p) { gemm_glds_body<128, 64, 2, 3, DBG>(p); }
-template <int DBG> __global__ __launch_bounds__(512, 2) void k_gemm_dbg8(GemmP p) { gemm_glds_body<256, 128, 2, 3, DBG>(p); }
-template <int DBG> static void launch_dbg(const GemmP& p, bool big, hipStream_t stream) {
-    if (big) {
-        const size_t lds = (size_t)3 * 384 * 128;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_dbg8<DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        dim3 grid(((p.M + 255) / 256) * ((p.N + 127) / 128) * (p.splitk > 1 ? p.splitk : 1));
-        hipLaunchKernelGGL((k_gemm_dbg8<DBG>), grid, dim3(512), lds, stream, p);
-    } else {
-        const size_t lds = (size_t)3 * 192 * 128;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_dbg4<DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        dim3 grid(((p.M + 127) / 128) * ((p.N + 63) / 64) * (p.splitk > 1 ? p.splitk : 1));
-        hipLaunchKernelGGL((k_gemm_dbg4<DBG>), grid, dim3(256), lds, stream, p);
-    }
-}
-#endif
 
 // Algorithmic flops of one launch for the profiler table: 2*M*N*K, with the zero taps of an input-dilated (strided-conv
 // dgrad) convolution not counted.
@@ -1176,9 +1057,14 @@ static double gemm_flops(const GemmP& p, int batch) {
     return f;
 }
 
-template <int BN, int AKIND, int S>
-static void launch_glds_s(const GemmP& p_, int batch, hipStream_t stream, const char* name) {
-    const GemmP p = with_counters(p_, (long long)((p_.M + 127) / 128) * ((p_.N + BN - 1) / BN));
+// Pipeline depth.  Measured on MI355X at HEAD of round 2 (bench.py, 2 vs 3 stages everywhere, average launch): the 128x64 tile gains from a
+// third stage (72 KiB of LDS still leaves the 2 workgroups per CU these small-M launches have anyway): conv fast path 24.6 -> 23.5 us,
+// plain rows 17.3 -> 15.6 us; the 128x128 tile loses (96 KiB -> ONE workgroup per CU: 44 -> 59 us, 122 -> 209 us), and so does the
+// generic im2col loader (38 -> 41 us: its per-stage index arithmetic is the cost there).  So: 3 stages for the narrow tile with the
+// plain-row / fast-conv loaders, 2 otherwise.
+template <int BN, int AKIND>
+static void launch_glds(const GemmP& p, int batch, hipStream_t stream, const char* name) {
+    constexpr int S = (BN == 64 && AKIND != 1) ? 3 : 2;
     size_t lds = (size_t)S * (128 + BN) * 128;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1187,18 +1073,16 @@ static void launch_glds_s(const GemmP& p_, int batch, hipStream_t stream, const 
     }
     dim3 grid(((p.M + 127) / 128) * ((p.N + BN - 1) / BN) * (p.splitk > 1 ? p.splitk : 1), 1, batch);
     // profiler symbols spelled as rocprofv3 prints the instantiation: k_gemm_glds<BN, AKIND, S>
-    static const char* const sym[2][2][4] = {{{"k_gemm_glds<64, 0, 2>", "k_gemm_glds<64, 1, 2>", "k_gemm_glds<64, 2, 2>", "k_gemm_glds<64, 3, 2>"},
-                                              {"k_gemm_glds<64, 0, 3>", "k_gemm_glds<64, 1, 3>", "k_gemm_glds<64, 2, 3>", "k_gemm_glds<64, 3, 3>"}},
-                                             {{"k_gemm_glds<128, 0, 2>", "k_gemm_glds<128, 1, 2>", "k_gemm_glds<128, 2, 2>", "k_gemm_glds<128, 3, 2>"},
-                                              {"k_gemm_glds<128, 0, 3>", "k_gemm_glds<128, 1, 3>", "k_gemm_glds<128, 2, 3>", "k_gemm_glds<128, 3, 3>"}}};
-    DWG_LAUNCH_W(name, sym[BN == 128][S == 3][AKIND], gemm_flops(p, batch), (k_gemm_glds<BN, AKIND, S>), grid, dim3(256), lds, stream, p);
+    static const char* const sym[2][4] = {{"k_gemm_glds<64, 0, 3>", "k_gemm_glds<64, 1, 2>", "k_gemm_glds<64, 2, 3>", "k_gemm_glds<64, 3, 3>"},
+                                          {"k_gemm_glds<128, 0, 2>", "k_gemm_glds<128, 1, 2>", "k_gemm_glds<128, 2, 2>", "k_gemm_glds<128, 3, 2>"}};
+    DWG_LAUNCH_W(name, sym[BN == 128][AKIND], gemm_flops(p, batch), (k_gemm_glds<BN, AKIND, S>), grid, dim3(256), lds, stream, p);
     launch_splitk_epilogue(p, stream);
 }
 
-// The eight-wave tiles: BM x BN = 256 x 128 | 128 x 256, 512 threads, S stages of 48 KiB (S = 3: 144 of the CU's 160 KiB)
-template <int BM, int BN, int AKIND, int S>
-static void launch_glds8(const GemmP& p_, int batch, hipStream_t stream, const char* name) {
-    const GemmP p = with_counters(p_, (long long)((p_.M + BM - 1) / BM) * ((p_.N + BN - 1) / BN));
+// The eight-wave tiles: BM x BN = 256 x 128 | 128 x 256, 512 threads, three stages of 48 KiB (144 of the CU's 160 KiB)
+template <int BM, int BN, int AKIND>
+static void launch_glds8(const GemmP& p, int batch, hipStream_t stream, const char* name) {
+    constexpr int S = 3;
     const size_t lds = (size_t)S * (BM + BN) * 128;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1207,32 +1091,11 @@ static void launch_glds8(const GemmP& p_, int batch, hipStream_t stream, const c
     }
     dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * (p.splitk > 1 ? p.splitk : 1), 1, batch);
     // (as rocprofv3 prints the instantiation: k_gemm_glds8<BM, BN, AKIND, S>)
-    static const char* const sym[2][2][4] = {
-        {{"k_gemm_glds8<256, 128, 0, 2>", "k_gemm_glds8<256, 128, 1, 2>", "k_gemm_glds8<256, 128, 2, 2>", "k_gemm_glds8<256, 128, 3, 2>"},
-         {"k_gemm_glds8<128, 256, 0, 2>", "k_gemm_glds8<128, 256, 1, 2>", "k_gemm_glds8<128, 256, 2, 2>", "k_gemm_glds8<128, 256, 3, 2>"}},
-        {{"k_gemm_glds8<256, 128, 0, 3>", "k_gemm_glds8<256, 128, 1, 3>", "k_gemm_glds8<256, 128, 2, 3>", "k_gemm_glds8<256, 128, 3, 3>"},
-         {"k_gemm_glds8<128, 256, 0, 3>", "k_gemm_glds8<128, 256, 1, 3>", "k_gemm_glds8<128, 256, 2, 3>", "k_gemm_glds8<128, 256, 3, 3>"}}};
-    DWG_LAUNCH_W(name, sym[S == 3][BN == 256][AKIND], gemm_flops(p, batch), (k_gemm_glds8<BM, BN, AKIND, S>), grid, dim3(512), lds, stream, p);
+    static const char* const sym[2][4] = {
+        {"k_gemm_glds8<256, 128, 0, 3>", "k_gemm_glds8<256, 128, 1, 3>", "k_gemm_glds8<256, 128, 2, 3>", "k_gemm_glds8<256, 128, 3, 3>"},
+        {"k_gemm_glds8<128, 256, 0, 3>", "k_gemm_glds8<128, 256, 1, 3>", "k_gemm_glds8<128, 256, 2, 3>", "k_gemm_glds8<128, 256, 3, 3>"}};
+    DWG_LAUNCH_W(name, sym[BN == 256][AKIND], gemm_flops(p, batch), (k_gemm_glds8<BM, BN, AKIND, S>), grid, dim3(512), lds, stream, p);
     launch_splitk_epilogue(p, stream);
-}
-template <int AKIND>
-static void launch_big(const GemmP& p, int bm, int batch, hipStream_t stream, const char* name) {
-    static const int stages = getenv("DWG_GEMM_BIG_STAGES") ? atoi(getenv("DWG_GEMM_BIG_STAGES")) : 3;
-    if (bm == 256) { if (stages >= 3) launch_glds8<256, 128, AKIND, 3>(p, batch, stream, name); else launch_glds8<256, 128, AKIND, 2>(p, batch, stream, name); }
-    else { if (stages >= 3) launch_glds8<128, 256, AKIND, 3>(p, batch, stream, name); else launch_glds8<128, 256, AKIND, 2>(p, batch, stream, name); }
-}
-
-// Pipeline depth.  Measured on MI355X at HEAD of round 2 (bench.py, DWG_GEMM_STAGES=2|3, average launch): the 128x64 tile gains from a
-// third stage (72 KiB of LDS still leaves the 2 workgroups per CU these small-M launches have anyway): conv fast path 24.6 -> 23.5 us,
-// plain rows 17.3 -> 15.6 us; the 128x128 tile loses (96 KiB -> ONE workgroup per CU: 44 -> 59 us, 122 -> 209 us), and so does the
-// generic im2col loader (38 -> 41 us: its per-stage index arithmetic is the cost there).  Default: 3 stages for the narrow tile with
-// the plain-row / fast-conv loaders, 2 otherwise; DWG_GEMM_STAGES forces one depth everywhere.
-template <int BN, int AKIND>
-static void launch_glds(const GemmP& p, int batch, hipStream_t stream, const char* name) {
-    static const int forced = getenv("DWG_GEMM_STAGES") ? atoi(getenv("DWG_GEMM_STAGES")) : 0;
-    const bool three = forced ? forced >= 3 : (BN == 64 && AKIND != 1);
-    if (three) launch_glds_s<BN, AKIND, 3>(p, batch, stream, name);
-    else launch_glds_s<BN, AKIND, 2>(p, batch, stream, name);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1242,196 +1105,8 @@ static void launch_glds(const GemmP& p, int batch, hipStream_t stream, const cha
 // 64-channel slab it brings the (8+2) x (16+2) halo patch into LDS ONCE (direct-to-LDS loads, same source-side XOR swizzle,
 // halo / out-of-image pixels from the zero page) and forms all nine taps from it; only the weight slab streams per tap.
 // L2->LDS bytes per flop drop by ~40 % (A: 16 KiB/tap -> 23 KiB/9 taps).
-// ---------------------------------------------------------------------------------------------------------------------
-template <int BN, bool SPLIT>      // SPLIT: split-K over 64-channel slabs (its own instantiation: the plain one keeps its register budget)
-__global__ __launch_bounds__(256, 2) void k_conv3x3_patch(GemmP p) {   // 2 waves per SIMD: LDS allows 2 workgroups per CU anyway
-    constexpr int PH = 8, PW = 16, HP = PH + 2, WP = PW + 2, NPIX = HP * WP;     // 180 patch pixels, 128 B each
-    constexpr int NPI = (NPIX + 7) / 8;                                          // 23 wave-instructions per patch
-    constexpr int WN = BN / 64, WM = 4 / WN, TM = 128 / WM / 32, TN = 2;
-    constexpr int PBYTES = NPI * 8 * 128, BBYTES = BN * 128;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];     // [2 patches][2 weight tiles]
-    unsigned char* sP = smem_raw;
-    unsigned char* sB = smem_raw + 2 * PBYTES;
-    const ConvP& cv = p.conv;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int tiles_x = (cv.Wout + PW - 1) / PW, tiles_y = (cv.Hout + PH - 1) / PH;
-    const int nimg = p.M / (cv.Hout * cv.Wout);
-    const int gm = nimg * tiles_y * tiles_x, ntn = (p.N + BN - 1) / BN;
-    int id = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg / 8, r = nwg % 8, xcd = id % 8, loc = id / 8;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
-    int ks_id = 0;                                        // split-K slice: a contiguous range of 64-channel slabs
-    if constexpr (SPLIT) { ks_id = id / (gm * ntn); id -= ks_id * gm * ntn; }
-    const int mt = id / ntn, n0 = (id % ntn) * BN;
-    const int img = mt / (tiles_y * tiles_x), trem = mt % (tiles_y * tiles_x);
-    const int y0 = (trem / tiles_x) * PH, x0 = (trem % tiles_x) * PW;
-    const HT* X = reinterpret_cast<const HT*>(p.A) + (long long)img * cv.Hin * cv.Win * cv.Cin;
-    const HT* Wt = reinterpret_cast<const HT*>(p.B);
-    const HT* zero = reinterpret_cast<const HT*>(g_zero16);
-    const int sub = lane >> 3, lg0 = (lane & 7) ^ (sub >> 1);      // logical chunk of an even 8-row block; odd: ^ 4
-
-    // patch loader state: this wave issues patch instructions wave, wave+4, ... ; lane -> patch pixel (inst*8 + sub)
-    auto issue_patch = [&](int cc, unsigned char* dst) {
-        const int wv = __builtin_amdgcn_readfirstlane(wave);
-        for (int inst = wv; inst < NPI; inst += 4) {
-            const int pi = inst * 8 + sub;
-            const int py = pi / WP, px = pi - py * WP;
-            const int iy = y0 - 1 + py, ix = x0 - 1 + px;
-            const bool ok = pi < NPIX && iy >= 0 && iy < cv.Hin && ix >= 0 && ix < cv.Win;
-            const int logical = lg0 ^ ((inst & 1) << 2);
-            const HT* src = ok ? X + ((long long)iy * cv.Win + ix) * cv.Cin + cc * 64 + logical * 8 : zero;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(dst + inst * 8 * 128), 16, 0, 0);
-        }
-    };
-    // weight slab loader: rows n0 .. n0+BN of Wt[Cout][9*Cin], columns (tap*Cin + cc*64) .. +64.  Row pointers (with the lane's
-    // swizzled chunk folded in) are fixed for the whole kernel; per step only a wave-uniform column offset is added.
-    constexpr int NJW = BN / 32;
-    const HT* wrow[NJW];
-    {
-        const int wv = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-        for (int j = 0; j < NJW; j++) {
-            const int r = n0 + (wv * NJW + j) * 8 + sub;
-            wrow[j] = r < p.N ? Wt + (long long)r * p.sbn + (lg0 ^ ((j & 1) << 2)) * 8 : nullptr;
-        }
-    }
-    auto issue_w = [&](int cc, int tap, unsigned char* dst) {
-        const int wv = __builtin_amdgcn_readfirstlane(wave);
-        const long long kofs = (long long)tap * cv.Cin + cc * 64;          // wave-uniform
-#pragma unroll
-        for (int j = 0; j < NJW; j++) {
-            const HT* src = wrow[j] ? wrow[j] + kofs : zero;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(dst + (wv * NJW + j) * 8 * 128), 16, 0, 0);
-        }
-    };
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
-#ifdef DWG_GEMM_X_TU
-    f32x16 acx[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acx[i][j][r] = 0.f;
-#endif
-    // this lane's output pixels (rows of the A operand): r = (wm*TM + i)*32 + (lane & 31) -> (oy, ox) = (r >> 4, r & 15)
-    int pbase[TM];
-#pragma unroll
-    for (int i = 0; i < TM; i++) {
-        const int r = (wm * TM + i) * 32 + (lane & 31);
-        pbase[i] = (r >> 4) * WP + (r & 15);
-    }
-    int cc0 = 0, ncc = cv.Cin / 64;
-    if constexpr (SPLIT) {
-        const int per = (ncc + p.splitk - 1) / p.splitk;
-        cc0 = ks_id * per; ncc = min(ncc, cc0 + per);
-    }
-    const int frow = lane & 31, fx = (lane >> 1) & 7, fh = lane >> 5;
-    if constexpr (SPLIT) {
-        if (cc0 < ncc) { issue_patch(cc0, sP + (cc0 & 1) * PBYTES); issue_w(cc0, 0, sB + ((cc0 & 1) ? BBYTES : 0)); }
-    } else {
-        issue_patch(0, sP);
-        issue_w(0, 0, sB);
-    }
-    // 9 taps unrolled: the tap's patch offset is an immediate and there is no step -> (slab, tap) division in the loop
-    for (int cc = cc0; cc < ncc; cc++) {
-        const unsigned char* pa = sP + (cc & 1) * PBYTES;
-#ifdef DWG_GEMM_X_TU
-        // two accumulator sets leave no room for the 9 x TM x 4 loop-invariant fragment addresses the compiler otherwise hoists out of this loop
-        // (304 bytes of scratch per lane in the 128-wide instantiation): launder the pixel bases so they are recomputed next to their reads
-#pragma unroll
-        for (int i = 0; i < TM; i++) asm volatile("" : "+v"(pbase[i]));
-#endif
-#pragma unroll
-        for (int tap = 0; tap < 9; tap++) {
-            const int par = (cc + tap) & 1;                     // step parity: 9 steps per slab
-            __syncthreads();                                    // everything issued so far has landed; older buffers are free
-            if (tap < 8) issue_w(cc, tap + 1, sB + (par ^ 1) * BBYTES);
-            else if (cc + 1 < ncc) issue_w(cc + 1, 0, sB + (par ^ 1) * BBYTES);
-            if (tap == 0 && cc + 1 < ncc) issue_patch(cc + 1, sP + ((cc + 1) & 1) * PBYTES);   // a full slab ahead
-            const unsigned char* tb = sB + par * BBYTES + (wn * 64 + frow) * 128;
-            const int toff = (tap / 3) * WP + (tap % 3);
-#ifdef DWG_GEMM_X_TU
-#pragma unroll
-            for (int ks = 0; ks < 2; ks++) {
-                const int cl = ks * 4 + fh * 2;              // hi chunk; the lo chunk is cl + 1 (see k_gemm_glds)
-                bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-                for (int i = 0; i < TM; i++) {
-                    const int pi = pbase[i] + toff, sw = (pi >> 1) & 7;
-                    ah[i] = *reinterpret_cast<const bf16x8*>(pa + pi * 128 + ((cl ^ sw) << 4));
-                    al[i] = *reinterpret_cast<const bf16x8*>(pa + pi * 128 + (((cl + 1) ^ sw) << 4));
-                }
-#pragma unroll
-                for (int j = 0; j < TN; j++) {
-                    bh[j] = *reinterpret_cast<const bf16x8*>(tb + j * 32 * 128 + ((cl ^ fx) << 4));
-                    bl[j] = *reinterpret_cast<const bf16x8*>(tb + j * 32 * 128 + (((cl + 1) ^ fx) << 4));
-                }
-#pragma unroll
-                for (int i = 0; i < TM; i++)
-#pragma unroll
-                    for (int j = 0; j < TN; j++) acc[i][j] = DWG_MFMA16(bh[j], ah[i], acc[i][j]);   // transposed
-#pragma unroll
-                for (int i = 0; i < TM; i++)
-#pragma unroll
-                    for (int j = 0; j < TN; j++) acx[i][j] = DWG_MFMA16(bl[j], ah[i], acx[i][j]);
-#pragma unroll
-                for (int i = 0; i < TM; i++)
-#pragma unroll
-                    for (int j = 0; j < TN; j++) acx[i][j] = DWG_MFMA16(bh[j], al[i], acx[i][j]);
-            }
-#else
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                const int cl = ks * 2 + fh;
-                bf16x8 af[TM], bf[TN];
-#pragma unroll
-                for (int i = 0; i < TM; i++) {
-                    const int pi = pbase[i] + toff;
-                    af[i] = *reinterpret_cast<const bf16x8*>(pa + pi * 128 + ((cl ^ ((pi >> 1) & 7)) << 4));
-                }
-#pragma unroll
-                for (int j = 0; j < TN; j++) bf[j] = *reinterpret_cast<const bf16x8*>(tb + j * 32 * 128 + ((cl ^ fx) << 4));
-#pragma unroll
-                for (int i = 0; i < TM; i++)
-#pragma unroll
-                    for (int j = 0; j < TN; j++) acc[i][j] = DWG_MFMA16(bf[j], af[i], acc[i][j]);   // transposed
-            }
-#endif
-        }
-    }
-#ifdef DWG_GEMM_X_TU
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = fmaf(acx[i][j][r], DWG_X_LO_INV, acc[i][j][r]);
-#endif
-    // epilogue: tile-local row rr <-> output pixel (y0 + rr / 16, x0 + rr % 16) of image img
-    constexpr int NPASS = EpiLds<BN>::passes((size_t)2 * PBYTES + 2 * BBYTES);
-    static_assert((size_t)2 * PBYTES + 2 * BBYTES >= EpiLds<BN>::bytes(NPASS), "epilogue staging fits in the patch / weight buffers");
-    tile_epilogue_lds<BN, NPASS, TM, TN, !SPLIT>(p, acc, reinterpret_cast<float*>(smem_raw), n0, wm, wn, lane, tid, ks_id, 0, 0, [&](int rr) {
-        const int y = y0 + (rr >> 4), x = x0 + (rr & 15);
-        return (y < cv.Hout && x < cv.Wout) ? (img * cv.Hout + y) * cv.Wout + x : -1;
-    }, id);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Round 6: the LDS-patch convolution with a PIPELINED step.  k_conv3x3_patch above runs, per (64-channel slab, tap): __syncthreads() [= wait
-// for EVERY outstanding load: the next tap's weight tile was issued one step earlier, so its latency is exposed each step] -> issue -> read
-// fragments -> wait -> MFMAs.  Here (same data layout, same arithmetic, same results):
+// The step is pipelined (round 6: a __syncthreads() per (64-channel slab, tap) step -- a wait for EVERY outstanding load -- exposed the
+// latency of the next tap's weight tile each step):
 //   * NBS weight stages: the tile of step g + NBS - 1 is issued in step g and awaited by COUNT (s_waitcnt vmcnt(N), N a compile-time
 //     constant per unrolled tap: every wave issues the same number of loads per step -- the last patch instruction is duplicated where the
 //     patch does not divide evenly -- and steps past the end load from the zero page);
@@ -1440,6 +1115,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_patch(GemmP p) {   // 2 wave
 //   * the step's loads are issued between its first slab's MFMAs;
 //   * NW = 8: a 16 x 16-pixel tile (256 rows) x BN = 128 on eight waves -- half the weight-tile traffic per multiply-add of the 8 x 16 tile,
 //     one workgroup per CU -- for the layers whose grid still fills the chip (the VAE's, the 32^2 / 16^2 levels with split-K).
+// SPLIT: split-K over 64-channel slabs (its own instantiation: the plain one keeps its register budget).
 // ---------------------------------------------------------------------------------------------------------------------
 template <bool V> struct BoolC { static constexpr bool value = V; };
 template <int BN, int NW> struct Patch2Geom {
@@ -1685,17 +1361,16 @@ __global__ __launch_bounds__(NW * 64, 2) void k_conv3x3_patch2(GemmP p) {
     tile_epilogue_lds<BN, NPASS, TM, TN, !SPLIT, BM, NT>(p, acc, reinterpret_cast<float*>(smem_raw), n0, wm, wn, lane, tid, ks_id, 0, 0, [&](int rr) {
         const int y = y0 + rr / PW, x = x0 + rr % PW;
         return (y < cv.Hout && x < cv.Wout) ? (img * cv.Hout + y) * cv.Wout + x : -1;
-    }, id);
+    });
 }
 
 template <int BN, int NW, int NBS>
-static void launch_conv3x3_patch2(const GemmP& p_, hipStream_t stream, const char* name) {
+static void launch_conv3x3_patch2(const GemmP& p, hipStream_t stream, const char* name) {
     typedef Patch2Geom<BN, NW> G;
     const size_t lds = (size_t)2 * G::PBYTES + (size_t)NBS * G::BBYTES;
-    const ConvP& cv = p_.conv;
-    const int nimg = p_.M / (cv.Hout * cv.Wout);
+    const ConvP& cv = p.conv;
+    const int nimg = p.M / (cv.Hout * cv.Wout);
     const int gm = nimg * ((cv.Hout + G::PH - 1) / G::PH) * ((cv.Wout + G::PW - 1) / G::PW);
-    const GemmP p = with_counters(p_, (long long)gm * ((p_.N + BN - 1) / BN));
     dim3 grid(gm * ((p.N + BN - 1) / BN) * (p.splitk > 1 ? p.splitk : 1));
     static bool attr_set = false;
     if (!attr_set) {
@@ -1715,33 +1390,8 @@ static void launch_conv3x3_patch2(const GemmP& p_, hipStream_t stream, const cha
     launch_splitk_epilogue(p, stream);
 }
 
-template <int BN>
-static void launch_conv3x3_patch(const GemmP& p_, hipStream_t stream, const char* name) {
-    constexpr int NPI = (10 * 18 + 7) / 8;
-    const size_t lds = (size_t)2 * NPI * 8 * 128 + (size_t)2 * BN * 128;
-    const ConvP& cv = p_.conv;
-    const int nimg = p_.M / (cv.Hout * cv.Wout);
-    const int gm = nimg * ((cv.Hout + 7) / 8) * ((cv.Wout + 15) / 16);
-    const GemmP p = with_counters(p_, (long long)gm * ((p_.N + BN - 1) / BN));
-    dim3 grid(gm * ((p.N + BN - 1) / BN) * (p.splitk > 1 ? p.splitk : 1));
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_patch<BN, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_patch<BN, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    if (p.splitk > 1 && p.ws)
-        DWG_LAUNCH_W(name, (BN == 64 ? "k_conv3x3_patch<64, true>" : "k_conv3x3_patch<128, true>"), gemm_flops(p, 1),
-                     (k_conv3x3_patch<BN, true>), grid, dim3(256), lds, stream, p);
-    else
-        DWG_LAUNCH_W(name, (BN == 64 ? "k_conv3x3_patch<64, false>" : "k_conv3x3_patch<128, false>"), gemm_flops(p, 1), (k_conv3x3_patch<BN, false>), grid,
-                     dim3(256), lds, stream, p);
-    launch_splitk_epilogue(p, stream);
-}
-
 template <typename T, int BN, int AMODE, int BMODE>
-static void launch(const GemmP& p_, int batch, hipStream_t stream, const char* name) {
-    const GemmP p = with_counters(p_, (long long)((p_.M + 127) / 128) * ((p_.N + BN - 1) / BN));
+static void launch(const GemmP& p, int batch, hipStream_t stream, const char* name) {
     constexpr int LDT = TT<T>::BK + TT<T>::PAD;
     size_t lds = (size_t)2 * (128 + BN) * LDT * sizeof(T);
     dim3 grid((p.M + 127) / 128, ((p.N + BN - 1) / BN) * (p.splitk > 1 ? p.splitk : 1), batch);
@@ -1771,27 +1421,35 @@ static void dispatch_a(const GemmP& p, int amode, int bmode, int batch, hipStrea
 }
 
 static int batch_of(const dwg_gemm_desc* d) { return d->batch1 * d->batch2; }
+
+// Mid-size layers (e.g. 64x64 latents, N = 320): 128x128 tiles give < 1 workgroup per CU and waste the last n-tile; 128x64 tiles double the
+// workgroup count (3 resident per CU) -- latency hiding beats operand reuse there
 static int tile_bn(const dwg_gemm_desc* d) {
     if (d->N <= 64) return 64;
-    {
-        long long blocks128 = (long long)((d->M + 127) / 128) * ((d->N + 127) / 128) * batch_of(d);
-        if (blocks128 < 256 && getenv("DWG_GEMM_NO_NARROW") == nullptr) return 64;
-    }
-    return 128;
+    const long long blocks128 = (long long)((d->M + 127) / 128) * ((d->N + 127) / 128) * batch_of(d);
+    return blocks128 < 256 ? 64 : 128;
+}
+
+// A grid of `wgs` workgroups on the 256 CUs is worth launching when it has at least kMinWgs of them and no round less than 80 % full: a grid
+// that leaves a fifth of the CUs idle, or spills a few workgroups into a second round, loses to the smaller tiles' finer grain
+constexpr int kCUs = 256, kMinWgs = 200;
+static bool fills_cus(long long wgs) {
+    const long long rounds = (wgs + kCUs - 1) / kCUs;
+    return wgs >= kMinWgs && wgs * 100 >= rounds * kCUs * 80;
 }
 
 // split-K factor for shapes that cannot fill 256 CUs with 128 x BN output tiles (small-M layers: 8x8 / 16x16 latents)
+// round 6: 256 workgroups of >= 12 k-steps (was 512 of >= 8): a weight-streaming slice is bound by 128-byte row pieces out of HBM, and
+// longer slices stream better than more of them (8 x 8-latent convolution 33.4 -> 28.2 us; the step 25.33 -> 25.07 ms)
+constexpr int kSplitkTarget = 256;      // workgroups aimed at: ~1 per CU
+constexpr int kSplitkNoSplit = 384;     // output tiles from which a layer is not split
+constexpr int kSplitkMinSteps = 12;     // k-steps per slice
 static int auto_splitk(int M, int N, int K, int bn, int bk) {
-    // round 6: 256 workgroups of >= 12 k-steps (was 512 of >= 8): a weight-streaming slice is bound by 128-byte row pieces out of HBM, and
-    // longer slices stream better than more of them (8 x 8-latent convolution 33.4 -> 28.2 us; the step 25.33 -> 25.07 ms)
-    static const int target = getenv("DWG_SPLITK_TARGET") ? atoi(getenv("DWG_SPLITK_TARGET")) : 256;
-    static const int nosplit = getenv("DWG_SPLITK_NOSPLIT") ? atoi(getenv("DWG_SPLITK_NOSPLIT")) : 384;
-    static const int minsteps = getenv("DWG_SPLITK_MINSTEPS") ? atoi(getenv("DWG_SPLITK_MINSTEPS")) : 12;
     long long blocks = (long long)((M + 127) / 128) * ((N + bn - 1) / bn);
-    if (blocks >= nosplit || K < 2 * minsteps * bk) return 1;
+    if (blocks >= kSplitkNoSplit || K < 2 * kSplitkMinSteps * bk) return 1;
     if (2.0 * M * N * K < 4.0e8) return 1;      // tiny products are launch-bound: a second (reduce) launch costs more than it buys
-    long long sk = target / blocks;             // aim at ~1 workgroup per CU
-    long long kmax = K / (minsteps * bk);       // keep >= 12 k-steps per slice
+    long long sk = kSplitkTarget / blocks;
+    long long kmax = K / (kSplitkMinSteps * bk);
     if (sk > kmax) sk = kmax;
     if (sk > 16) sk = 16;
     return sk >= 2 ? (int)sk : 1;
@@ -1799,39 +1457,31 @@ static int auto_splitk(int M, int N, int K, int bn, int bk) {
 
 // Round 6: the eight-wave tiles.  Returns BM (256: the 256 x 128 tile, 128: the 128 x 256 tile) or 0 (keep the four-wave tiles), and the
 // split-K factor that fills the chip with ONE workgroup per CU.  Shape-only, so that the workspace query and the launch agree.
-//   * only where the k-loop is long enough to pay for the larger prologue / epilogue (K >= DWG_GEMM_BIG_MINK physical halves);
+//   * only where the k-loop is long enough to pay for the larger prologue / epilogue (K >= kBigMinK physical halves);
 //   * M >= 192: 256 x 128 when N fills whole 128-wide tiles (or is large); M <= 128: 128 x 256 for N >= 256;
-//   * layers with >= DWG_GEMM_BIG_MAXTILES big tiles already fill the chip with small tiles at full rate (the VAE): left alone.
+//   * layers with > kBigMaxTiles big tiles already fill the chip with small tiles at full rate (the VAE): left alone.
+constexpr int kBigMinK = 1280, kBigMaxTiles = 2048;
+constexpr int kBigMinSteps = 8, kBigSkMax = 24;     // split: >= 8 k-steps per slice, <= 24 slices
 static int big_tile(int M, int N, int K, int* splitk_out) {
-    static const int mode = getenv("DWG_GEMM_BIG") ? atoi(getenv("DWG_GEMM_BIG")) : 1;
-    static const int mink = getenv("DWG_GEMM_BIG_MINK") ? atoi(getenv("DWG_GEMM_BIG_MINK")) : 1280;
-    static const int skmax = getenv("DWG_GEMM_BIG_SKMAX") ? atoi(getenv("DWG_GEMM_BIG_SKMAX")) : 24;
-    static const int maxtiles = getenv("DWG_GEMM_BIG_MAXTILES") ? atoi(getenv("DWG_GEMM_BIG_MAXTILES")) : 2048;
-    static const int minsteps = getenv("DWG_GEMM_BIG_MINSTEPS") ? atoi(getenv("DWG_GEMM_BIG_MINSTEPS")) : 8;
-    static const int tall_only = getenv("DWG_GEMM_BIG_TALL_ONLY") ? atoi(getenv("DWG_GEMM_BIG_TALL_ONLY")) : 0;
-    if (splitk_out) *splitk_out = 1;
-    if (mode == 0 || K < mink) return 0;
+    *splitk_out = 1;
+    if (K < kBigMinK) return 0;
     int bm = 0;
     if (M >= 192) { if (N >= 128 && (N % 128 == 0 || N >= 640)) bm = 256; }
-    else if (N >= 256 && !tall_only) bm = 128;
+    else if (N >= 256) bm = 128;
     if (!bm) return 0;
     const int bn = bm == 256 ? 128 : 256;
     const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-    if (tiles > maxtiles) return 0;
-    static const int target = getenv("DWG_GEMM_BIG_TARGET") ? atoi(getenv("DWG_GEMM_BIG_TARGET")) : 256;     // one workgroup per CU
-    static const int minwg = getenv("DWG_GEMM_BIG_MINWG") ? atoi(getenv("DWG_GEMM_BIG_MINWG")) : 200;
+    if (tiles > kBigMaxTiles) return 0;
     long long sk = 1;
-    if (tiles < target) {
-        sk = target / tiles;            // FLOOR: tiles x sk must not exceed the CU count -- a 257th workgroup is a second round of the whole launch
-        const long long kmax = K / (minsteps * 64);
+    if (tiles < kCUs) {
+        sk = kCUs / tiles;              // FLOOR: tiles x sk must not exceed the CU count -- a 257th workgroup is a second round of the whole launch
+        const long long kmax = K / (kBigMinSteps * 64);
         if (sk > kmax) sk = kmax;
-        if (sk > skmax) sk = skmax;
+        if (sk > kBigSkMax) sk = kBigSkMax;
         if (sk < 1) sk = 1;
     }
-    // a grid that leaves a fifth of the CUs idle, or spills a few workgroups into a second round: the small tiles' finer grain wins
-    const long long wgs = tiles * sk, rounds = (wgs + target - 1) / target;
-    if (mode < 2 && (wgs < minwg || wgs * 100 < rounds * target * 80)) return 0;
-    if (splitk_out) *splitk_out = (int)sk;
+    if (!fills_cus(tiles * sk)) return 0;
+    *splitk_out = (int)sk;
     return bm;
 }
 
@@ -1843,6 +1493,150 @@ static int pick_mode(const void* base, long long srow, long long sk, int nrows, 
     if (sk == 1 && aligned && K % VEC == 0 && srow % VEC == 0) return MODE_KVEC;
     if (srow == 1 && aligned && nrows % VEC == 0 && sk % VEC == 0) return MODE_RVEC;
     return MODE_SCALAR;
+}
+
+// The split-K factor a descriptor gets on the four-wave tiles before the workspace caps it (splitk == 0: the library's choice)
+static int splitk_of(const dwg_gemm_desc* d) {
+    if (d->splitk > 1) return d->splitk;
+    if (d->splitk != 0 || d->act == DWG_ACT_GEGLU_PAIR) return 1;
+    return auto_splitk(d->M, d->N, d->K, tile_bn(d), d->dtype == DWG_DTYPE_HALF ? TT<HT>::BK : TT<float>::BK);
+}
+// slabs: one batch, and float4 pieces of C that k_splitk_epilogue indexes with 32 bits
+static bool slabs_possible(const dwg_gemm_desc* d) { return batch_of(d) == 1 && (long long)d->M * d->N < (1LL << 33); }
+// the largest split <= sk whose slabs fit the caller's workspace
+static long long fit_workspace(const dwg_gemm_desc* d, long long sk) {
+    while (sk > 1 && (size_t)sk * d->M * d->N * sizeof(float) > d->workspace_bytes) sk--;
+    return sk;
+}
+
+// What DWG_GEMM_FN launches for a descriptor: the kernel family, its tile, its loaders and its split-K factor.
+enum Family { FAM_GENERIC, FAM_GLDS, FAM_GLDS8, FAM_PATCH2 };
+struct Plan {
+    Family fam;         // register-staged k_gemm | k_gemm_glds | k_gemm_glds8 | k_conv3x3_patch2
+    int bm, bn, nw;     // workgroup tile BM x BN on NW waves
+    int amode, bmode;   // the operand loaders (MODE_*) of k_gemm
+    int akind;          // the A loader of k_gemm_glds / k_gemm_glds8 (ALoaderOf)
+    int splitk;         // contraction slices (1: none)
+    bool slabs;         // the slices write fp32 slabs into the workspace and k_splitk_epilogue sums them (false: atomicAdd into C)
+};
+
+// LDS-patch convolution: the halo patch of a 64-channel slab is loaded once for all nine taps (2.3x less L2 -> LDS traffic per flop than the
+// im2col loader, which is what bounds these layers).  The four-wave kernel from M = kPatchMinM on; below 64x64 latents it needs split-K over
+// the channel slabs to fill the chip.  DWG_CONV_PATCH_MINM overrides kPatchMinM (read per call: the tests drive the patch kernels below it).
+constexpr int kPatchMinM = 8192;
+// The eight-wave patch kernel runs one workgroup per CU, which exposes every tile's prologue (first patch from HBM) and epilogue (128 KB of
+// stores): with few steps per tile (the VAE's 512^2 / 256^2 layers: 36 - 72) the four-wave kernel's two workgroups per CU overlap them
+constexpr int kPatch8MinSteps = 100;
+
+// p: the launch parameters of d (operand strides; conv.enabled is false for a convolution that runs as a plain product)
+static int make_plan(const dwg_gemm_desc* d, const GemmP& p, Plan& pl) {
+    const bool half = d->dtype == DWG_DTYPE_HALF;
+#if defined(DWG_GEMM_F16_TU) || defined(DWG_GEMM_X_TU)
+    if (!half) return DWG_E_ARG;          // the exact-f32 kernels live in the bf16 unit
+#endif
+    pl = Plan{FAM_GENERIC, 128, tile_bn(d), 4, MODE_KVEC, MODE_KVEC, 0, d->splitk > 1 ? d->splitk : 1, false};
+    if (d->workspace && slabs_possible(d)) {
+        pl.splitk = (int)fit_workspace(d, splitk_of(d));
+        pl.slabs = pl.splitk > 1;
+    }
+    const long long ao[2] = {p.bA1, p.bA2}, bo[2] = {p.bB1, p.bB2};
+    if (p.conv.enabled) {
+        const int vec = half ? TT<HT>::VEC : TT<float>::VEC;
+        if (d->conv_cin % vec != 0 || ((uintptr_t)d->A % 16) != 0) return DWG_E_ARG;
+        if (d->A2 && (d->conv_cin1 % vec != 0 || d->conv_cin1 <= 0 || d->conv_cin1 >= d->conv_cin || ((uintptr_t)d->A2 % 16) != 0))
+            return DWG_E_ARG;
+        if (d->K != d->conv_kh * d->conv_kw * d->conv_cin) return DWG_E_ARG;
+        pl.amode = MODE_CONV;
+    } else {
+        pl.amode = half ? pick_mode<HT>(p.A, p.sam, p.sak, p.M, p.K, ao, 2) : pick_mode<float>(p.A, p.sam, p.sak, p.M, p.K, ao, 2);
+    }
+    pl.bmode = half ? pick_mode<HT>(p.B, p.sbn, p.sbk, p.N, p.K, bo, 2) : pick_mode<float>(p.B, p.sbn, p.sbk, p.N, p.K, bo, 2);
+    // exact-f32 operands (v_mfma_f32_32x32x2_f32): the avatar's MLPs, and every layer of the fp32 denoiser / VAE plans -- the precision the
+    // reference runs the 3DGS stage in (configs/__init__.py:236,241) -- take the register-staged kernel, incl. its im2col loader
+    if (!half) return DWG_OK;
+    if (pl.bmode != MODE_KVEC || (pl.amode != MODE_KVEC && pl.amode != MODE_CONV)) {
+#ifdef DWG_GEMM_X_TU
+        return DWG_E_ARG;     // split-precision operands exist only for the direct-to-LDS kernels (K-contiguous, 16-byte aligned rows)
+#else
+        return DWG_OK;
+#endif
+    }
+    const ConvP& cv = p.conv;
+    const char* minm = getenv("DWG_CONV_PATCH_MINM");
+    const int patch_min_m = minm ? atoi(minm) : kPatchMinM;
+    const bool patch_geom = pl.amode == MODE_CONV && batch_of(d) == 1 && d->conv_kh == 3 && d->conv_kw == 3 && d->conv_stride == 1 &&
+                            cv.dil == 1 && cv.up == 1 && d->conv_pad_t == 1 && d->conv_pad_l == 1 && !d->A2 && d->conv_cin % 64 == 0 &&
+                            d->conv_hout == d->conv_hin && d->conv_wout == d->conv_win && d->conv_wout >= 16 && d->conv_hout >= 8;
+    const int ncc = d->conv_cin / 64;     // 64-channel slabs
+    // Round 6: the eight-wave patch kernel (16 x 16-pixel tile x 128 columns) where whole 16 x 16 tiles cover the image and the grid -- with
+    // split-K over the 64-channel slabs when it has to -- still fills the chip; this also brings the 32^2 / 16^2 levels of the denoiser
+    // (M < 8192, split-K) onto the patch kernel
+    if (patch_geom && d->splitk <= 1 && d->conv_hout % 16 == 0 && d->conv_wout % 16 == 0 && (d->N % 128 == 0 || d->N >= 512)) {
+        const long long tiles8 = (long long)(d->M / 256) * ((d->N + 127) / 128);
+        long long sk = 1;
+        if (tiles8 < kMinWgs && d->workspace && d->splitk == 0 && slabs_possible(d)) {
+            sk = kCUs / tiles8;
+            if (sk > ncc / 2) sk = ncc / 2;
+            sk = fit_workspace(d, sk);
+            if (sk < 1) sk = 1;
+            const long long per = (ncc + sk - 1) / sk;
+            sk = (ncc + per - 1) / per;                          // no empty slices
+        }
+        const long long steps = (ncc + sk - 1) / sk * 9;
+        const bool worth = sk > 1 || steps >= kPatch8MinSteps || d->M < patch_min_m;
+        if (worth && fills_cus(tiles8 * sk) && (d->act == 0 || d->act == 3 || sk > 1)) {
+            pl = Plan{FAM_PATCH2, 256, 128, 8, MODE_CONV, pl.bmode, 0, (int)sk, sk > 1};
+            return DWG_OK;
+        }
+    }
+    // the four-wave patch kernel (8 x 16-pixel tiles); its unsplit epilogue has identity / SiLU only (apply_act<true>)
+    if (patch_geom && d->M >= patch_min_m && (d->act == 0 || d->act == 3 || pl.splitk > 1)) {
+        if (pl.splitk > 1) {
+            // the slice count for this kernel's tiling: (8x16 pixel tiles) x (N / BN) workgroups, >= 2 slabs per slice
+            const int gm = (d->M / (d->conv_hout * d->conv_wout)) * ((d->conv_hout + 7) / 8) * ((d->conv_wout + 15) / 16);
+            const int blocks = gm * ((d->N + pl.bn - 1) / pl.bn);
+            int sk = blocks >= 256 ? 1 : (384 + blocks - 1) / blocks;
+            if (sk > ncc / 2) sk = ncc / 2;
+            if (sk > pl.splitk) sk = pl.splitk;           // the workspace holds pl.splitk slabs
+            if (sk < 2) sk = 1;
+            pl.splitk = sk;
+            pl.slabs = pl.slabs && sk > 1;
+        }
+        pl.fam = FAM_PATCH2;
+        return DWG_OK;
+    }
+    const bool fast_geom = pl.amode == MODE_CONV && d->conv_cin % 64 == 0 && cv.dil == 1 && cv.up == 1 && d->conv_kh * d->conv_kw <= 32;
+    const bool cat_fast = d->A2 && d->conv_cin1 % 64 == 0 && (d->conv_cin - d->conv_cin1) % 64 == 0;
+    pl.akind = pl.amode != MODE_CONV ? 0 : (fast_geom && !d->A2 ? 2 : (fast_geom && cat_fast ? 3 : 1));
+    // the eight-wave tiles (round 6): long-K layers that do not take the LDS-patch kernel
+    int big_sk = 1;
+    const int big_bm = d->splitk <= 1 ? big_tile(d->M, d->N, d->K, &big_sk) : 0;
+    if (big_bm) {
+        if (d->act == DWG_ACT_GEGLU_PAIR || !d->workspace || !slabs_possible(d) || d->splitk == 1) big_sk = 1;
+        big_sk = (int)fit_workspace(d, big_sk);
+        const int bbn = big_bm == 256 ? 128 : 256;
+        const long long tiles = (long long)((d->M + big_bm - 1) / big_bm) * ((d->N + bbn - 1) / bbn) * batch_of(d);
+        if (fills_cus(tiles * big_sk)) {      // (else an unsplittable launch that would leave CUs idle)
+            pl = Plan{FAM_GLDS8, big_bm, bbn, 8, pl.amode, pl.bmode, pl.akind, big_sk, big_sk > 1};
+            return DWG_OK;
+        }
+    }
+    pl.fam = FAM_GLDS;
+    return DWG_OK;
+}
+
+template <typename T>
+static void launch_generic(const GemmP& p, const Plan& pl, int batch, hipStream_t s, const char* name) {
+    if (pl.bn == 64) dispatch_a<T, 64>(p, pl.amode, pl.bmode, batch, s, name);
+    else dispatch_a<T, 128>(p, pl.amode, pl.bmode, batch, s, name);
+}
+// f(std::integral_constant<int, akind>{}): the direct-to-LDS A loader as a template argument
+template <typename F>
+static void with_akind(int akind, F f) {
+    if (akind == 3) f(std::integral_constant<int, 3>{});
+    else if (akind == 2) f(std::integral_constant<int, 2>{});
+    else if (akind == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
 }
 
 }  // namespace
@@ -1888,6 +1682,8 @@ size_t dwg_gemm_workspace_bytes_x(const dwg_gemm_desc* d);
 int dwg_gemm_x(const dwg_gemm_desc* d, dwg_stream_t stream);
 #endif
 
+// The workspace is sized for the larger of the four-wave split (splitk_of) and the eight-wave tiles' split (big_tile).  The patch kernels
+// derive their own split in make_plan and cap it by the workspace they are given -- sizing for them too would change their split factors.
 size_t DWG_GEMM_WS_FN(const dwg_gemm_desc* d) {
 #if !defined(DWG_GEMM_F16_TU) && !defined(DWG_GEMM_X_TU)
     if (d && d->dtype == DWG_DTYPE_F16) return dwg_gemm_workspace_bytes_f16(d);
@@ -1898,15 +1694,13 @@ size_t DWG_GEMM_WS_FN(const dwg_gemm_desc* d) {
     if (!x_physical(d, &xd)) return 0;
     d = &xd;
 #endif
-    if (!d || d->batch1 * d->batch2 != 1 || d->M <= 0 || d->N <= 0) return 0;
-    if ((long long)d->M * d->N >= (1LL << 33)) return 0;       // k_splitk_epilogue indexes the float4 pieces of C with 32 bits
-    const int bn = tile_bn(d), bk = d->dtype == DWG_DTYPE_HALF ? TT<HT>::BK : TT<float>::BK;
-    int sk = d->splitk > 1 ? d->splitk : (d->splitk == 0 && d->act != DWG_ACT_GEGLU_PAIR ? auto_splitk(d->M, d->N, d->K, bn, bk) : 1);
-    if (d->dtype == DWG_DTYPE_HALF && d->splitk == 0 && d->act != DWG_ACT_GEGLU_PAIR) {      // the eight-wave tiles split deeper (one workgroup per CU)
+    if (!d || d->M <= 0 || d->N <= 0 || !slabs_possible(d)) return 0;
+    int sk = splitk_of(d);
+    if (d->dtype == DWG_DTYPE_HALF && d->splitk == 0 && d->act != DWG_ACT_GEGLU_PAIR) {
         int bsk = 1;
         if (big_tile(d->M, d->N, d->K, &bsk) && bsk > sk) sk = bsk;
     }
-    return sk > 1 ? (size_t)sk * d->M * d->N * sizeof(float) + DWG_GEMM_WS_HEADER_BYTES : 0;     // slabs + the tile-counter header
+    return sk > 1 ? (size_t)sk * d->M * d->N * sizeof(float) : 0;
 }
 
 int DWG_GEMM_FN(const dwg_gemm_desc* d, dwg_stream_t stream_) {
@@ -1926,16 +1720,7 @@ int DWG_GEMM_FN(const dwg_gemm_desc* d, dwg_stream_t stream_) {
     if (d->splitk > 1 && !d->workspace && (d->out_dtype != DWG_DTYPE_F32 || d->bias || d->residual || d->act)) return DWG_E_ARG;
     if (d->accumulate && d->out_dtype != DWG_DTYPE_F32) return DWG_E_ARG;
     if (d->act == DWG_ACT_GEGLU_PAIR && (d->N % 64 != 0 || d->residual || d->splitk > 1 || d->bias_per_row || d->bias_row_div)) return DWG_E_ARG;
-    // workspace_counters: the first DWG_GEMM_WS_HEADER_BYTES of the workspace are tile counters (zero between launches), the slabs follow
-    dwg_gemm_desc wd = *d;
-    int* ws_counters = nullptr;
-    if (wd.workspace && wd.workspace_counters) {
-        if (wd.workspace_bytes <= DWG_GEMM_WS_HEADER_BYTES || ((uintptr_t)wd.workspace & 15)) return DWG_E_ARG;
-        ws_counters = reinterpret_cast<int*>(wd.workspace);
-        wd.workspace = reinterpret_cast<char*>(wd.workspace) + DWG_GEMM_WS_HEADER_BYTES;
-        wd.workspace_bytes -= DWG_GEMM_WS_HEADER_BYTES;
-    }
-    d = &wd;
+    if ((uintptr_t)d->workspace & 15) return DWG_E_ARG;      // the slabs are written and summed in float4 pieces
     GemmP p;
     p.A = d->A; p.B = d->B; p.C = d->C; p.bias = d->bias; p.residual = d->residual;
     p.M = d->M; p.N = d->N; p.K = d->K;
@@ -1946,25 +1731,12 @@ int DWG_GEMM_FN(const dwg_gemm_desc* d, dwg_stream_t stream_) {
     p.bC1 = d->c_batch1_stride; p.bC2 = d->c_batch2_stride; p.bR1 = d->r_batch1_stride; p.bR2 = d->r_batch2_stride;
     p.act = d->act; p.alpha = d->alpha;
     p.out_bf16 = d->out_dtype == DWG_DTYPE_HALF; p.res_bf16 = d->residual_dtype == DWG_DTYPE_HALF;
-    p.bias_per_row = d->bias_per_row; p.splitk = d->splitk > 1 ? d->splitk : 1; p.accumulate = d->accumulate;
-    p.ws = nullptr; p.cnt = ws_counters;
-    static const int dbg = getenv("DWG_GEMM_DEBUG") ? atoi(getenv("DWG_GEMM_DEBUG")) : 0;
-    p.dbg = dbg;
-    {
-        const int bn = tile_bn(d), bk = d->dtype == DWG_DTYPE_HALF ? TT<HT>::BK : TT<float>::BK;
-        if (d->workspace && d->batch1 * d->batch2 == 1 && (long long)d->M * d->N < (1LL << 33)) {
-            int sk = d->splitk > 1 ? d->splitk : (d->splitk == 0 && d->act != DWG_ACT_GEGLU_PAIR ? auto_splitk(d->M, d->N, d->K, bn, bk) : 1);
-            while (sk > 1 && (size_t)sk * d->M * d->N * sizeof(float) > d->workspace_bytes) sk--;
-            p.splitk = sk;
-            if (sk > 1) p.ws = reinterpret_cast<float*>(d->workspace);
-        }
-    }
+    p.bias_per_row = d->bias_per_row; p.accumulate = d->accumulate;
     // A 1 x 1 / stride 1 / unpadded convolution over NHWC rows IS the plain product of the [M, Cin] row matrix: it takes the plain-row loader
-    // (no per-stage pixel arithmetic), DWG_CONV1X1_PLAIN=0: the convolution loader as before
-    static const bool conv1x1_plain = !(getenv("DWG_CONV1X1_PLAIN") && atoi(getenv("DWG_CONV1X1_PLAIN")) == 0);
-    const bool plain1x1 = conv1x1_plain && d->conv_enabled && d->conv_kh == 1 && d->conv_kw == 1 && d->conv_stride == 1 && d->conv_pad_t == 0 &&
+    // (no per-stage pixel arithmetic)
+    const bool plain1x1 = d->conv_enabled && d->conv_kh == 1 && d->conv_kw == 1 && d->conv_stride == 1 && d->conv_pad_t == 0 &&
                           d->conv_pad_l == 0 && d->conv_in_dilation <= 1 && d->conv_in_upsample <= 1 && !d->A2 && d->conv_hout == d->conv_hin &&
-                          d->conv_wout == d->conv_win && d->K == d->conv_cin && d->batch1 * d->batch2 == 1;
+                          d->conv_wout == d->conv_win && d->K == d->conv_cin && batch_of(d) == 1;
     if (plain1x1) { p.sam = d->conv_cin; p.sak = 1; }
     p.conv.enabled = d->conv_enabled && !plain1x1;
     p.conv.Cin = d->conv_cin; p.conv.Hin = d->conv_hin; p.conv.Win = d->conv_win; p.conv.Hout = d->conv_hout;
@@ -1973,158 +1745,42 @@ int DWG_GEMM_FN(const dwg_gemm_desc* d, dwg_stream_t stream_) {
     p.conv.up = d->conv_in_upsample > 1 ? d->conv_in_upsample : 1;
     p.conv.A2 = d->A2; p.conv.cin1 = d->A2 ? d->conv_cin1 : d->conv_cin;
     p.bias_row_div = d->bias_row_div; p.bias_ld = d->bias_ld > 0 ? d->bias_ld : d->N;
-    const int batch = d->batch1 * d->batch2;
+    Plan pl;
+    const int rc = make_plan(d, p, pl);
+    if (rc != DWG_OK) return rc;
+    p.splitk = pl.splitk;
+    p.ws = pl.slabs ? reinterpret_cast<float*>(d->workspace) : nullptr;
+    const int batch = batch_of(d);
     hipStream_t stream = (hipStream_t)stream_;
     const char* name = d->name ? d->name : (d->conv_enabled ? "conv_igemm" : "gemm");
-    bool narrow = d->N <= 64;
-    if (!narrow) {
-        // mid-size layers (e.g. 64x64 latents, N = 320): 128x128 tiles give < 1 workgroup per CU and waste the last n-tile;
-        // 128x64 tiles double the workgroup count (3 resident per CU) -- latency hiding beats operand reuse there
-        long long blocks128 = (long long)((d->M + 127) / 128) * ((d->N + 127) / 128) * batch_of(d);
-        if (blocks128 < 256 && getenv("DWG_GEMM_NO_NARROW") == nullptr) narrow = true;
-    }
-    if (d->dtype == DWG_DTYPE_HALF) {
-        typedef HT T;
-        int amode, bmode;
-        long long ao[2] = {p.bA1, p.bA2}, bo[2] = {p.bB1, p.bB2};
-        if (d->conv_enabled && !plain1x1) {
-            if (d->conv_cin % 8 != 0 || ((uintptr_t)d->A % 16) != 0) return DWG_E_ARG;
-            if (d->A2 && (d->conv_cin1 % 8 != 0 || d->conv_cin1 <= 0 || d->conv_cin1 >= d->conv_cin || ((uintptr_t)d->A2 % 16) != 0))
-                return DWG_E_ARG;
-            if (d->K != d->conv_kh * d->conv_kw * d->conv_cin) return DWG_E_ARG;
-            amode = MODE_CONV;
-        } else amode = pick_mode<T>(p.A, p.sam, p.sak, p.M, p.K, ao, 2);
-        bmode = pick_mode<T>(p.B, p.sbn, p.sbk, p.N, p.K, bo, 2);
-        const bool glds_ok = bmode == MODE_KVEC && (amode == MODE_KVEC || amode == MODE_CONV) && !d->force_register_staging;
-        // LDS-patch convolution: the halo patch of a 64-channel slab is loaded once for all nine taps (2.3x less L2 -> LDS traffic
-        // per flop than the im2col loader, which is what bounds these layers).  Below 64x64 latents it needs split-K over the
-        // channel slabs to fill the chip; DWG_CONV_PATCH_MINM = smallest M it is used for (experiment switch).
-        const int patch_min_m = getenv("DWG_CONV_PATCH_MINM") ? atoi(getenv("DWG_CONV_PATCH_MINM")) : 8192;
-        static const int patch2 = getenv("DWG_CONV_PATCH2") ? atoi(getenv("DWG_CONV_PATCH2")) : 1;            // 0: the round-2 kernel
-        static const int patch2_low = getenv("DWG_CONV_PATCH2_LOWRES") ? atoi(getenv("DWG_CONV_PATCH2_LOWRES")) : 1;
-        const bool patch_geom = glds_ok && amode == MODE_CONV && batch == 1 && d->conv_kh == 3 && d->conv_kw == 3 &&
-                                d->conv_stride == 1 && p.conv.dil == 1 && p.conv.up == 1 && d->conv_pad_t == 1 && d->conv_pad_l == 1 &&
-                                !d->A2 && d->conv_cin % 64 == 0 && d->conv_hout == d->conv_hin && d->conv_wout == d->conv_win &&
-                                d->conv_wout >= 16 && d->conv_hout >= 8 && getenv("DWG_CONV_NO_PATCH") == nullptr;
-        bool patch_ok = patch_geom && d->M >= patch_min_m && (d->act == 0 || d->act == 3 || p.splitk > 1);
-        // Round 6: the pipelined patch kernel on EIGHT waves (16 x 16-pixel tile x 128 columns) where whole 16 x 16 tiles cover the image and the
-        // grid -- with split-K over the 64-channel slabs when it has to -- still gives >= 200 workgroups; this also brings the 32^2 / 16^2
-        // levels of the denoiser (M < 8192, split-K) onto the patch kernel
-        int p2_nw = 0, p2_sk = 1;
-        if (patch2 && patch_geom && d->splitk <= 1 && d->conv_hout % 16 == 0 && d->conv_wout % 16 == 0 && (d->N % 128 == 0 || d->N >= 512) &&
-            (d->M >= patch_min_m || patch2_low)) {
-            const long long tiles8 = (long long)(d->M / 256) * ((d->N + 127) / 128);
-            const int ncc = d->conv_cin / 64;
-            long long sk = 1;
-            if (tiles8 < 200 && d->workspace && d->splitk == 0 && (long long)d->M * d->N < (1LL << 33)) {
-                sk = 256 / tiles8;
-                if (sk > ncc / 2) sk = ncc / 2;
-                while (sk > 1 && (size_t)sk * d->M * d->N * sizeof(float) > d->workspace_bytes) sk--;
-                if (sk < 1) sk = 1;
-                const long long per = (ncc + sk - 1) / sk;
-                sk = (ncc + per - 1) / per;                          // no empty slices
-            }
-            const long long wgs = tiles8 * sk, rounds = (wgs + 255) / 256;
-            static const int nw8 = getenv("DWG_CONV_PATCH2_NW8") ? atoi(getenv("DWG_CONV_PATCH2_NW8")) : 1;   // 0: never, 1: auto, 2: whenever legal
-            // one workgroup per CU exposes every tile's prologue (first patch from HBM) and epilogue (128 KB of stores): with few steps per
-            // tile (the VAE's 512^2 / 256^2 layers: 36 - 72) the four-wave kernel's two workgroups per CU overlap them; DWG_CONV_PATCH2_NW8_MINSTEPS
-            static const int minsteps8 = getenv("DWG_CONV_PATCH2_NW8_MINSTEPS") ? atoi(getenv("DWG_CONV_PATCH2_NW8_MINSTEPS")) : 100;
-            const long long steps = (long long)((ncc + sk - 1) / sk) * 9;
-            const bool worth = nw8 == 2 || (nw8 == 1 && (sk > 1 || steps >= minsteps8 || d->M < patch_min_m));
-            if (worth && wgs >= 200 && wgs * 100 >= rounds * 256 * 80 && (d->act == 0 || d->act == 3 || sk > 1)) { p2_nw = 8; p2_sk = (int)sk; patch_ok = true; }
-        }
-        if (patch_ok && !p2_nw && patch2) p2_nw = 4;
-        if (patch_ok && p2_nw != 8 && p.splitk > 1) {
-            // re-derive the slice count for this kernel's tiling: (8x16 pixel tiles) x (N / BN) workgroups, >= 2 slabs per slice
-            const int gm = (d->M / (d->conv_hout * d->conv_wout)) * ((d->conv_hout + 7) / 8) * ((d->conv_wout + 15) / 16);
-            const int blocks = gm * ((d->N + (narrow ? 64 : 128) - 1) / (narrow ? 64 : 128));
-            int sk = blocks >= 256 ? 1 : (384 + blocks - 1) / blocks;
-            const int ncc = d->conv_cin / 64;
-            if (sk > ncc / 2) sk = ncc / 2;
-            if (sk > p.splitk) sk = p.splitk;             // the workspace was sized for p.splitk slabs
-            if (sk < 2) { sk = 1; p.ws = nullptr; }
-            p.splitk = sk;
-        }
-        if (p2_nw == 8) { p.splitk = p2_sk; p.ws = p2_sk > 1 ? reinterpret_cast<float*>(d->workspace) : nullptr; }
-        // the eight-wave tiles (round 6): long-K layers that do not take the LDS-patch kernel
-        int big_sk = 1;
-        int big_bm = (glds_ok && !patch_ok && d->splitk <= 1) ? big_tile(d->M, d->N, d->K, &big_sk) : 0;
-        if (big_bm) {
-            if (d->act == DWG_ACT_GEGLU_PAIR || !d->workspace || batch != 1 || d->splitk == 1 || (long long)d->M * d->N >= (1LL << 33)) big_sk = 1;
-            while (big_sk > 1 && (size_t)big_sk * d->M * d->N * sizeof(float) > d->workspace_bytes) big_sk--;
-            const int bbn = big_bm == 256 ? 128 : 256;
-            const long long tiles = (long long)((d->M + big_bm - 1) / big_bm) * ((d->N + bbn - 1) / bbn) * batch;
-            static const int force = getenv("DWG_GEMM_BIG") ? atoi(getenv("DWG_GEMM_BIG")) : 1;
-            const long long wgs = tiles * big_sk, rounds = (wgs + 255) / 256;
-            if (force < 2 && (wgs < 200 || wgs * 100 < rounds * 256 * 80)) big_bm = 0;      // (an unsplittable launch that would leave CUs idle)
-        }
-        if (patch_ok && p2_nw == 8) {
-            launch_conv3x3_patch2<128, 8, 4>(p, stream, name);
-        } else if (patch_ok && p2_nw == 4) {
-            if (narrow) launch_conv3x3_patch2<64, 4, 4>(p, stream, name); else launch_conv3x3_patch2<128, 4, 2>(p, stream, name);
-        } else if (patch_ok) {
-            if (narrow) launch_conv3x3_patch<64>(p, stream, name); else launch_conv3x3_patch<128>(p, stream, name);
-        } else if (glds_ok) {
-            static const bool no_fast = getenv("DWG_CONV_NO_FAST") != nullptr;
-            static const bool no_cat_fast = getenv("DWG_CONV_NO_CAT_FAST") != nullptr;
-            const bool fast_geom = amode == MODE_CONV && d->conv_cin % 64 == 0 && p.conv.dil == 1 && p.conv.up == 1 && d->conv_kh * d->conv_kw <= 32 && !no_fast;
-            const int akind = amode != MODE_CONV ? 0
-                              : (fast_geom && !d->A2 ? 2
-                                 : (fast_geom && d->A2 && d->conv_cin1 % 64 == 0 && (d->conv_cin - d->conv_cin1) % 64 == 0 && !no_cat_fast ? 3 : 1));
-#ifdef DWG_GEMM_X_TU
-            if (dbg && akind == 2 && ((big_bm == 256) || (!big_bm && narrow))) {         // timing experiments (no epilogue launch: garbage anyway)
-                if (big_bm) { p.splitk = big_sk; p.ws = big_sk > 1 ? reinterpret_cast<float*>(d->workspace) : nullptr; }
-                if (dbg == 1) launch_dbg<1>(p, big_bm != 0, stream); else if (dbg == 2) launch_dbg<2>(p, big_bm != 0, stream);
-                else if (dbg == 3) launch_dbg<3>(p, big_bm != 0, stream); else if (dbg == 5) launch_dbg<5>(p, big_bm != 0, stream);
-                else if (dbg == 6) launch_dbg<6>(p, big_bm != 0, stream); else if (dbg == 7) launch_dbg<7>(p, big_bm != 0, stream);
-                else launch_dbg<0>(p, big_bm != 0, stream);
-                return DWG_OK;
-            }
-#endif
-            if (big_bm) {
-                p.splitk = big_sk; p.ws = big_sk > 1 ? reinterpret_cast<float*>(d->workspace) : nullptr;
-                if (akind == 3) launch_big<3>(p, big_bm, batch, stream, name);
-                else if (akind == 2) launch_big<2>(p, big_bm, batch, stream, name);
-                else if (akind == 1) launch_big<1>(p, big_bm, batch, stream, name);
-                else launch_big<0>(p, big_bm, batch, stream, name);
-            } else if (narrow) {
-                if (akind == 3) launch_glds<64, 3>(p, batch, stream, name);
-                else if (akind == 2) launch_glds<64, 2>(p, batch, stream, name);
-                else if (akind == 1) launch_glds<64, 1>(p, batch, stream, name);
-                else launch_glds<64, 0>(p, batch, stream, name);
-            } else {
-                if (akind == 3) launch_glds<128, 3>(p, batch, stream, name);
-                else if (akind == 2) launch_glds<128, 2>(p, batch, stream, name);
-                else if (akind == 1) launch_glds<128, 1>(p, batch, stream, name);
-                else launch_glds<128, 0>(p, batch, stream, name);
-            }
-        }
-#ifdef DWG_GEMM_X_TU
-        else return DWG_E_ARG;     // split-precision operands exist only for the direct-to-LDS kernels (K-contiguous, 16-byte aligned rows)
+    switch (pl.fam) {
+        case FAM_PATCH2:
+            if (pl.nw == 8) launch_conv3x3_patch2<128, 8, 4>(p, stream, name);
+            else if (pl.bn == 64) launch_conv3x3_patch2<64, 4, 4>(p, stream, name);
+            else launch_conv3x3_patch2<128, 4, 2>(p, stream, name);
+            break;
+        case FAM_GLDS8:
+            with_akind(pl.akind, [&](auto ak) {
+                if (pl.bm == 256) launch_glds8<256, 128, decltype(ak)::value>(p, batch, stream, name);
+                else launch_glds8<128, 256, decltype(ak)::value>(p, batch, stream, name);
+            });
+            break;
+        case FAM_GLDS:
+            with_akind(pl.akind, [&](auto ak) {
+                if (pl.bn == 64) launch_glds<64, decltype(ak)::value>(p, batch, stream, name);
+                else launch_glds<128, decltype(ak)::value>(p, batch, stream, name);
+            });
+            break;
+        case FAM_GENERIC:
+#if defined(DWG_GEMM_X_TU)
+            return DWG_E_ARG;     // (not planned: split-precision operands have no register-staged kernel)
+#elif defined(DWG_GEMM_F16_TU)
+            launch_generic<HT>(p, pl, batch, stream, name);
 #else
-        else if (narrow) dispatch_a<T, 64>(p, amode, bmode, batch, stream, name);
-        else dispatch_a<T, 128>(p, amode, bmode, batch, stream, name);
+            if (d->dtype == DWG_DTYPE_HALF) launch_generic<HT>(p, pl, batch, stream, name);
+            else launch_generic<float>(p, pl, batch, stream, name);
 #endif
-    } else {
-#if defined(DWG_GEMM_F16_TU) || defined(DWG_GEMM_X_TU)
-        return DWG_E_ARG;          // the exact-f32 kernels live in the bf16 unit
-#else
-        // exact-f32 path (v_mfma_f32_32x32x2_f32): the avatar's MLPs, and every layer of the fp32 denoiser / VAE plans -- the precision the
-        // reference runs the 3DGS stage in (configs/__init__.py:236,241).  Register-staged generic kernel, incl. the im2col loader.
-        typedef float T;
-        long long ao[2] = {p.bA1, p.bA2}, bo[2] = {p.bB1, p.bB2};
-        int amode;
-        if (d->conv_enabled && !plain1x1) {
-            if (d->conv_cin % 4 != 0 || ((uintptr_t)d->A % 16) != 0) return DWG_E_ARG;
-            if (d->A2 && (d->conv_cin1 % 4 != 0 || d->conv_cin1 <= 0 || d->conv_cin1 >= d->conv_cin || ((uintptr_t)d->A2 % 16) != 0))
-                return DWG_E_ARG;
-            if (d->K != d->conv_kh * d->conv_kw * d->conv_cin) return DWG_E_ARG;
-            amode = MODE_CONV;
-        } else amode = pick_mode<T>(p.A, p.sam, p.sak, p.M, p.K, ao, 2);
-        int bmode = pick_mode<T>(p.B, p.sbn, p.sbk, p.N, p.K, bo, 2);
-        if (narrow) dispatch_a<T, 64>(p, amode, bmode, batch, stream, name);
-        else dispatch_a<T, 128>(p, amode, bmode, batch, stream, name);
-#endif
+            break;
     }
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;

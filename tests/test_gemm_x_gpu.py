@@ -210,10 +210,9 @@ def test_x_conv3x3_small_latents_splitk_paths(C, H, patch_min_m):
 
 
 @pytest.mark.parametrize("case", ["gemm_small_m", "gemm_qkv", "gemm_ff_out", "conv_1280_16", "conv_640_32", "conv_320_64", "conv_im2col"])
-def test_x_splitk_reduce_inside_the_kernel_matches_the_reduce_pass_bit_for_bit(case):
-    """dwg_gemm_desc::workspace_counters (round 6): the slice that arrives last at a tile sums the slabs inside the GEMM kernel.  Same
-    additions in the same order as k_splitk_epilogue: identical bits, whichever slice is last; the counters are zero again afterwards (the
-    second and third run on the same workspace agree); no reduce launch."""
+def test_x_splitk_reduce_pass_is_bit_reproducible_and_matches_float64(case):
+    """Shapes of the step: the library splits all but the 64x64-latent convolution (its grid fills the chip), k_splitk_epilogue sums the slabs
+    in slice order -- two runs on one workspace give identical bits -- and the result is fp32-grade against a float64 reference."""
     import os
     from dreamwaltz_g_amd import gemm, _lib
     g = torch.Generator().manual_seed(len(case))
@@ -222,6 +221,7 @@ def test_x_splitk_reduce_inside_the_kernel_matches_the_reduce_pass_bit_for_bit(c
         M, N, K = {"gemm_small_m": (128, 1280, 11520), "gemm_qkv": (512, 3840, 1280), "gemm_ff_out": (2048, 640, 2560)}[case]
         x = torch.randn(M, K, generator=g); w = torch.randn(N, K, generator=g) / K ** 0.5
         b = torch.randn(N, generator=g); r = torch.randn(M, N, generator=g)
+        ref = torch.nn.functional.silu(x.double() @ w.double().t() + b.double()) + r.double()
         xc, wc, bc, rx = _x(x), _x(w), b.cuda(), _x(r)
         shape = (M, N)
         make = lambda y: gemm.gemm_raw(xc, wc, y, M, N, K, (K, 1), (K, 1), N, bias=bc, residual=rx, ldr=N, act="silu", run=False)  # noqa: E731
@@ -232,37 +232,40 @@ def test_x_splitk_reduce_inside_the_kernel_matches_the_reduce_pass_bit_for_bit(c
         Bn = 2
         x = torch.randn(Bn, C, H, H, generator=g); w = torch.randn(C, C, 3, 3, generator=g) / (C * 9) ** 0.5
         bimg = torch.randn(Bn, C, generator=g); r = torch.randn(Bn, H, H, C, generator=g)
+        ref = (torch.nn.functional.conv2d(x.double(), w.double(), None, padding=1).permute(0, 2, 3, 1) + bimg.double()[:, None, None, :]
+               + r.double())
         xc, wc, bc, rcu = _x(x.permute(0, 2, 3, 1)), _x(w.permute(0, 2, 3, 1)), bimg.cuda(), _x(r)
         M, K = Bn * H * H, 9 * C
         shape = (Bn, H, H, C)
         make = lambda y: gemm.gemm_raw(xc, wc, y, M, C, K, (0, 1), (K, 1), C, bias=bc, bias_row_div=H * H, bias_ld=C, residual=rcu, ldr=C,  # noqa: E731
                                        conv=(C, H, H, H, H, 3, 3, 1, 1, 1, 1), run=False)
+    splits = case != "conv_320_64"
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     try:
-        outs, launches = [], []
-        for counters in (0, 1, 1, 1):
+        outs, launches, ws = [], [], None
+        for _ in range(2):
             y = torch.empty(shape, device="cuda", dtype=torch.int32)
             d = make(y)
             d.splitk = 0
             need = _lib.lib().dwg_gemm_workspace_bytes(ctypes.byref(d))
-            if need == 0:
-                pytest.skip("the library does not split this shape")
-            if counters == 0 or len(outs) == 1:
-                ws = torch.zeros(need // 4, device="cuda")          # the fused runs share ONE workspace: counters must come back to zero
-            d.workspace, d.workspace_bytes, d.workspace_counters = ws.data_ptr(), need, counters
+            assert (need > 0) == splits, need
+            if not splits:
+                d.splitk = 1
+            elif ws is None:
+                ws = torch.empty(need // 4, device="cuda")          # both runs on ONE workspace
+            if ws is not None:
+                d.workspace, d.workspace_bytes = ws.data_ptr(), need
             _lib.prof_enable(True)
             gemm.run_desc(d, st)
             torch.cuda.synchronize()
             launches.append(_lib.prof_symbols()); _lib.prof_enable(False)
-            outs.append(y.clone())
-            if counters:
-                assert int(ws[:4096].view(torch.int32).abs().sum()) == 0, "tile counters not back at zero"
+            outs.append(y)
     finally:
         os.environ.pop("DWG_CONV_PATCH_MINM", None)
-    assert any("splitk_epilogue" in k for k in launches[0]), launches[0].keys()
-    for k in (1, 2, 3):
-        assert not any("splitk_epilogue" in s_ for s_ in launches[k]), launches[k].keys()
-        assert torch.equal(outs[0], outs[k]), (case, k)
+    for syms in launches:
+        assert any("splitk_epilogue" in k for k in syms) == splits, syms.keys()
+    assert torch.equal(outs[0], outs[1]), case
+    assert _rel(_u(outs[0]), ref) < TOL, case
 
 
 def test_x_rejects_what_the_format_cannot_express():

@@ -1,5 +1,5 @@
 """Times a few denoiser conv / linear shapes on the f32x GEMM unit with COLD weights (a ring of copies larger than the Infinity Cache):
-A/B of csrc/gemm.hip environment switches (DWG_GEMM_BIG, DWG_GEMM_DEBUG, ...) per shape.   DWG_...=x python tools/gemm_probe.py [f32x|bf16]"""
+per-shape launch times of the library's own dispatch.   python tools/gemm_probe.py [f32x|bf16]"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
