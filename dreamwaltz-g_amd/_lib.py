@@ -82,8 +82,23 @@ SIGNATURES = {
                                                       _u32, _u32, _vp, _vp, _sz, _vp]),
     "dwg_grid_encode_backward_slabs_accumulate": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32,
                                                                  _u32, _u32, _u32, _vp, _vp, _sz, _vp]),
+    # include/dwg_raymarch.h
+    "dwg_raymarch_near_far_from_aabb": (ctypes.c_int, [_vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp]),
+    "dwg_raymarch_sph_from_ray": (ctypes.c_int, [_vp, _vp, _f32, _u32, _vp, _vp]),
+    "dwg_raymarch_morton3d": (ctypes.c_int, [_vp, _u32, _vp, _vp]),
+    "dwg_raymarch_morton3d_invert": (ctypes.c_int, [_vp, _u32, _vp, _vp]),
+    "dwg_raymarch_packbits": (ctypes.c_int, [_vp, _u32, _f32, _vp, _vp]),
+    "dwg_raymarch_flatten_rays": (ctypes.c_int, [_vp, _u32, _u32, _vp, _vp]),
+    "dwg_raymarch_train_workspace_bytes": (_sz, [_u32]),
+    "dwg_raymarch_march_rays_train": (ctypes.c_int, [_vp, _vp, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32,
+                                                     _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dwg_raymarch_composite_rays_train_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "dwg_raymarch_composite_rays_train_backward": (ctypes.c_int, [_vp] * 11 + [_u32, _u32, _u32, _f32, _u32, _vp, _vp, _vp]),
+    "dwg_raymarch_march_rays": (ctypes.c_int, [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp,
+                                               _vp, _vp, _vp]),
+    "dwg_raymarch_composite_rays": (ctypes.c_int, [_u32, _u32, _u32, _f32, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     # include/dwg_gemm.h
-    "dwg_gemm": (ctypes.c_int, [_vp, _vp]),
+    "dwg_gemm":(ctypes.c_int, [_vp, _vp]),
     "dwg_gemm_workspace_bytes": (_sz, [_vp]),
     "dwg_transpose_2byte": (ctypes.c_int, [_i32, _i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "dwg_transpose_dt": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),

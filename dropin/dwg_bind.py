@@ -8,6 +8,8 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
 
   B1  diff_gaussian_rasterization           dropin/diff_gaussian_rasterization/  (found through PYTHONPATH; nothing to patch)
   B2  core.nerf.gridencoder backend         dropin/_gridencoder.py               (found through PYTHONPATH before the JIT build)
+  B6  _raymarchingrgb / _raymarchinglatent  dropin/_raymarching{rgb,latent}.py    (found through PYTHONPATH; nothing to patch -- the NeRF
+                                             stage's ray marcher, core/nerf/raymarching/*/raymarching.py:14-27)
   B3  core.system.avatar.build_gaussian_avatar (avatar.py:1642-1714)  -> the reference builds ITS avatar (point cloud, nearest triangles,
                                              inverse LBS, LBS weights ...), then `DreamWaltzG.from_reference(ref)` adopts every Parameter
                                              and buffer by name; non-DreamWaltzG gs_types are returned untouched (reference path)
