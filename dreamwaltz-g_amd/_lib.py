@@ -41,6 +41,23 @@ class RasterFramesC(ctypes.Structure):
     _fields_ = [("num_frames", ctypes.c_int32), ("gaussian_stride", ctypes.c_int64), ("camera_stride", ctypes.c_int64)]
 
 
+class NerfFieldDescC(ctypes.Structure):
+    """struct dwg_nerf_field_desc (include/dwg_nerf.h)."""
+    _fields_ = [("embeddings", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("host_offsets", ctypes.c_void_p),
+                ("num_levels", ctypes.c_uint32), ("log2_per_level_scale", ctypes.c_float), ("base_resolution", ctypes.c_uint32),
+                ("gridtype", ctypes.c_uint32), ("align_corners", ctypes.c_uint32), ("interp", ctypes.c_uint32), ("bound", ctypes.c_float),
+                ("num_layers", ctypes.c_uint32), ("hidden", ctypes.c_uint32), ("out_dim", ctypes.c_uint32),
+                ("weight", ctypes.c_void_p * 4), ("bias", ctypes.c_void_p * 4),
+                ("density_activation", ctypes.c_uint32), ("density_prior", ctypes.c_uint32), ("albedo_sigmoid", ctypes.c_uint32),
+                ("raw", ctypes.c_uint32), ("sigma_scale", ctypes.c_void_p), ("precision", ctypes.c_uint32)]
+
+
+class NerfFieldGradsC(ctypes.Structure):
+    """struct dwg_nerf_field_grads (include/dwg_nerf.h)."""
+    _fields_ = [("embeddings", ctypes.c_void_p), ("weight", ctypes.c_void_p * 4), ("bias", ctypes.c_void_p * 4),
+                ("sigma_scale", ctypes.c_void_p), ("accumulate", ctypes.c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares must be listed here (tests check it)
 _vp, _i32, _i64, _f32, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _u32 = ctypes.c_uint32
@@ -82,6 +99,11 @@ SIGNATURES = {
                                                       _u32, _u32, _vp, _vp, _sz, _vp]),
     "dwg_grid_encode_backward_slabs_accumulate": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32,
                                                                  _u32, _u32, _u32, _vp, _vp, _sz, _vp]),
+    # include/dwg_nerf.h
+    "dwg_nerf_field_forward": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+    "dwg_nerf_field_backward_workspace_bytes": (_sz, [ctypes.POINTER(NerfFieldDescC), ctypes.c_uint64]),
+    "dwg_nerf_field_backward": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _vp, _vp,
+                                               ctypes.POINTER(NerfFieldGradsC), _vp, _sz, _vp]),
     # include/dwg_raymarch.h
     "dwg_raymarch_near_far_from_aabb": (ctypes.c_int, [_vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp]),
     "dwg_raymarch_sph_from_ray": (ctypes.c_int, [_vp, _vp, _f32, _u32, _vp, _vp]),

@@ -1,0 +1,528 @@
+// nerf_field.hip -- the fused NeRF field of stage I (boundary B7): grid encoding -> sigma_net -> density / albedo epilogue.
+//
+// Native restatement of _NeRFNetwork.common_forward / local_geometry_forward (core/nerf/nerf_model.py:268-295) for the grid
+// backbone.  A workgroup (4 waves) takes 64 points at a time:
+//   1. the 64 x L grid lookups (gridenc_common.h, the same code as gridenc.hip) fill an LDS tile enc[64][2L];
+//   2. each wave runs its 16 rows through the layers on the matrix cores (16x16 output blocks, weights resident in LDS),
+//      every layer's output going back to LDS; nothing between x and (sigma, albedo) is written to HBM;
+//   3. one thread per point applies the density activation / prior and the albedo sigmoid and writes the outputs.
+// The backward recomputes 1-2 per tile, then walks the layers backwards in LDS: dZ_l -> dW_l (MFMA over the tile's 64 points,
+// accumulated in registers across the workgroup's tiles), db_l, dZ_{l-1} = (dZ_l W_l) * relu'.  The encoding gradient goes to
+// HBM in the [points, 2L] layout that the slab-binned table gradient of gridenc.hip reads.  The per-workgroup weight-gradient
+// partials are summed by a second kernel in workgroup order; no float atomics anywhere, so the gradients are bit-reproducible.
+#include "dwg_common.h"
+#include "dwg_prof_internal.h"
+#include "../../include/dwg_gridenc.h"
+#include "../../include/dwg_nerf.h"
+#include "gridenc_common.h"
+
+namespace {
+
+constexpr int NF_TILE = 64;                 // points per workgroup tile (4 waves x 16 rows)
+constexpr int NF_MAXS = 13;                 // weight-gradient blocks per wave: (16 + 16 + 16 + 4) 16x16 blocks of 4 layers / 4 waves
+constexpr int NF_BWD_WG = 1024;             // workgroups of the backward (4 per CU): the number of weight-gradient partials
+constexpr uint64_t NF_CHUNK = 1ull << 20;   // points per backward chunk (bounds the d_enc and table-gradient workspace)
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct NfP {
+    GridP g;
+    const float2* table;                    // embeddings [offsets[L]] (C = 2)
+    const int* offsets;
+    float bound, inv2b;
+    uint32_t nl, W;                         // layers, out_dim
+    uint32_t K[4], N[4], KP[4], NP[4];      // true and padded (multiple of 16) in / out widths per layer
+    const float* w[4];
+    const float* b[4];
+    uint32_t act, prior, sig, raw;
+    const float* sigma_scale;
+    // LDS layout, in elements of the operand type: weights [NP][KP + pad], activations [64][width + pad]
+    uint32_t woff[4], wst[4];
+    uint32_t aoff[5], ast[5];               // 0: enc, 1..nl-1: hidden outputs, nl: last layer's output
+    uint32_t bias_byte_off;                 // float bias[4][64] after the operand-typed part
+    // weight-gradient partial layout (floats): W_l [N][K], then b_l [N]; the last slot is sigma_scale's
+    uint32_t pw[4], pb[4], P;
+    uint32_t bb[5];                         // prefix over layers of the 16x16 weight-gradient blocks: wave w owns blocks w, w + 4, ...
+    uint32_t sumN;                          // biases: thread t < sumN owns one
+};
+
+template <typename T> struct Mm;
+template <> struct Mm<_Float16> {
+    static constexpr int KS = 16, NJ = 4;
+    typedef _Float16 frag __attribute__((ext_vector_type(4)));
+    __device__ static f32x4 mma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
+    __device__ static void set(frag& f, int j, _Float16 v) { f[j] = v; }
+};
+template <> struct Mm<float> {
+    static constexpr int KS = 4, NJ = 1;
+    typedef float frag;
+    __device__ static f32x4 mma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    __device__ static void set(frag& f, int, float v) { f = v; }
+};
+
+// One 16x16 output block of D = A B over K (multiple of the MFMA's k step) from LDS: A(i, k) = A[i * sa + k * ska] with
+// ska == 1 when AK (contiguous along k), B(k, j) = B[k * sbk + j * sb] with sbk == 1 when BK.  Lane l holds D[4 (l >> 4) + v][l & 15].
+template <typename T, bool AK, bool BK>
+__device__ __forceinline__ f32x4 mma_block(const T* A, uint32_t sa, uint32_t ska, const T* B, uint32_t sbk, uint32_t sb, uint32_t K, f32x4 acc) {
+    typedef Mm<T> M;
+    const uint32_t lane = threadIdx.x & 63u, r = lane & 15u, q = lane >> 4;
+    for (uint32_t k0 = 0; k0 < K; k0 += M::KS) {
+        const uint32_t k = k0 + M::NJ * q;
+        typename M::frag a, b;
+        if (AK) a = *reinterpret_cast<const typename M::frag*>(A + r * sa + k);
+        else {
+#pragma unroll
+            for (int j = 0; j < M::NJ; j++) M::set(a, j, A[r * sa + (k + j) * ska]);
+        }
+        if (BK) b = *reinterpret_cast<const typename M::frag*>(B + k + r * sb);
+        else {
+#pragma unroll
+            for (int j = 0; j < M::NJ; j++) M::set(b, j, B[(k + j) * sbk + r * sb]);
+        }
+        acc = M::mma(a, b, acc);
+    }
+    return acc;
+}
+
+__device__ __forceinline__ float nf_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }      // F.softplus, beta 1, threshold 20
+__device__ __forceinline__ float nf_softplus_bwd(float g, float x) { if (x > 20.f) return g; const float z = expf(x); return g * z / (z + 1.f); }
+
+__device__ __forceinline__ float nf_prior(const NfP& p, float x0, float x1, float x2) {
+    if (p.prior == 0) return 0.f;
+    const float d = x0 * x0 + x1 * x1 + x2 * x2;                            // nerf_model.py:43
+    if (p.prior == 1) return 5.f * expf(-d / 0.08f);                        // gaussian: peak 5, std 0.2
+    return 10.f * (1.f - sqrtf(d) / 0.5f);                                  // sqrt: blob density 10, radius 0.5
+}
+
+// weights (rounded to T) and biases into LDS; padding zero
+template <typename T>
+__device__ void load_weights(const NfP& p, T* lds, float* bias) {
+    for (uint32_t l = 0; l < p.nl; l++) {
+        T* w = lds + p.woff[l];
+        const uint32_t n_el = p.NP[l] * p.wst[l];
+        for (uint32_t e = threadIdx.x; e < n_el; e += 256) {
+            const uint32_t n = e / p.wst[l], k = e - n * p.wst[l];
+            w[e] = (T)((n < p.N[l] && k < p.K[l]) ? p.w[l][n * p.K[l] + k] : 0.f);
+        }
+        for (uint32_t n = threadIdx.x; n < 64; n += 256) bias[l * 64 + n] = n < p.N[l] ? p.b[l][n] : 0.f;
+    }
+    // the encoding's padding columns are never written by a lookup: zero them once
+    T* e = lds + p.aoff[0];
+    for (uint32_t i = threadIdx.x; i < NF_TILE * p.ast[0]; i += 256) e[i] = (T)0.f;
+}
+
+
+// x of the tile -> sx, the encoder's (x + bound) / (2 bound) -> sxn, the 64 x L lookups -> enc, then the layers; points at or past
+// `mend` are encoded from x = 0 (their outputs are never stored).  Ends with a barrier: every layer output is in LDS.
+template <typename T>
+__device__ void field_tile(const NfP& p, const float* __restrict__ x, uint64_t mend, uint64_t p0, T* lds, const float* bias, float* sx,
+                           float* sxn) {
+    for (uint32_t i = threadIdx.x; i < NF_TILE * 3; i += 256) {
+        const float v = p0 + i / 3 < mend ? x[p0 * 3 + i] : 0.f;
+        sx[i] = v;
+        sxn[i] = (v + p.bound) * p.inv2b;       // torch evaluates the division by the Python scalar 2 bound as a product with its inverse
+    }
+    __syncthreads();
+    T* enc = lds + p.aoff[0];
+    const uint32_t L = p.g.L, est = p.ast[0];
+    for (uint32_t t = threadIdx.x; t < NF_TILE * L; t += 256) {
+        const uint32_t pt = t / L, level = t - pt * L;
+        Cell c = locate(p.g, p.offsets, level, sxn[3 * pt], sxn[3 * pt + 1], sxn[3 * pt + 2]);
+        float r0 = 0.f, r1 = 0.f;
+        if (!c.oob) {
+            const float2* g = p.table + (uint32_t)p.offsets[level];
+            float2 v[8];
+#pragma unroll
+            for (int idx = 0; idx < 8; idx++) {
+                uint32_t gx = c.g[0] + (idx & 1), gy = c.g[1] + ((idx >> 1) & 1), gz = c.g[2] + ((idx >> 2) & 1);
+                v[idx] = g[grid_index(p.g.gridtype, p.g.align_corners, c.hsize, c.res, gx, gy, gz) >> 1];
+                if (sizeof(T) == 2) { v[idx].x = (float)(_Float16)v[idx].x; v[idx].y = (float)(_Float16)v[idx].y; }   // the fp16 table (grid.py:47-48)
+            }
+#pragma unroll
+            for (int idx = 0; idx < 8; idx++) {
+                float w = ((idx & 1) ? c.w[0] : 1.f - c.w[0]) * ((idx & 2) ? c.w[1] : 1.f - c.w[1]) * ((idx & 4) ? c.w[2] : 1.f - c.w[2]);
+                r0 += w * v[idx].x; r1 += w * v[idx].y;
+            }
+        }
+        enc[pt * est + 2 * level] = (T)r0;
+        enc[pt * est + 2 * level + 1] = (T)r1;
+    }
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, r = lane & 15u, q = lane >> 4;
+    for (uint32_t l = 0; l < p.nl; l++) {
+        const T* X = lds + p.aoff[l] + wave * 16u * p.ast[l];
+        T* Y = lds + p.aoff[l + 1] + wave * 16u * p.ast[l + 1];
+        const T* Wl = lds + p.woff[l];
+        const bool relu = l + 1 < p.nl;
+        for (uint32_t cb = 0; cb < p.NP[l] / 16u; cb++) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = mma_block<T, true, true>(X, p.ast[l], 1u, Wl + cb * 16u * p.wst[l], 1u, p.wst[l], p.KP[l], acc);
+            const uint32_t col = cb * 16u + r;
+            const float bv = bias[l * 64u + col];
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                float y = acc[v] + bv;
+                if (relu && y < 0.f) y = 0.f;
+                Y[(4u * q + v) * p.ast[l + 1] + col] = (T)y;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void lds_carve(const NfP& p, unsigned char* smem, T*& lds, float*& bias, float*& sx, float*& sxn, float*& red) {
+    lds = reinterpret_cast<T*>(smem);
+    bias = reinterpret_cast<float*>(smem + p.bias_byte_off);
+    sx = bias + 256;
+    sxn = sx + NF_TILE * 3;
+    red = sxn + NF_TILE * 3;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_nf_fwd(NfP p, const float* __restrict__ x, uint64_t M, uint64_t ntiles, float* __restrict__ sigma,
+                                                T* __restrict__ albedo) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* lds; float *bias, *sx, *sxn, *red;
+    lds_carve(p, smem, lds, bias, sx, sxn, red);
+    load_weights(p, lds, bias);
+    const float es = p.act == 2 ? expf(*p.sigma_scale) : 0.f;
+    const uint32_t W = p.W;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t p0 = tile * NF_TILE;
+        field_tile(p, x, M, p0, lds, bias, sx, sxn);
+        const uint32_t t = threadIdx.x;
+        if (t < NF_TILE && p0 + t < M) {
+            const uint64_t pt = p0 + t;
+            const T* o = lds + p.aoff[p.nl] + t * p.ast[p.nl];
+            const float h0 = (float)o[0];
+            float s = h0;
+            if (!p.raw) {
+                const float xv = h0 + nf_prior(p, sx[3 * t], sx[3 * t + 1], sx[3 * t + 2]);
+                s = p.act == 0 ? expf(xv) : p.act == 1 ? nf_softplus(xv) : nf_softplus(xv * es - 1.f);
+            }
+            sigma[pt] = s;
+            T* a = albedo + pt * (W - 1u);
+            for (uint32_t c = 1; c < W; c++) {
+                float v = (float)o[c];
+                if (p.sig) v = 1.f / (1.f + expf(-v));
+                a[c - 1] = (T)v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// One chunk [m0, m0 + n) of the backward.  partial: [gridDim.x][P] floats, overwritten when `first`, else added to.
+template <typename T>
+__global__ __launch_bounds__(256) void k_nf_bwd(NfP p, const float* __restrict__ x, uint64_t m0, uint64_t n, const float* __restrict__ dsigma,
+                                                const T* __restrict__ dalbedo, float* __restrict__ d_enc, float* __restrict__ xn_out,
+                                                float* __restrict__ partial, int first, int want_w) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* lds; float *bias, *sx, *sxn, *red;
+    lds_carve(p, smem, lds, bias, sx, sxn, red);
+    load_weights(p, lds, bias);
+    const float es = p.act == 2 ? expf(*p.sigma_scale) : 0.f;
+    const uint32_t W = p.W, nl = p.nl;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, r = lane & 15u, q = lane >> 4;
+    const uint64_t mend = m0 + n, ntiles = (n + NF_TILE - 1) / NF_TILE;
+    // the bias this thread owns
+    uint32_t bl = 4, bn = 0;
+    {
+        uint32_t base = 0;
+        for (uint32_t l = 0; l < nl; l++) {
+            if (threadIdx.x >= base && threadIdx.x < base + p.N[l]) { bl = l; bn = threadIdx.x - base; }
+            base += p.N[l];
+        }
+    }
+    f32x4 acc[NF_MAXS];
+#pragma unroll
+    for (int s = 0; s < NF_MAXS; s++) acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float acc_b = 0.f, acc_s = 0.f;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t p0 = m0 + tile * NF_TILE;
+        field_tile(p, x, mend, p0, lds, bias, sx, sxn);
+        // d(last layer output), rounded to the operand type where autograd hands the reference an fp16 gradient
+        if (threadIdx.x < NF_TILE) {
+            const uint32_t t = threadIdx.x;
+            const uint64_t pt = p0 + t;
+            const bool valid = pt < mend;
+            T* o = lds + p.aoff[nl] + t * p.ast[nl];
+            float d[16];
+#pragma unroll
+            for (int c = 0; c < 16; c++) d[c] = 0.f;
+            if (valid) {
+                if (xn_out) { for (int k = 0; k < 3; k++) xn_out[(pt - m0) * 3 + k] = sxn[3 * t + k]; }
+                const float g = dsigma[pt];
+                const float h0 = (float)o[0];
+                if (p.raw) d[0] = g;
+                else {
+                    const float xv = h0 + nf_prior(p, sx[3 * t], sx[3 * t + 1], sx[3 * t + 2]);
+                    if (p.act == 0) d[0] = g * expf(fminf(fmaxf(xv, -15.f), 15.f));         // trunc_exp's backward (nerf_utils.py:189-191)
+                    else if (p.act == 1) d[0] = nf_softplus_bwd(g, xv);
+                    else { const float dy = nf_softplus_bwd(g, xv * es - 1.f); d[0] = dy * es; acc_s += dy * xv; }
+                }
+                const T* da = dalbedo + pt * (W - 1u);
+#pragma unroll
+                for (int c = 1; c < 16; c++) {
+                    if ((uint32_t)c < W) {
+                        float gv = (float)da[c - 1];
+                        if (p.sig) { const float a = (float)(T)(1.f / (1.f + expf(-(float)o[c]))); gv = gv * (1.f - a) * a; }
+                        d[c] = gv;
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 16; c++) o[c] = (T)d[c];
+        }
+        __syncthreads();
+        for (int l = (int)nl - 1; l >= 0; l--) {
+            const T* Z = lds + p.aoff[l + 1];
+            const uint32_t zs = p.ast[l + 1];
+            T* X = lds + p.aoff[l];
+            const uint32_t xs = p.ast[l];
+            if (want_w) {
+                const uint32_t nkb = p.KP[l] / 16u, b0 = p.bb[l], b1 = p.bb[l + 1];
+#pragma unroll
+                for (int s = 0; s < NF_MAXS; s++) {
+                    const uint32_t gb = wave + 4u * s;
+                    if (gb >= b0 && gb < b1) {
+                        const uint32_t loc = gb - b0, nb = loc / nkb, kb = loc - nb * nkb;
+                        // dW[n][k] += sum_p dZ[p][n] X[p][k]
+                        acc[s] = mma_block<T, false, false>(Z + nb * 16u, 1u, zs, X + kb * 16u, xs, 1u, (uint32_t)NF_TILE, acc[s]);
+                    }
+                }
+                if (bl == (uint32_t)l) {
+                    float sb = 0.f;
+                    for (uint32_t pp = 0; pp < NF_TILE; pp++) sb += (float)Z[pp * zs + bn];
+                    acc_b += sb;
+                }
+            }
+            const uint32_t ncb = p.KP[l] / 16u;
+            const T* Wl = lds + p.woff[l];
+            f32x4 dx[4];
+#pragma unroll
+            for (int cb = 0; cb < 4; cb++) {
+                dx[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+                // dX[i][j] = sum_n dZ[i][n] W[n][j]
+                if ((uint32_t)cb < ncb && (l > 0 || d_enc))
+                    dx[cb] = mma_block<T, true, false>(Z + wave * 16u * zs, zs, 1u, Wl + cb * 16u, p.wst[l], 1u, p.NP[l], dx[cb]);
+            }
+            if (l > 0) {
+                __syncthreads();            // every wave's weight-gradient reads of X are done
+#pragma unroll
+                for (int cb = 0; cb < 4; cb++) {
+                    if ((uint32_t)cb >= ncb) continue;
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        T* e = X + (wave * 16u + 4u * q + v) * xs + cb * 16u + r;
+                        *e = (T)((float)*e > 0.f ? dx[cb][v] : 0.f);          // relu' from the layer's (rounded) output
+                    }
+                }
+            } else if (d_enc) {
+                const uint32_t K0 = p.K[0];
+#pragma unroll
+                for (int cb = 0; cb < 4; cb++) {
+                    if ((uint32_t)cb >= ncb) continue;
+                    const uint32_t col = cb * 16u + r;
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        const uint64_t pt = p0 + wave * 16u + 4u * q + v;
+                        if (pt < mend && col < K0) d_enc[(pt - m0) * K0 + col] = dx[cb][v];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (!want_w) return;
+    float* P = partial + (size_t)blockIdx.x * p.P;
+#pragma unroll
+    for (int s = 0; s < NF_MAXS; s++) {
+        const uint32_t gb = wave + 4u * s;
+        if (gb >= p.bb[nl]) continue;
+        uint32_t l = 0;
+        while (gb >= p.bb[l + 1]) l++;
+        const uint32_t nkb = p.KP[l] / 16u, loc = gb - p.bb[l], nb = loc / nkb, kb = loc - nb * nkb;
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            const uint32_t nn = nb * 16u + 4u * q + v, k = kb * 16u + r;
+            if (nn < p.N[l] && k < p.K[l]) {
+                float* e = P + p.pw[l] + nn * p.K[l] + k;
+                *e = (first ? 0.f : *e) + acc[s][v];
+            }
+        }
+    }
+    if (bl < nl) { float* e = P + p.pb[bl] + bn; *e = (first ? 0.f : *e) + acc_b; }
+    if (threadIdx.x < NF_TILE) red[threadIdx.x] = acc_s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < NF_TILE; i++) s += red[i];
+        float* e = P + p.P - 1u;
+        *e = (first ? 0.f : *e) + s;
+    }
+}
+
+// sum of the G partials of every parameter, in workgroup order
+__global__ __launch_bounds__(256) void k_nf_reduce(NfP p, uint32_t G, const float* __restrict__ partial, dwg_nerf_field_grads gr) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= p.P) return;
+    float* dst = nullptr;
+    if (i == p.P - 1u) dst = gr.sigma_scale;
+    else {
+        for (uint32_t l = 0; l < p.nl; l++) {
+            if (i >= p.pw[l] && i < p.pb[l]) dst = gr.weight[l] ? gr.weight[l] + (i - p.pw[l]) : nullptr;
+            else if (i >= p.pb[l] && i < p.pb[l] + p.N[l]) dst = gr.bias[l] ? gr.bias[l] + (i - p.pb[l]) : nullptr;
+        }
+    }
+    if (!dst) return;
+    float s = 0.f;
+    for (uint32_t g = 0; g < G; g++) s += partial[(size_t)g * p.P + i];
+    if (i == p.P - 1u) s *= expf(*p.sigma_scale);           // d/d sigma_scale of exp(sigma_scale), after the sum (as autograd orders it)
+    *dst = gr.accumulate ? *dst + s : s;
+}
+
+int make_params(const dwg_nerf_field_desc* d, NfP& p, size_t& lds_bytes) {
+    if (!d) return DWG_E_ARG;
+    const uint32_t L = d->num_levels, nl = d->num_layers;
+    if (L == 0 || L > 32 || nl == 0 || nl > DWG_NERF_MAX_LAYERS || d->out_dim < 2 || d->out_dim > 16) return DWG_E_ARG;
+    if (nl > 1 && (d->hidden == 0 || d->hidden > 64)) return DWG_E_ARG;
+    if (d->precision > 1 || d->density_activation > 2 || d->density_prior > 2 || d->gridtype > 1 || d->interp > 1) return DWG_E_ARG;
+    if (!(d->bound > 0.f) || !d->embeddings || !d->offsets) return DWG_E_ARG;
+    if (d->density_activation == 2 && !d->sigma_scale) return DWG_E_ARG;
+    for (uint32_t l = 0; l < nl; l++) if (!d->weight[l] || !d->bias[l]) return DWG_E_ARG;
+    p = NfP{};
+    p.g = GridP{0u, L, d->log2_per_level_scale, d->base_resolution, d->gridtype, d->align_corners ? 1u : 0u, d->interp, 1u};
+    p.table = reinterpret_cast<const float2*>(d->embeddings);
+    p.offsets = d->offsets;
+    p.bound = d->bound;
+    p.inv2b = 1.0f / (2.0f * d->bound);
+    p.nl = nl; p.W = d->out_dim;
+    p.act = d->density_activation; p.prior = d->density_prior; p.sig = d->albedo_sigmoid ? 1u : 0u; p.raw = d->raw ? 1u : 0u;
+    p.sigma_scale = d->sigma_scale;
+    const uint32_t esz = d->precision ? 2u : 4u, pad = 16u / esz;
+    uint32_t off = 0, poff = 0;
+    p.bb[0] = 0;
+    p.sumN = 0;
+    for (uint32_t l = 0; l < nl; l++) {
+        p.K[l] = l == 0 ? 2u * L : d->hidden;
+        p.N[l] = l + 1 == nl ? d->out_dim : d->hidden;
+        p.KP[l] = (p.K[l] + 15u) / 16u * 16u;
+        p.NP[l] = (p.N[l] + 15u) / 16u * 16u;
+        p.w[l] = d->weight[l]; p.b[l] = d->bias[l];
+        p.woff[l] = off; p.wst[l] = p.KP[l] + pad; off += p.NP[l] * p.wst[l];
+        p.pw[l] = poff; p.pb[l] = poff + p.N[l] * p.K[l]; poff = p.pb[l] + p.N[l];
+        p.bb[l + 1] = p.bb[l] + (p.NP[l] / 16u) * (p.KP[l] / 16u);
+        p.sumN += p.N[l];
+    }
+    p.P = poff + 1u;
+    p.aoff[0] = off; p.ast[0] = p.KP[0] + pad; off += NF_TILE * p.ast[0];
+    for (uint32_t l = 0; l < nl; l++) { p.aoff[l + 1] = off; p.ast[l + 1] = p.NP[l] + pad; off += NF_TILE * p.ast[l + 1]; }
+    p.bias_byte_off = (uint32_t)dwg_align_up((size_t)off * esz, 16);
+    lds_bytes = p.bias_byte_off + (256 + 2 * NF_TILE * 3 + NF_TILE) * sizeof(float);
+    if (lds_bytes > 160 * 1024 || p.bb[nl] > 4u * NF_MAXS || p.sumN > 256) return DWG_E_ARG;
+    return DWG_OK;
+}
+
+template <typename K>
+void lds_opt_in(K* kernel, bool& done) {
+    if (!done) { hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); done = true; }
+}
+
+uint64_t nf_chunk(uint64_t M) { return M < NF_CHUNK ? M : NF_CHUNK; }
+uint32_t nf_bwd_groups(uint64_t M) { const uint64_t t = (M + NF_TILE - 1) / NF_TILE; return (uint32_t)(t < NF_BWD_WG ? t : NF_BWD_WG); }
+
+}  // namespace
+
+extern "C" {
+
+int dwg_nerf_field_forward(const dwg_nerf_field_desc* desc, const float* x, uint64_t M, float* sigma, void* albedo, dwg_stream_t stream) {
+    NfP p;
+    size_t lds = 0;
+    int rc = make_params(desc, p, lds);
+    if (rc) return rc;
+    if (M == 0) return DWG_OK;
+    if (!x || !sigma || !albedo) return DWG_E_ARG;
+    const uint64_t ntiles = (M + NF_TILE - 1) / NF_TILE;
+    const unsigned grid = (unsigned)(ntiles < 4096 ? ntiles : 4096);
+    hipStream_t st = (hipStream_t)stream;
+    if (desc->precision) {
+        static bool attr = false; lds_opt_in(&k_nf_fwd<_Float16>, attr);
+        DWG_LAUNCH("nerf_field_fwd", k_nf_fwd<_Float16>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, sigma, (_Float16*)albedo);
+    } else {
+        static bool attr = false; lds_opt_in(&k_nf_fwd<float>, attr);
+        DWG_LAUNCH("nerf_field_fwd", k_nf_fwd<float>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, sigma, (float*)albedo);
+    }
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+size_t dwg_nerf_field_backward_workspace_bytes(const dwg_nerf_field_desc* desc, uint64_t M) {
+    NfP p;
+    size_t lds = 0;
+    if (make_params(desc, p, lds) || M == 0) return 0;
+    const uint64_t ch = nf_chunk(M);
+    size_t b = dwg_align_up((size_t)nf_bwd_groups(M) * p.P * sizeof(float), 256) + dwg_align_up((size_t)ch * p.K[0] * sizeof(float), 256) +
+               dwg_align_up((size_t)ch * 3 * sizeof(float), 256);
+    if (desc->host_offsets) b += dwg_grid_backward_slabs_workspace_bytes((uint32_t)ch, desc->num_levels, (uint32_t)desc->host_offsets[desc->num_levels]);
+    return b;
+}
+
+int dwg_nerf_field_backward(const dwg_nerf_field_desc* desc, const float* x, uint64_t M, const float* dsigma, const void* dalbedo,
+                            const dwg_nerf_field_grads* grads, void* workspace, size_t workspace_bytes, dwg_stream_t stream) {
+    NfP p;
+    size_t lds = 0;
+    int rc = make_params(desc, p, lds);
+    if (rc) return rc;
+    if (!grads) return DWG_E_ARG;
+    if (M == 0) return DWG_OK;
+    if (!x || !dsigma || !dalbedo) return DWG_E_ARG;
+    bool want_w = grads->sigma_scale != nullptr;
+    for (uint32_t l = 0; l < p.nl; l++) want_w = want_w || grads->weight[l] || grads->bias[l];
+    const bool want_t = grads->embeddings != nullptr;
+    if (grads->sigma_scale && p.act != 2) return DWG_E_ARG;
+    if (want_t) {
+        if (!desc->host_offsets) return DWG_E_ARG;
+        if ((uint64_t)desc->host_offsets[desc->num_levels] > 16384ull * 4096ull) return DWG_E_ARG;      // the slab pass's table limit
+    }
+    if (!want_w && !want_t) return DWG_OK;
+    if (!workspace || ((uintptr_t)workspace & 255u)) return DWG_E_ARG;
+    if (workspace_bytes < dwg_nerf_field_backward_workspace_bytes(desc, M)) return DWG_E_CAPACITY;
+    const uint64_t ch = nf_chunk(M);
+    const uint32_t G = nf_bwd_groups(M);
+    unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
+    float* partial = reinterpret_cast<float*>(w); w += dwg_align_up((size_t)G * p.P * sizeof(float), 256);
+    float* d_enc = reinterpret_cast<float*>(w); w += dwg_align_up((size_t)ch * p.K[0] * sizeof(float), 256);
+    float* xn = reinterpret_cast<float*>(w); w += dwg_align_up((size_t)ch * 3 * sizeof(float), 256);
+    void* slab_ws = w;
+    const size_t slab_bytes = want_t ? workspace_bytes - (size_t)(w - reinterpret_cast<unsigned char*>(workspace)) : 0;
+    hipStream_t st = (hipStream_t)stream;
+    for (uint64_t m0 = 0; m0 < M; m0 += ch) {
+        const uint64_t n = M - m0 < ch ? M - m0 : ch;
+        if (desc->precision) {
+            static bool attr = false; lds_opt_in(&k_nf_bwd<_Float16>, attr);
+            DWG_LAUNCH("nerf_field_bwd", k_nf_bwd<_Float16>, dim3(G), dim3(256), lds, st, p, x, m0, n, dsigma, (const _Float16*)dalbedo,
+                       want_t ? d_enc : nullptr, want_t ? xn : nullptr, partial, m0 == 0 ? 1 : 0, want_w ? 1 : 0);
+        } else {
+            static bool attr = false; lds_opt_in(&k_nf_bwd<float>, attr);
+            DWG_LAUNCH("nerf_field_bwd", k_nf_bwd<float>, dim3(G), dim3(256), lds, st, p, x, m0, n, dsigma, (const float*)dalbedo,
+                       want_t ? d_enc : nullptr, want_t ? xn : nullptr, partial, m0 == 0 ? 1 : 0, want_w ? 1 : 0);
+        }
+        DWG_RETURN_IF_LAUNCH_FAILED();
+        if (want_t) {
+            rc = dwg_grid_encode_backward_slabs_accumulate(d_enc, xn, desc->embeddings, desc->offsets, grads->embeddings, (uint32_t)n, 3u, 2u,
+                                                           desc->num_levels, desc->log2_per_level_scale, desc->base_resolution, nullptr, nullptr,
+                                                           desc->gridtype, desc->align_corners ? 1u : 0u, desc->interp, 1u, desc->host_offsets,
+                                                           slab_ws, slab_bytes, stream);
+            if (rc) return rc;
+        }
+    }
+    if (want_w) {
+        DWG_LAUNCH("nerf_field_wgrad_reduce", k_nf_reduce, dim3((p.P + 255u) / 256u), dim3(256), 0, st, p, G, (const float*)partial, *grads);
+        DWG_RETURN_IF_LAUNCH_FAILED();
+    }
+    return DWG_OK;
+}
+
+}  // extern "C"

@@ -10,6 +10,13 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
   B2  core.nerf.gridencoder backend         dropin/_gridencoder.py               (found through PYTHONPATH before the JIT build)
   B6  _raymarchingrgb / _raymarchinglatent  dropin/_raymarching{rgb,latent}.py    (found through PYTHONPATH; nothing to patch -- the NeRF
                                              stage's ray marcher, core/nerf/raymarching/*/raymarching.py:14-27)
+  B7  core.nerf.nerf_model.build_NeRFNetwork (nerf_model.py:565-574)  -> the reference builds ITS network (resolved at call time:
+                                             trainer.py:499-501), then dreamwaltz_g_amd.nerf.bind_nerf_network rebinds common_forward and
+                                             local_geometry_forward of that object to the fused field kernel (grid encoding -> sigma_net ->
+                                             density / albedo); density, forward, normal and update_extra_state reach it through them.  The
+                                             network's own Parameters are read in place.  What the kernel does not cover (dual_mlp / dual_enc,
+                                             density_prior smpl, a decoder_layer, a non-grid backbone) stays unbound with the reason in
+                                             `_dwg_nerf_unbound`.  DWG_BIND_NERF=0: nothing is bound
   B3  core.system.avatar.build_gaussian_avatar (avatar.py:1642-1714)  -> the reference builds ITS avatar (point cloud, nearest triangles,
                                              inverse LBS, LBS weights ...), then `DreamWaltzG.from_reference(ref)` adopts every Parameter
                                              and buffer by name; non-DreamWaltzG gs_types are returned untouched (reference path)
@@ -21,7 +28,8 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              built from the loaded modules' state_dict()s.  Everything else (get_text_embeds, __call__,
                                              calc_gradients, tp_scheduler, pipe, decode_latents, isinstance checks) is the reference's own.
 
-Environment: DWG_BIND_DTYPE = f32x | f32 | f16 | bf16  storage type of the denoiser / VAE plans.  Unset: the precision the reference loaded its
+Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's field network (B7) on the reference path
+             DWG_BIND_DTYPE = f32x | f32 | f16 | bf16  storage type of the denoiser / VAE plans.  Unset: the precision the reference loaded its
                                                      pipeline in -- torch.float32 (its default, core/guidance/basic.py:233) -> f32x (fp32-grade
                                                      split precision on the 16-bit MFMA pipe), torch.float16 (`--guide.dtype fp16`,
                                                      basic.py:24-27) -> f16.  bf16 narrows the user's precision: only on request
@@ -73,6 +81,34 @@ def _patch_avatar_module(mod):
     setattr(build_gaussian_avatar, _PATCHED, True)
     build_gaussian_avatar.__wrapped__ = orig
     mod.build_gaussian_avatar = build_gaussian_avatar
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# B7: the NeRF stage's field network
+# --------------------------------------------------------------------------------------------------------------------------------------
+def bind_nerf(ref):
+    """Bind a constructed reference NeRF network to the fused field kernel; returns it (bound or, with the reason recorded, not)."""
+    if os.environ.get("DWG_BIND_NERF", "1") == "0":
+        return ref
+    _pkg()
+    from dreamwaltz_g_amd.nerf import bind_nerf_network
+    reason = bind_nerf_network(ref)
+    if reason is not None:
+        print("[dwg_bind] NeRF field left on the reference path: %s" % reason, file=sys.stderr)
+    return ref
+
+
+def _patch_nerf_module(mod):
+    orig = mod.build_NeRFNetwork
+    if getattr(orig, _PATCHED, False):
+        return
+
+    def build_NeRFNetwork(cfg):
+        return bind_nerf(orig(cfg))
+    build_NeRFNetwork.__doc__ = orig.__doc__
+    setattr(build_NeRFNetwork, _PATCHED, True)
+    build_NeRFNetwork.__wrapped__ = orig
+    mod.build_NeRFNetwork = build_NeRFNetwork
 
 
 # --------------------------------------------------------------------------------------------------------------------------------------
@@ -209,7 +245,7 @@ def _patch_guidance_module(mod):
 # post-import hooks
 # --------------------------------------------------------------------------------------------------------------------------------------
 HOOKS = {"core.system.avatar": _patch_avatar_module, "core.system.scene": _patch_scene_module,
-         "core.guidance.controlnet": _patch_guidance_module}
+         "core.guidance.controlnet": _patch_guidance_module, "core.nerf.nerf_model": _patch_nerf_module}
 
 
 class _HookLoader(importlib.abc.Loader):
@@ -270,7 +306,7 @@ def uninstall():
         mod = sys.modules.get(name)
         if mod is None:
             continue
-        for attr in ("build_gaussian_avatar", "build_scene"):
+        for attr in ("build_gaussian_avatar", "build_scene", "build_NeRFNetwork"):
             f = getattr(mod, attr, None)
             if f is not None and getattr(f, _PATCHED, False):
                 setattr(mod, attr, f.__wrapped__)
