@@ -104,6 +104,14 @@ SIGNATURES = {
     "dwg_nerf_field_backward_workspace_bytes": (_sz, [ctypes.POINTER(NerfFieldDescC), ctypes.c_uint64]),
     "dwg_nerf_field_backward": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _vp, _vp,
                                                ctypes.POINTER(NerfFieldGradsC), _vp, _sz, _vp]),
+    # include/dwg_sigma.h
+    "dwg_sigma_face_records": (ctypes.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "dwg_sigma_area_cdf": (ctypes.c_int, [_i32, _vp, _vp, _vp]),
+    "dwg_sigma_vertex_normals": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dwg_sigma_sample": (ctypes.c_int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dwg_sigma_distance_workspace_bytes": (_sz, [_i32, _i32]),
+    "dwg_sigma_point_mesh_distance": (ctypes.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dwg_sigma_keep_mask": (ctypes.c_int, [_i32, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp]),
     # include/dwg_raymarch.h
     "dwg_raymarch_near_far_from_aabb": (ctypes.c_int, [_vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp]),
     "dwg_raymarch_sph_from_ray": (ctypes.c_int, [_vp, _vp, _f32, _u32, _vp, _vp]),

@@ -17,6 +17,12 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              network's own Parameters are read in place.  What the kernel does not cover (dual_mlp / dual_enc,
                                              density_prior smpl, a decoder_layer, a non-grid backbone) stays unbound with the reason in
                                              `_dwg_nerf_unbound`.  DWG_BIND_NERF=0: nothing is bound
+  B8  core.trainer.Trainer.calc_sigma_loss (trainer.py:718-825)     -> dreamwaltz_g_amd.sigma_guidance.calc_sigma_loss: the SMPL-X sigma
+                                             guidance's geometry (part-mesh normals, area-weighted samples, point-to-mesh distance, keep
+                                             mask) on the device instead of trimesh + igl on the host, with no host sync; the loss runs
+                                             on the reference's own network (B7 when bound).  CPU vertices and unknown sigma_loss_types
+                                             go to the original method.  The samples are drawn from torch's CUDA generator: the same
+                                             distribution as trimesh's, not the same draws.  DWG_BIND_SIGMA=0: nothing is bound
   B3  core.system.avatar.build_gaussian_avatar (avatar.py:1642-1714)  -> the reference builds ITS avatar (point cloud, nearest triangles,
                                              inverse LBS, LBS weights ...), then `DreamWaltzG.from_reference(ref)` adopts every Parameter
                                              and buffer by name; non-DreamWaltzG gs_types are returned untouched (reference path)
@@ -29,6 +35,7 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              calc_gradients, tp_scheduler, pipe, decode_latents, isinstance checks) is the reference's own.
 
 Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's field network (B7) on the reference path
+             DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
              DWG_BIND_DTYPE = f32x | f32 | f16 | bf16  storage type of the denoiser / VAE plans.  Unset: the precision the reference loaded its
                                                      pipeline in -- torch.float32 (its default, core/guidance/basic.py:233) -> f32x (fp32-grade
                                                      split precision on the 16-bit MFMA pipe), torch.float16 (`--guide.dtype fp16`,
@@ -109,6 +116,38 @@ def _patch_nerf_module(mod):
     setattr(build_NeRFNetwork, _PATCHED, True)
     build_NeRFNetwork.__wrapped__ = orig
     mod.build_NeRFNetwork = build_NeRFNetwork
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# B8: the NeRF stage's SMPL-X sigma guidance
+# --------------------------------------------------------------------------------------------------------------------------------------
+def _sigma_covered(trainer, data):
+    verts = getattr(data.get('smpl_outputs') if isinstance(data, dict) else None, 'vertices', None)
+    if verts is None or not getattr(verts, 'is_cuda', False):
+        return False
+    _pkg()
+    from dreamwaltz_g_amd.sigma_guidance import LOSS_TYPES
+    return getattr(trainer.cfg, 'sigma_loss_type', None) in LOSS_TYPES
+
+
+def _patch_trainer_module(mod):
+    if os.environ.get("DWG_BIND_SIGMA", "1") == "0":
+        return
+    cls = mod.Trainer
+    orig = cls.calc_sigma_loss
+    if getattr(orig, _PATCHED, False):
+        return
+    import functools
+
+    @functools.wraps(orig)
+    def calc_sigma_loss(self, data, render_outputs, sd_inputs, selected_parts, wo_wrist: bool = True):
+        if not _sigma_covered(self, data):
+            return orig(self, data, render_outputs, sd_inputs, selected_parts, wo_wrist=wo_wrist)
+        from dreamwaltz_g_amd.sigma_guidance import calc_sigma_loss as native
+        return native(self, data, render_outputs, sd_inputs, selected_parts, wo_wrist=wo_wrist, logger=getattr(mod, 'logger', None))
+    setattr(calc_sigma_loss, _PATCHED, True)
+    calc_sigma_loss.__wrapped__ = orig
+    cls.calc_sigma_loss = calc_sigma_loss
 
 
 # --------------------------------------------------------------------------------------------------------------------------------------
@@ -245,7 +284,8 @@ def _patch_guidance_module(mod):
 # post-import hooks
 # --------------------------------------------------------------------------------------------------------------------------------------
 HOOKS = {"core.system.avatar": _patch_avatar_module, "core.system.scene": _patch_scene_module,
-         "core.guidance.controlnet": _patch_guidance_module, "core.nerf.nerf_model": _patch_nerf_module}
+         "core.guidance.controlnet": _patch_guidance_module, "core.nerf.nerf_model": _patch_nerf_module,
+         "core.trainer": _patch_trainer_module}
 
 
 class _HookLoader(importlib.abc.Loader):
@@ -313,3 +353,6 @@ def uninstall():
         cls = getattr(mod, "ControlNetScoreDistillation", None)
         if cls is not None and getattr(cls.__init__, _PATCHED, False):
             cls.__init__ = cls.__init__.__wrapped__
+        cls = getattr(mod, "Trainer", None)
+        if cls is not None and getattr(cls.__dict__.get("calc_sigma_loss"), _PATCHED, False):
+            cls.calc_sigma_loss = cls.calc_sigma_loss.__wrapped__
