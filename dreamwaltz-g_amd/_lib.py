@@ -104,6 +104,9 @@ SIGNATURES = {
     "dwg_nerf_field_backward_workspace_bytes": (_sz, [ctypes.POINTER(NerfFieldDescC), ctypes.c_uint64]),
     "dwg_nerf_field_backward": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _vp, _vp,
                                                ctypes.POINTER(NerfFieldGradsC), _vp, _sz, _vp]),
+    # include/dwg_background.h
+    "dwg_video_composite_forward": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "dwg_video_composite_backward": (ctypes.c_int, [_i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     # include/dwg_sigma.h
     "dwg_sigma_face_records": (ctypes.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "dwg_sigma_area_cdf": (ctypes.c_int, [_i32, _vp, _vp, _vp]),

@@ -48,6 +48,7 @@ class RenderConfig:
     use_fixed_n_gaussians: Optional[int] = None
     avatar_transl: Optional[str] = None
     avatar_scale: Optional[str] = None
+    use_video_background: Optional[str] = None       # a video file (or "motionx_reenact,<name>" through the reference): scene.py:229-230
     use_densifier: bool = False                      # configs/__init__.py:159-171 (off in every shipped recipe)
     densify_from_iter: Optional[int] = None
     densify_until_iter: Optional[int] = None

@@ -8,7 +8,11 @@ about as much: the eager loop is host-bound.  A replay costs one copy of the pos
 What is static in the graph: the camera, the Gaussian count and the pair-buffer capacity of the rasterizer (frozen at 1.5x the largest
 count of the warm-up frames, at least the running capacity).  A frame that needs more pairs than that is TRUNCATED by the kernels and
 flags it (in the graph's OWN pair state: eager frames through the same Scene keep the renderer's); `GraphedAnimation.check()` (one stream synchronisation) reports it, and `recapture()` grows the capacity.  Callers that cannot
-tolerate a truncated frame call check() per frame -- that still skips all the per-frame host work."""
+tolerate a truncated frame call check() per frame -- that still skips all the per-frame host work.
+
+A scene with a video background (background.VideoBackground, bg_mode not a pure colour) gets the frame index as one more static input:
+an int32 device word the captured composite reads, set per `replay(pose, frame_index=i)` by a device-to-device copy from the
+background's index table -- one capture replays a whole clip with no host sync."""
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -16,9 +20,9 @@ import torch
 
 class GraphedAnimation:
     def __init__(self, scene, data: dict, example_pose: Optional[Dict[str, torch.Tensor]], warmup_poses: Optional[Iterable[dict]] = None,
-                 bg_mode: Optional[str] = None):
+                 bg_mode: Optional[str] = None, frame_index: Optional[int] = None):
         """`example_pose` None: the canonical-pose frame (Scene.forward without observed pose: BASELINE config c1) -- no per-frame input at
-        all, a replay is one graph launch."""
+        all, a replay is one graph launch.  `frame_index`: the first frame of a video background (default data['frame_index'], else 0)."""
         self.scene, self.data, self.bg_mode = scene, data, bg_mode
         self.device = next(iter(example_pose.values())).device if example_pose is not None else torch.device(data['extrinsic'].device)
         if self.device.type != "cuda":
@@ -26,6 +30,11 @@ class GraphedAnimation:
         if not scene.renderer.async_pair_count:
             raise ValueError("GraphedAnimation needs a renderer with async_pair_count=True (no host read-back inside the frame)")
         self.pose = {k: v.clone() for k, v in example_pose.items()} if example_pose is not None else None      # static inputs of the graph
+        self.frame_index = None
+        if getattr(scene, "background", None) is not None and bg_mode not in scene.pure_colors:
+            self.frame_index = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.set_frame_index(frame_index if frame_index is not None else data.get('frame_index', 0))
+            self.data = dict(data, frame_index=self.frame_index)
         self.graph, self.outputs = None, None
         self._state = None
         self._capture(list(warmup_poses) if warmup_poses is not None else [example_pose] * (1 if example_pose is not None else 3))
@@ -98,9 +107,17 @@ class GraphedAnimation:
         for k, v in pose.items():
             self.pose[k].copy_(v, non_blocking=True)
 
-    def replay(self, pose: Optional[Dict[str, torch.Tensor]] = None) -> dict:
+    def set_frame_index(self, frame_index):
+        """Video background: the frame the next replay composites (host-checked like the reference's list: IndexError out of range)."""
+        if self.frame_index is None:
+            raise ValueError("this GraphedAnimation has no video background")
+        self.frame_index.copy_(self.scene.background.index_tensor(frame_index, self.device, count=1), non_blocking=True)
+
+    def replay(self, pose: Optional[Dict[str, torch.Tensor]] = None, frame_index: Optional[int] = None) -> dict:
         """One frame: the outputs dict of Scene.forward (static tensors, overwritten by the next replay)."""
         self.set_pose(pose)
+        if frame_index is not None:
+            self.set_frame_index(frame_index)
         self.graph.replay()
         return self.outputs
 

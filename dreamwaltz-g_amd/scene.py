@@ -1,7 +1,8 @@
 """Mirror of Scene (/root/reference/core/system/scene.py:15-168; SURVEY.md section 8a row R7, boundary B5): avatar_forward
 (optional per-avatar scale / translation), multi-avatar merge, the debug overrides, GaussianRenderer.render, and the background
-compositing `image + bg (1 - alpha)` for bg_mode in {black, white, gray}.  Learned / video / Gaussian backgrounds are outside the
-hot path (scene.py:123-132,158-165) and are rejected."""
+compositing `image + bg (1 - alpha)` for bg_mode in {black, white, gray} and for a video background (background.VideoBackground:
+the frames on the device, one launch per frame chain).  Learned (MLP) and Gaussian backgrounds are outside the hot path
+(scene.py:123-132,162-165) and are rejected."""
 from typing import Iterable, Optional
 
 import contextlib
@@ -10,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from .avatar import DreamWaltzG, GaussianOutput, merge_gaussians
+from .background import VideoBackground, video_composite
 from .renderer import GaussianRenderer
 
 
@@ -37,15 +39,16 @@ def downsample_gaussians(gaussians: GaussianOutput, n: int) -> GaussianOutput:
 class Scene(nn.Module):
     def __init__(self, cfg, avatar, background=None, async_pair_count=False) -> None:
         super().__init__()
-        if background is not None:
-            raise NotImplementedError("learned / video / Gaussian backgrounds are outside the SDS hot path (scene.py:123-132,158-165)")
+        if background is not None and not isinstance(background, VideoBackground):
+            raise NotImplementedError("learned (MLP) and Gaussian backgrounds are outside the SDS hot path (scene.py:123-132,162-165); "
+                                      "a video background is a background.VideoBackground")
         self.device = torch.device(cfg.device)
         if isinstance(avatar, DreamWaltzG):
             self.avatar, self.avatars = avatar, None
         else:
             self.avatars = nn.ModuleList(avatar)
             self.avatar = self.avatars[0]
-        self.background = None
+        self.background = background
         self.pure_colors = PureColorBackground()
         self.renderer = GaussianRenderer(sh_levels=cfg.render.sh_levels, bg_color=cfg.render.bg_color, async_pair_count=async_pair_count)
         r = cfg.render
@@ -76,15 +79,32 @@ class Scene(nn.Module):
             gaussians.positions = gaussians.positions + t.unsqueeze(0)
         return gaussians
 
-    def forward_frames(self, data: dict, poses, bg_mode: Optional[str] = None, frozen_avatar: bool = False) -> dict:
+    def _video_indices(self, data, frame_indices):
+        if frame_indices is not None:
+            return frame_indices
+        if isinstance(data, (list, tuple)):
+            idx = [d.get('frame_index') for d in data]
+            if any(i is None for i in idx):
+                idx = None
+            elif any(isinstance(i, torch.Tensor) and i.is_cuda for i in idx):
+                idx = torch.cat([i.reshape(-1).to(torch.int32) for i in idx])
+        else:
+            idx = data.get('frame_index')
+        if idx is None:
+            raise ValueError("a video background needs one frame index per frame: frame_indices= or data['frame_index']")
+        return idx
+
+    def forward_frames(self, data: dict, poses, bg_mode: Optional[str] = None, frozen_avatar: bool = False, frame_indices=None) -> dict:
         """Playback of F pose frames under one camera (`data`: the loader's dict) or each under its own (`data`: a list of F dicts, as the
         reference's evaluation loader yields them): `animate` per pose, then ONE rasterizer launch chain for all of them
         (renderer.render_frames).  Frame f equals `forward(data, poses[f], use_densifier=False, bg_mode=bg_mode)` bit for bit -- the
         reference's evaluation loop renders such sequences one pose at a time under inference mode (trainer.py:1019-1150).  Single avatar,
         no gradients.  `frozen_avatar`: the avatar's parameters do not change between the frames (a trained avatar playing a motion): the
         pose-independent part of `animate` -- canonical positions, grid encoding, colour / opacity network -- is computed once and kept until
-        a parameter changes (avatar.DreamWaltzG.frozen_playback; same bits, 0.3 ms less per 300 k-Gaussian frame).
-        -> {'image' | 'image_fg' | 'depth' | 'alpha': [F, H, W, C]}."""
+        a parameter changes (avatar.DreamWaltzG.frozen_playback; same bits, 0.3 ms less per 300 k-Gaussian frame).  A video background
+        takes one frame index per frame (`frame_indices`: ints or an int32 CUDA tensor; else each data dict's 'frame_index', or a
+        single dict's list / tensor of F) and composites all F frames in one launch after the rasterizer chain.
+        -> {'image' | 'image_fg' | 'image_bg' | 'depth' | 'alpha': [F, H, W, C]}."""
         if self.avatars is not None:
             raise NotImplementedError("forward_frames renders one avatar per frame")
         frames = []
@@ -108,6 +128,11 @@ class Scene(nn.Module):
             outputs['image_bg'] = self.pure_colors.get_background_like(bg_mode, outputs['image'])
             outputs['image_fg'] = outputs['image']
             outputs['image'] = outputs['image'] + outputs['image_bg'] * (1 - outputs['alpha'])
+        elif self.background is not None:
+            image, outputs['image_bg'] = video_composite(outputs['image'], outputs['alpha'], self.background,
+                                                         self._video_indices(data, frame_indices))
+            outputs['image_fg'] = outputs['image']
+            outputs['image'] = image
         else:
             outputs['image_fg'] = outputs['image']
         return outputs
@@ -144,10 +169,17 @@ class Scene(nn.Module):
             for side in streams[:len(frames)]:
                 main.wait_stream(side)
         out = self.renderer.render_frames(data=list(datas), frames=frames)
+        video = bg_mode not in self.pure_colors and self.background is not None
+        if video:                                          # all V views in one launch; view v's pixels are those of forward()
+            composite, bg = video_composite(out['image'], out['alpha'], self.background, self._video_indices(list(datas), None))
         views = []
         for v in range(len(frames)):
             o = {k: t[v:v + 1] for k, t in out.items()}
-            if bg_mode in self.pure_colors:
+            if video:
+                o['image_bg'] = bg[v]
+                o['image_fg'] = o['image']
+                o['image'] = composite[v:v + 1]
+            elif bg_mode in self.pure_colors:
                 o['image_bg'] = self.pure_colors.get_background_like(bg_mode, o['image'])
                 o['image_fg'] = o['image']
                 o['image'] = o['image'] + o['image_bg'] * (1 - o['alpha'])
@@ -180,6 +212,12 @@ class Scene(nn.Module):
             outputs['image_bg'] = self.pure_colors.get_background_like(bg_mode, outputs['image'])
             outputs['image_fg'] = outputs['image']
             outputs['image'] = outputs['image'] + outputs['image_bg'] * (1 - outputs['alpha'])
+        elif self.background is not None:
+            # scene.py:157-160: image_bg is the [H, W, 3] frame of data['frame_index'] (an int, or an int32 CUDA tensor of one index)
+            image, image_bg = video_composite(outputs['image'], outputs['alpha'], self.background, data['frame_index'])
+            outputs['image_bg'] = image_bg[0]
+            outputs['image_fg'] = outputs['image']
+            outputs['image'] = image
         else:
             outputs['image_fg'] = outputs['image']
         return outputs

@@ -27,7 +27,9 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              inverse LBS, LBS weights ...), then `DreamWaltzG.from_reference(ref)` adopts every Parameter
                                              and buffer by name; non-DreamWaltzG gs_types are returned untouched (reference path)
   B5  core.system.scene.build_scene (scene.py:224-245)                -> dreamwaltz_g_amd.scene.Scene around that avatar (same forward /
-                                             state_dict / avatar.get_optimizer surface the Trainer uses: trainer.py:578-604,680-709,859-890)
+                                             state_dict / avatar.get_optimizer surface the Trainer uses: trainer.py:578-604,680-709,859-890).
+                                             `--render.use_video_background`: the reference's VideoBackground decodes the video, and
+                                             dreamwaltz_g_amd.background.VideoBackground.from_reference adopts its frames on the device
   B4  core.guidance.controlnet.ControlNetScoreDistillation (controlnet.py:75-114) -> the reference constructs its object as always
                                              (diffusers pipeline, text encoder, schedulers); after __init__ the two hot methods of THAT object,
                                              `_predict` (controlnet.py:83-114) and `encode_images` (vae.py:34-40), are bound to the HIP plans
@@ -166,11 +168,17 @@ def _patch_scene_module(mod):
         from dreamwaltz_g_amd.scene import Scene
         import torch
         r = cfg.render
-        if r.use_mlp_background or r.use_video_background or r.use_gs_background:
-            raise NotImplementedError("learned / video / Gaussian backgrounds are outside the bound hot path (scene.py:226-237)")
+        if r.use_mlp_background or r.use_gs_background:
+            raise NotImplementedError("learned / Gaussian backgrounds are outside the bound hot path (scene.py:226-237)")
+        background = None
+        if r.use_video_background:
+            # the reference's OWN VideoBackground (resolved at call time like its build_scene does: scene.py:229-230) decodes the video,
+            # with its motionx temp-file extraction; the adopted device store keeps it alive (its __del__ removes that file)
+            from dreamwaltz_g_amd.background import VideoBackground
+            background = VideoBackground.from_reference(mod.VideoBackground(r.use_video_background))
         # exact pair sizing through the 16-byte read-back per frame, like the reference's CUDA extension: the reference's loop body does
         # not know about re-rendering a truncated frame
-        return Scene(cfg, avatar, background=None, async_pair_count=False).to(torch.device(cfg.device))
+        return Scene(cfg, avatar, background=background, async_pair_count=False).to(torch.device(cfg.device))
     setattr(build_scene, _PATCHED, True)
     build_scene.__wrapped__ = orig
     mod.build_scene = build_scene
