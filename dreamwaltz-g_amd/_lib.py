@@ -90,15 +90,9 @@ SIGNATURES = {
                                                _u32, _vp]),
     "dwg_grid_encode_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32,
                                                 _u32, _u32, _u32, _vp, _vp]),
-    "dwg_grid_encode_backward_xcd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32,
-                                                    _u32, _u32, _u32, _vp, _vp, _vp]),
-    "dwg_grid_encode_backward_owner": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32,
-                                                      _u32, _u32, _u32, _vp, _vp, _vp]),
     "dwg_grid_backward_slabs_workspace_bytes": (_sz, [_u32, _u32, _u32]),
     "dwg_grid_encode_backward_slabs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32, _u32,
-                                                      _u32, _u32, _vp, _vp, _sz, _vp]),
-    "dwg_grid_encode_backward_slabs_accumulate": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32,
-                                                                 _u32, _u32, _u32, _vp, _vp, _sz, _vp]),
+                                                      _u32, _u32, _vp, _vp, _sz, _i32, _vp]),
     # include/dwg_nerf.h
     "dwg_nerf_field_forward": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _vp, _vp, _vp]),
     "dwg_nerf_field_backward_workspace_bytes": (_sz, [ctypes.POINTER(NerfFieldDescC), ctypes.c_uint64]),

@@ -64,25 +64,12 @@ __global__ __launch_bounds__(256) void k_grid_fwd(GridP p, const float* __restri
     }
 }
 
-// grad_table += w * grad (atomics), and grad_x[b,d] = sum_{l,c} grad[b,l,c] * dy_dx[b,l,d,c]
-// XCD-private accumulation (XCD = true): device-scope float atomics are executed at the memory side on this chip (the 8 XCD L2s
-// are not coherent with each other): one fabric transaction per atomic, ~13 G atomics/s measured.  Instead every XCD adds into
-// ITS OWN copy of the table gradient with workgroup-scope atomics, which the XCD's L2 executes in cache (all CUs of an XCD share
-// that L2, and a wave never leaves its XCD: HW_REG_XCC_ID is where it physically runs).  The copies are summed (and cleared) by
-// k_xcd_reduce_clear afterwards.  Which copy a contribution lands in changes only the summation order.
-__device__ __forceinline__ uint32_t xcc_id() { return __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7u; }   // HW_REG_XCC_ID[3:0]
-
-template <bool XCD>
-__device__ __forceinline__ void table_add(float* p, float v) {
-    if (XCD) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else atomicAdd(p, v);
-}
-
-template <bool XCD>
+// grad_table += w * grad (device-scope float atomics), and grad_x[b,d] = sum_{l,c} grad[b,l,c] * dy_dx[b,l,d,c].  The path of small
+// calls and of tables beyond the slab path's limits; every such atomic is executed at the memory side on this chip (see the slab-binned
+// path below, which large calls take instead).
 __global__ __launch_bounds__(256) void k_grid_bwd(GridP p, const float* __restrict__ grad, const float* __restrict__ x,
                                                   const int* __restrict__ offsets, float* __restrict__ grad_table,
-                                                  const float* __restrict__ dy_dx, float* __restrict__ grad_x, uint32_t first_table_level,
-                                                  size_t xcd_stride) {
+                                                  const float* __restrict__ dy_dx, float* __restrict__ grad_x, uint32_t first_table_level) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     const uint32_t b = t / p.L, level = t - b * p.L;
     const bool live = b < p.B;
@@ -95,15 +82,15 @@ __global__ __launch_bounds__(256) void k_grid_bwd(GridP p, const float* __restri
         Cell c = locate(p, offsets, level, x0, x1, x2);
         if (!c.oob) {
             if (grad_table && level >= first_table_level) {
-                float* gt = grad_table + (size_t)(uint32_t)offsets[level] * 2 + (XCD ? xcc_id() * xcd_stride : (size_t)0);
+                float* gt = grad_table + (size_t)(uint32_t)offsets[level] * 2;
 #pragma unroll
                 for (int idx = 0; idx < 8; idx++) {
                     uint32_t cx = c.g[0] + (idx & 1), cy = c.g[1] + ((idx >> 1) & 1), cz = c.g[2] + ((idx >> 2) & 1);
                     float w = ((idx & 1) ? c.w[0] : 1.f - c.w[0]) * ((idx & 2) ? c.w[1] : 1.f - c.w[1]) *
                               ((idx & 4) ? c.w[2] : 1.f - c.w[2]);
                     uint32_t index = grid_index(p.gridtype, p.align_corners, c.hsize, c.res, cx, cy, cz);
-                    table_add<XCD>(gt + index, w * g0);
-                    table_add<XCD>(gt + index + 1, w * g1);
+                    atomicAdd(gt + index, w * g0);
+                    atomicAdd(gt + index + 1, w * g1);
                 }
             }
             if (dy_dx && grad_x) {
@@ -127,72 +114,6 @@ __global__ __launch_bounds__(256) void k_grid_bwd(GridP p, const float* __restri
             atomicAdd(&grad_x[3 * b], gx[0]); atomicAdd(&grad_x[3 * b + 1], gx[1]); atomicAdd(&grad_x[3 * b + 2], gx[2]);
         }
     }
-}
-
-// XCD-OWNED table slabs: every 128-byte line of the table gradient belongs to ONE XCD (owner = line index mod 8).  Each chunk of
-// 256 (point, level) lanes is visited by a workgroup on EVERY XCD; a workgroup evaluates all 8 corners but only adds to the entries
-// its own XCD owns -- with workgroup-scope atomics, which that XCD's L2 executes in cache.  No line is ever cached by two XCDs, so
-// there are no private copies to allocate, reduce or clear (the 8-copy variant above moved 4.9x the algorithmic traffic), and an
-// XCD's share of the table (1/8 = 6.3 MB) mostly stays in its 4 MiB L2 / the Infinity Cache.  The redundant index arithmetic
-// (8x) is a few tens of microseconds of VALU.  Work is handed out per PHYSICAL XCD (HW_REG_XCC_ID) through 8 counters, so
-// correctness does not depend on how workgroups are placed -- only on every XCD running at least one of them (checked: `done`).
-__global__ __launch_bounds__(256) void k_grid_bwd_owner(GridP p, uint32_t nchunks, const float* __restrict__ grad, const float* __restrict__ x,
-                                                        const int* __restrict__ offsets, float* __restrict__ grad_table,
-                                                        const float* __restrict__ dy_dx, float* __restrict__ grad_x,
-                                                        uint32_t first_table_level, uint32_t* __restrict__ counters /*[8] next chunk, [8..15] done*/) {
-    __shared__ uint32_t s_chunk;
-    const uint32_t my = xcc_id();
-    for (;;) {
-        if (threadIdx.x == 0) s_chunk = atomicAdd(&counters[my], 1u);
-        __syncthreads();
-        const uint32_t chunk = s_chunk;
-        __syncthreads();
-        if (chunk >= nchunks) break;
-        const uint32_t t = chunk * 256u + threadIdx.x;
-        const uint32_t b = t / p.L, level = t - b * p.L;
-        const bool live = b < p.B;
-        const bool do_x = dy_dx && grad_x && ((chunk & 7u) == my);      // exactly one of the 8 visits of a chunk
-        float gx[3] = {0.f, 0.f, 0.f};
-        if (live) {
-            const float* gsrc = p.layout ? grad + (size_t)b * p.L * 2 + level * 2 : grad + ((size_t)level * p.B + b) * 2;
-            const float g0 = gsrc[0], g1 = gsrc[1];
-            Cell c = locate(p, offsets, level, x[3 * b], x[3 * b + 1], x[3 * b + 2]);
-            if (!c.oob) {
-                if (level >= first_table_level) {
-                    const uint32_t lvl_off = (uint32_t)offsets[level] * 2u;
-#pragma unroll
-                    for (int idx = 0; idx < 8; idx++) {
-                        uint32_t cx = c.g[0] + (idx & 1), cy = c.g[1] + ((idx >> 1) & 1), cz = c.g[2] + ((idx >> 2) & 1);
-                        const uint32_t index = lvl_off + grid_index(p.gridtype, p.align_corners, c.hsize, c.res, cx, cy, cz);
-                        if (((index >> 5) & 7u) != my) continue;        // 32 floats = one 128-byte line
-                        float w = ((idx & 1) ? c.w[0] : 1.f - c.w[0]) * ((idx & 2) ? c.w[1] : 1.f - c.w[1]) *
-                                  ((idx & 4) ? c.w[2] : 1.f - c.w[2]);
-                        table_add<true>(grad_table + index, w * g0);
-                        table_add<true>(grad_table + index + 1, w * g1);
-                    }
-                }
-                if (do_x) {
-                    const float* dd = dy_dx + ((size_t)b * p.L + level) * 6;
-#pragma unroll
-                    for (int d = 0; d < 3; d++) gx[d] = g0 * dd[2 * d] + g1 * dd[2 * d + 1];
-                }
-            }
-        }
-        if (do_x) {
-            if (p.L == 16) {
-#pragma unroll
-                for (int d = 0; d < 3; d++) {
-                    float v = gx[d];
-                    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-                    gx[d] = v;
-                }
-                if (live && level == 0) { grad_x[3 * b] = gx[0]; grad_x[3 * b + 1] = gx[1]; grad_x[3 * b + 2] = gx[2]; }
-            } else if (live) {
-                atomicAdd(&grad_x[3 * b], gx[0]); atomicAdd(&grad_x[3 * b + 1], gx[1]); atomicAdd(&grad_x[3 * b + 2], gx[2]);
-            }
-        }
-    }
-    if (threadIdx.x == 0) atomicMax(&counters[8 + my], 1u);             // this XCD took part
 }
 
 // Coarse levels (a few thousand cells, hundreds of points per cell): the whole level table is privatised in LDS so the
@@ -224,21 +145,6 @@ __global__ __launch_bounds__(256) void k_grid_bwd_coarse(GridP p, uint32_t level
     for (uint32_t e = threadIdx.x; e < hsize * 2; e += 256) { float v = tab[e]; if (v != 0.f) atomicAdd(gt + e, v); }
 }
 
-// dst[i] += sum over the 8 XCD-private copies, which are cleared for the next use (one pass: 8 reads + 8 zero writes + 1 RMW)
-__global__ __launch_bounds__(256) void k_xcd_reduce_clear(size_t n4, float4* __restrict__ scratch, size_t stride4, float4* __restrict__ dst) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        float4 a = dst[i];
-#pragma unroll
-        for (int x = 0; x < 8; x++) {
-            float4 v = scratch[x * stride4 + i];
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-            scratch[x * stride4 + i] = z;
-        }
-        dst[i] = a;
-    }
-}
-
 static int check(uint32_t B, uint32_t D, uint32_t C, uint32_t L) {
     if (D != 3 || C != 2 || L == 0 || L > 32) return DWG_E_ARG;  // the avatar's encoder: D=3, C=2, L=16
     if ((uint64_t)B * L > 0xffffff00ull) return DWG_E_ARG;
@@ -253,8 +159,8 @@ static int check(uint32_t B, uint32_t D, uint32_t C, uint32_t L) {
 // BINNED by 4096-entry slab of the table (count per workgroup in LDS -> scan -> scatter 16-byte records into slab order), then one
 // workgroup per slab accumulates its records in a 32 KiB LDS image with LDS atomics and writes the slab out with plain 16-byte
 // stores.  Only slabs with more than GS_MAXREC records (the densest few levels) are split over several workgroups that add their
-// images with global atomics.  The coarse levels keep their LDS-privatised kernel.  Needs a zero-filled gradient table (the
-// untouched entries of a plain-stored slab are written as zeros again) and B * L * 8 * 16 bytes of record workspace.
+// images with global atomics; the dense coarse levels are such slabs.  Needs a zero-filled gradient table (the untouched entries of
+// a plain-stored slab are written as zeros again) unless it accumulates, and B * L * 8 * 16 bytes of record workspace.
 // ---------------------------------------------------------------------------------------------------------------------
 #define GS_SLAB 4096u          // table entries (float2) per slab: 32 KiB of LDS (four accumulate workgroups per CU)
 #define GS_NWG 256u            // workgroups of the count / scatter passes (each owns a contiguous range of (point, level) chunks)
@@ -507,6 +413,32 @@ __global__ __launch_bounds__(256) void k_gs_finalize(uint32_t first_entry, uint3
     for (uint32_t e = threadIdx.x; e < ne * 2u; e += 256) dst[e] = gs_from_fixed((long long)img[e], sx) + (accumulate ? dst[e] : 0.f);
 }
 
+// The slab path's workspace: sub-buffer offsets (each 256-byte aligned) and the total, in one place for the size query and the launcher.
+struct GsWorkspace {
+    size_t max_units, max_multi;        // launch bounds of k_gs_accumulate / k_gs_finalize
+    size_t records, counts, slab_start, slab_total, units, n_units, wgmax, sexp, multi_list, n_multi, gimg, bytes;
+    GsWorkspace(uint32_t B, uint32_t L, uint32_t total_entries) {
+        const size_t nslab = (total_entries + GS_SLAB - 1u) / GS_SLAB;
+        const size_t recs = (size_t)B * L * 8;
+        max_units = nslab + recs / GS_MAXREC + 2;
+        max_multi = nslab < recs / GS_MAXREC + 1 ? nslab : recs / GS_MAXREC + 1;      // slabs with more than GS_MAXREC records
+        size_t at = 0;
+        auto take = [&at](size_t bytes) { const size_t o = at; at += dwg_align_up(bytes, 256); return o; };
+        records = take(recs * sizeof(uint4));
+        counts = take((size_t)GS_NWG * nslab * 4);
+        slab_start = take((nslab + 1) * 4);
+        slab_total = take((nslab + 1) * 4);
+        units = take(max_units * sizeof(GsUnit));
+        n_units = take(256);
+        wgmax = take((size_t)GS_NWG * 4);
+        sexp = take(nslab * 4);
+        multi_list = take(max_multi * 4);
+        n_multi = take(256);
+        gimg = take(max_multi * GS_SLAB * 2 * 8);
+        bytes = at;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -527,10 +459,10 @@ int dwg_grid_encode_forward(const float* inputs, const float* embeddings, const 
     return DWG_OK;
 }
 
-static int grid_backward(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
-                         float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                         const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
-                         uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, float* xcd_scratch, dwg_stream_t stream) {
+int dwg_grid_encode_backward(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
+                             float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                             const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
+                             uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, dwg_stream_t stream) {
     int rc = check(B, D, C, L);
     if (rc) return rc;
     if (B == 0) return DWG_OK;
@@ -559,107 +491,21 @@ static int grid_backward(const float* grad, const float* inputs, const float* em
             first_table_level++;
         }
     }
-    if (xcd_scratch && grad_embeddings && host_offsets && first_table_level < L) {
-        const size_t total = (size_t)(uint32_t)host_offsets[L] * 2;                    // floats per table copy (multiple of 16)
-        DWG_LAUNCH("grid_bwd", (k_grid_bwd<true>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, grad, inputs, offsets,
-                   xcd_scratch, dy_dx, grad_inputs, first_table_level, total);
-        const size_t lo = (size_t)(uint32_t)host_offsets[first_table_level] * 2;       // coarse levels went through LDS straight to dst
-        const size_t n4 = (total - lo) / 4;
-        size_t blocks = (n4 + 255) / 256; if (blocks > 4096) blocks = 4096;
-        DWG_LAUNCH("grid_bwd_xcd_reduce", k_xcd_reduce_clear, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n4,
-                   reinterpret_cast<float4*>(xcd_scratch + lo), total / 4, reinterpret_cast<float4*>(grad_embeddings + lo));
-    } else {
-        DWG_LAUNCH("grid_bwd", (k_grid_bwd<false>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, grad, inputs, offsets,
-                   grad_embeddings, dy_dx, grad_inputs, first_table_level, (size_t)0);
-    }
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
-}
-
-int dwg_grid_encode_backward_owner(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
-                                   float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                                   const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
-                                   uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, uint32_t* xcd_counters,
-                                   dwg_stream_t stream) {
-    int rc = check(B, D, C, L);
-    if (rc) return rc;
-    if (B == 0) return DWG_OK;
-    (void)embeddings;
-    if (!grad || !inputs || !offsets || !grad_embeddings || !host_offsets || !xcd_counters) return DWG_E_ARG;
-    if (((uintptr_t)grad_embeddings % 128) != 0) return DWG_E_ARG;          // line ownership assumes a line-aligned table
-    if ((dy_dx == nullptr) != (grad_inputs == nullptr)) return DWG_E_ARG;
-    GridP p{B, L, S, H, gridtype, align_corners, interp, grad_layout};
-    if (grad_inputs && L != 16) {
-        if (hipMemsetAsync(grad_inputs, 0, (size_t)B * 3 * sizeof(float), (hipStream_t)stream) != hipSuccess) return DWG_E_LAUNCH;
-    }
-    if (hipMemsetAsync(xcd_counters, 0, 16 * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) return DWG_E_LAUNCH;
-    uint32_t first_table_level = 0;
-    hipStream_t main_stream = (hipStream_t)stream, side = nullptr;
-    hipEvent_t ev_join = nullptr;
-    if (B >= 16384) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grid_bwd_coarse), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            attr_set = true;
-        }
-        // The LDS-privatised coarse levels are a handful of fat workgroups (13 - 49 of them, up to 97 KiB of LDS each) that touch
-        // their own part of the table gradient: they run on a library-owned side stream NEXT TO the fine-level kernel instead of
-        // in front of it (0.27 ms of a 1.9 ms backward otherwise spent on a mostly idle chip).  DWG_GRID_SERIAL_COARSE=1: one stream.
-        static const bool serial = getenv("DWG_GRID_SERIAL_COARSE") != nullptr;
-        static hipStream_t side_streams[16] = {nullptr};
-        static hipEvent_t ev_forks[16] = {nullptr}, ev_joins[16] = {nullptr};
-        int dev = 0;
-        hipEvent_t ev_fork = nullptr;
-        if (!serial && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
-            if (!side_streams[dev]) {
-                if (hipStreamCreateWithFlags(&side_streams[dev], hipStreamNonBlocking) != hipSuccess ||
-                    hipEventCreateWithFlags(&ev_forks[dev], hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&ev_joins[dev], hipEventDisableTiming) != hipSuccess) return DWG_E_LAUNCH;
-            }
-            side = side_streams[dev]; ev_fork = ev_forks[dev]; ev_join = ev_joins[dev];
-        }
-        bool forked = false;
-        while (first_table_level < L) {
-            uint32_t hs = (uint32_t)(host_offsets[first_table_level + 1] - host_offsets[first_table_level]);
-            if ((size_t)hs * 8 > 152 * 1024 || (uint64_t)B * 8 < (uint64_t)hs * 16) break;
-            uint32_t ppb = hs * 8 > 64 * 1024 ? 8192 : 2048;
-            if (side && !forked) {          // everything queued on the caller's stream so far (zeroed gradients, inputs) happens first
-                if (hipEventRecord(ev_fork, main_stream) != hipSuccess || hipStreamWaitEvent(side, ev_fork, 0) != hipSuccess) return DWG_E_LAUNCH;
-                forked = true;
-            }
-            DWG_LAUNCH("grid_bwd_coarse", k_grid_bwd_coarse, dim3((B + ppb - 1) / ppb), dim3(256), (size_t)hs * 8, side ? side : main_stream, p,
-                       first_table_level, ppb, grad, inputs, offsets, grad_embeddings);
-            first_table_level++;
-        }
-        if (!forked) side = nullptr;
-        else if (hipEventRecord(ev_join, side) != hipSuccess) return DWG_E_LAUNCH;
-    }
-    const uint32_t nchunks = (uint32_t)(((uint64_t)B * L + 255) / 256);
-    uint32_t blocks = nchunks * 8u; if (blocks > 2048u) blocks = 2048u;       // persistent: 8 per CU, chunks pulled per physical XCD
-    if (blocks < 64u) blocks = 64u;                                          // enough that every XCD receives workgroups
-    DWG_LAUNCH("grid_bwd", k_grid_bwd_owner, dim3(blocks), dim3(256), 0, main_stream, p, nchunks, grad, inputs, offsets,
-               grad_embeddings, dy_dx, grad_inputs, first_table_level, xcd_counters);
-    if (side && hipStreamWaitEvent(main_stream, ev_join, 0) != hipSuccess) return DWG_E_LAUNCH;       // join: later work sees both
+    DWG_LAUNCH("grid_bwd", k_grid_bwd, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, grad, inputs, offsets,
+               grad_embeddings, dy_dx, grad_inputs, first_table_level);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }
 
 size_t dwg_grid_backward_slabs_workspace_bytes(uint32_t B, uint32_t L, uint32_t total_entries) {
-    const size_t nslab = (total_entries + GS_SLAB - 1u) / GS_SLAB;
-    const size_t recs = (size_t)B * L * 8;
-    const size_t max_units = nslab + recs / GS_MAXREC + 2;
-    const size_t max_multi = (nslab < recs / GS_MAXREC + 1 ? nslab : recs / GS_MAXREC + 1);      // slabs with more than GS_MAXREC records
-    return dwg_align_up(recs * sizeof(uint4), 256) + dwg_align_up((size_t)GS_NWG * nslab * 4, 256) + 2 * dwg_align_up((nslab + 1) * 4, 256) +
-           dwg_align_up(max_units * sizeof(GsUnit), 256) + 256 +
-           dwg_align_up((size_t)GS_NWG * 4, 256) + dwg_align_up(nslab * 4, 256) + dwg_align_up(max_multi * 4, 256) + 256 +
-           dwg_align_up(max_multi * GS_SLAB * 2 * 8, 256);
+    return GsWorkspace(B, L, total_entries).bytes;
 }
 
-static int grid_backward_slabs(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
-                               float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                               const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
-                               uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, void* workspace,
-                               size_t workspace_bytes, dwg_stream_t stream, int accumulate) {
+int dwg_grid_encode_backward_slabs(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
+                                   float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                   const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
+                                   uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, void* workspace,
+                                   size_t workspace_bytes, int accumulate, dwg_stream_t stream) {
     int rc = check(B, D, C, L);
     if (rc) return rc;
     if (B == 0) return DWG_OK;
@@ -667,57 +513,34 @@ static int grid_backward_slabs(const float* grad, const float* inputs, const flo
     if (!grad || !inputs || !offsets || !host_offsets || !grad_embeddings || !workspace) return DWG_E_ARG;
     if ((dy_dx == nullptr) != (grad_inputs == nullptr)) return DWG_E_ARG;
     const uint32_t total_entries = (uint32_t)host_offsets[L];
-    if (workspace_bytes < dwg_grid_backward_slabs_workspace_bytes(B, L, total_entries)) return DWG_E_CAPACITY;
+    const GsWorkspace ws(B, L, total_entries);
+    if (workspace_bytes < ws.bytes) return DWG_E_CAPACITY;
     hipStream_t st = (hipStream_t)stream;
     GridP p{B, L, S, H, gridtype, align_corners, interp, grad_layout};
     if (grad_inputs && L != 16) {
         if (hipMemsetAsync(grad_inputs, 0, (size_t)B * 3 * sizeof(float), st) != hipSuccess) return DWG_E_LAUNCH;
     }
-    // ALL levels go through the slabs by default: the dense coarse levels become a few oversubscribed slabs (split into units that add
-    // their LDS images with atomics) and cost nothing extra in the accumulate pass, where their separate LDS-privatised kernel was two
-    // poorly parallel launches of 0.13 ms each (c2 404 -> 464 steps/s).  DWG_GRID_SLAB_COARSE=1 restores that kernel for them.
-    uint32_t first_table_level = 0;
-    static const bool coarse = getenv("DWG_GRID_SLAB_COARSE") != nullptr;
-    if (B >= 16384 && coarse) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grid_bwd_coarse), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            attr_set = true;
-        }
-        while (first_table_level < L) {
-            uint32_t hs = (uint32_t)(host_offsets[first_table_level + 1] - host_offsets[first_table_level]);
-            if ((size_t)hs * 8 > 152 * 1024 || (uint64_t)B * 8 < (uint64_t)hs * 16) break;
-            uint32_t ppb = hs * 8 > 64 * 1024 ? 8192 : 2048;
-            DWG_LAUNCH("grid_bwd_coarse", k_grid_bwd_coarse, dim3((B + ppb - 1) / ppb), dim3(256), (size_t)hs * 8, st, p, first_table_level, ppb,
-                       grad, inputs, offsets, grad_embeddings);
-            first_table_level++;
-        }
-    }
+    // ALL levels go through the slabs: the dense coarse levels become a few oversubscribed slabs (split into units that add their LDS
+    // images with atomics) and cost nothing extra in the accumulate pass, where their separate LDS-privatised kernel was two poorly
+    // parallel launches of 0.13 ms each (c2 404 -> 464 steps/s).  So the kernels' first level / first entry are always 0.
+    const uint32_t first_table_level = 0, first_entry = 0;
     const uint32_t nchunks = (uint32_t)(((uint64_t)B * L + 255) / 256);
-    if (first_table_level >= L) {           // nothing left for the table pass; the input gradient still needs its walk
-        first_table_level = L;
-    }
-    const uint32_t first_entry = (uint32_t)host_offsets[first_table_level < L ? first_table_level : L];
-    const uint32_t nslab = (total_entries - first_entry + GS_SLAB - 1u) / GS_SLAB > 0 ? (total_entries - first_entry + GS_SLAB - 1u) / GS_SLAB : 1u;
-    const size_t recs = (size_t)B * L * 8;
-    const size_t max_units = (size_t)nslab + recs / GS_MAXREC + 2;
+    const uint32_t nslab = total_entries > 0 ? (total_entries + GS_SLAB - 1u) / GS_SLAB : 1u;
     // limits of this path (callers fall back to dwg_grid_encode_backward): the binning kernels keep one u32 counter per slab in LDS
     // (64 KiB without an opt-in: tables up to 67 M entries) and record positions are u32
-    if ((size_t)nslab * 4 > 64 * 1024 || recs > 0xffffffffull) return DWG_E_CAPACITY;
+    if ((size_t)nslab * 4 > 64 * 1024 || (size_t)B * L * 8 > 0xffffffffull) return DWG_E_CAPACITY;
     unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-    uint4* records = reinterpret_cast<uint4*>(w); w += dwg_align_up(recs * sizeof(uint4), 256);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(w); w += dwg_align_up((size_t)GS_NWG * ((total_entries + GS_SLAB - 1u) / GS_SLAB) * 4, 256);
-    uint32_t* slab_start = reinterpret_cast<uint32_t*>(w); w += dwg_align_up(((size_t)(total_entries + GS_SLAB - 1u) / GS_SLAB + 1) * 4, 256);
-    uint32_t* slab_total = reinterpret_cast<uint32_t*>(w); w += dwg_align_up(((size_t)(total_entries + GS_SLAB - 1u) / GS_SLAB + 1) * 4, 256);
-    GsUnit* units = reinterpret_cast<GsUnit*>(w); w += dwg_align_up(((size_t)(total_entries + GS_SLAB - 1u) / GS_SLAB + recs / GS_MAXREC + 2) * sizeof(GsUnit), 256);
-    uint32_t* n_units = reinterpret_cast<uint32_t*>(w); w += 256;
-    const size_t nslab_all = ((size_t)total_entries + GS_SLAB - 1u) / GS_SLAB;
-    const size_t max_multi = (nslab_all < recs / GS_MAXREC + 1 ? nslab_all : recs / GS_MAXREC + 1);
-    float* wgmax = reinterpret_cast<float*>(w); w += dwg_align_up((size_t)GS_NWG * 4, 256);
-    int32_t* sexp = reinterpret_cast<int32_t*>(w); w += dwg_align_up(nslab_all * 4, 256);
-    uint32_t* multi_list = reinterpret_cast<uint32_t*>(w); w += dwg_align_up(max_multi * 4, 256);
-    uint32_t* n_multi = reinterpret_cast<uint32_t*>(w); w += 256;
-    unsigned long long* gimg = reinterpret_cast<unsigned long long*>(w);
+    uint4* records = reinterpret_cast<uint4*>(w + ws.records);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(w + ws.counts);
+    uint32_t* slab_start = reinterpret_cast<uint32_t*>(w + ws.slab_start);
+    uint32_t* slab_total = reinterpret_cast<uint32_t*>(w + ws.slab_total);
+    GsUnit* units = reinterpret_cast<GsUnit*>(w + ws.units);
+    uint32_t* n_units = reinterpret_cast<uint32_t*>(w + ws.n_units);
+    float* wgmax = reinterpret_cast<float*>(w + ws.wgmax);
+    int32_t* sexp = reinterpret_cast<int32_t*>(w + ws.sexp);
+    uint32_t* multi_list = reinterpret_cast<uint32_t*>(w + ws.multi_list);
+    uint32_t* n_multi = reinterpret_cast<uint32_t*>(w + ws.n_multi);
+    unsigned long long* gimg = reinterpret_cast<unsigned long long*>(w + ws.gimg);
     static bool attr2 = false;
     if (!attr2) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gs_accumulate), hipFuncAttributeMaxDynamicSharedMemorySize, GS_SLAB * 16);
@@ -730,49 +553,12 @@ static int grid_backward_slabs(const float* grad, const float* inputs, const flo
                (const float*)wgmax, sexp, multi_list, n_multi);
     DWG_LAUNCH("grid_bwd_scatter", (k_gs_bin<true>), dim3(GS_NWG), dim3(256), (size_t)nslab * 4, st, p, nchunks, nslab, first_entry, grad, inputs,
                offsets, first_table_level, counts, (const uint32_t*)slab_start, records, dy_dx, grad_inputs, wgmax, (const uint32_t*)n_multi, gimg);
-    DWG_LAUNCH("grid_bwd", k_gs_accumulate, dim3((unsigned)max_units), dim3(256), (size_t)GS_SLAB * 16, st, first_entry, total_entries,
+    DWG_LAUNCH("grid_bwd", k_gs_accumulate, dim3((unsigned)ws.max_units), dim3(256), (size_t)GS_SLAB * 16, st, first_entry, total_entries,
                (const GsUnit*)units, (const uint32_t*)n_units, (const uint4*)records, grad_embeddings, accumulate, (const int32_t*)sexp, gimg);
-    DWG_LAUNCH("grid_bwd", k_gs_finalize, dim3((unsigned)max_multi), dim3(256), 0, st, first_entry, total_entries, (const uint32_t*)multi_list,
+    DWG_LAUNCH("grid_bwd", k_gs_finalize, dim3((unsigned)ws.max_multi), dim3(256), 0, st, first_entry, total_entries, (const uint32_t*)multi_list,
                (const uint32_t*)n_multi, (const int32_t*)sexp, (const unsigned long long*)gimg, grad_embeddings, accumulate);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
-}
-
-int dwg_grid_encode_backward_slabs(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
-                                   float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                                   const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
-                                   uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, void* workspace,
-                                   size_t workspace_bytes, dwg_stream_t stream) {
-    return grid_backward_slabs(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners,
-                               interp, grad_layout, host_offsets, workspace, workspace_bytes, stream, 0);
-}
-
-int dwg_grid_encode_backward_slabs_accumulate(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
-                                              float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                                              const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
-                                              uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, void* workspace,
-                                              size_t workspace_bytes, dwg_stream_t stream) {
-    return grid_backward_slabs(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners,
-                               interp, grad_layout, host_offsets, workspace, workspace_bytes, stream, 1);
-}
-
-int dwg_grid_encode_backward(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
-                             float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                             const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
-                             uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, dwg_stream_t stream) {
-    return grid_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
-                         align_corners, interp, grad_layout, host_offsets, nullptr, stream);
-}
-
-int dwg_grid_encode_backward_xcd(const float* grad, const float* inputs, const float* embeddings, const int32_t* offsets,
-                                 float* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                                 const float* dy_dx, float* grad_inputs, uint32_t gridtype, uint32_t align_corners,
-                                 uint32_t interp, uint32_t grad_layout, const int32_t* host_offsets, float* xcd_scratch,
-                                 dwg_stream_t stream) {
-    if (!xcd_scratch || !host_offsets || ((uintptr_t)xcd_scratch % 16) || (grad_embeddings && ((uintptr_t)grad_embeddings % 16)))
-        return DWG_E_ARG;
-    return grid_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
-                         align_corners, interp, grad_layout, host_offsets, xcd_scratch, stream);
 }
 
 }  // extern "C"

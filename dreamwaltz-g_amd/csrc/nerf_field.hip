@@ -511,10 +511,10 @@ int dwg_nerf_field_backward(const dwg_nerf_field_desc* desc, const float* x, uin
         }
         DWG_RETURN_IF_LAUNCH_FAILED();
         if (want_t) {
-            rc = dwg_grid_encode_backward_slabs_accumulate(d_enc, xn, desc->embeddings, desc->offsets, grads->embeddings, (uint32_t)n, 3u, 2u,
-                                                           desc->num_levels, desc->log2_per_level_scale, desc->base_resolution, nullptr, nullptr,
-                                                           desc->gridtype, desc->align_corners ? 1u : 0u, desc->interp, 1u, desc->host_offsets,
-                                                           slab_ws, slab_bytes, stream);
+            rc = dwg_grid_encode_backward_slabs(d_enc, xn, desc->embeddings, desc->offsets, grads->embeddings, (uint32_t)n, 3u, 2u,
+                                                desc->num_levels, desc->log2_per_level_scale, desc->base_resolution, nullptr, nullptr,
+                                                desc->gridtype, desc->align_corners ? 1u : 0u, desc->interp, 1u, desc->host_offsets,
+                                                slab_ws, slab_bytes, /*accumulate*/ 1, stream);
             if (rc) return rc;
         }
     }

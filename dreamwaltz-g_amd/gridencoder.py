@@ -61,71 +61,6 @@ def _host_offsets_of(offsets):
     return arr
 
 
-_xcd_scratch = {}
-_xcd_checked = {}
-
-
-def xcd_scratch_for(embeddings):
-    """8 XCD-private copies of the table gradient (zero between calls), one allocation per (device, table size, stream): two
-    backward passes in flight on different streams never share a scratch."""
-    key = (embeddings.device, embeddings.numel(), torch.cuda.current_stream(embeddings.device).cuda_stream)
-    if key not in _xcd_scratch:
-        _xcd_scratch[key] = torch.zeros(8, embeddings.numel(), device=embeddings.device, dtype=torch.float32)
-    return _xcd_scratch[key]
-
-
-def xcd_path_ok(device) -> bool:
-    """The XCD-private accumulation relies on a gfx950 property outside the HIP memory model: workgroup-scope float atomics to
-    addresses shared by the workgroups of one XCD are performed in that XCD's L2, hence atomic among them (MI355X_MICROARCH:
-    per-XCD L2, block b -> XCD b % 8).  Guarded twice: the device must be gfx950, and a one-off self-test per device compares
-    the path against the agent-scope (memory-side) atomics on a random problem; a mismatch disables it for the process."""
-    key = str(device)
-    if key in _xcd_checked:
-        return _xcd_checked[key]
-    import os
-    ok = os.environ.get("DWG_GRID_NO_XCD") != "1" and "gfx950" in torch.cuda.get_device_properties(device).gcnArchName
-    if ok:
-        _xcd_checked[key] = False               # no recursion while the self-test runs
-        g = torch.Generator().manual_seed(0)
-        enc_off = np.array([0, 4920, 20552], dtype=np.int32)
-        B = 20000
-        x = torch.rand(B, 3, generator=g).to(device)
-        table = torch.zeros(int(enc_off[-1]), 2, device=device)
-        grad = torch.randn(B, 4, generator=g).to(device)
-        off = torch.from_numpy(enc_off).to(device)
-        ho = _host_array(tuple(int(v) for v in enc_off))
-        res = []
-        for mode in ("device", "copies", "owner"):
-            ge = torch.zeros_like(table)
-            scratch = torch.zeros(8, table.numel(), device=device) if mode == "copies" else None
-            cnt = torch.zeros(16, dtype=torch.int32, device=device) if mode == "owner" else None
-            grid_encode_backward(grad, x, table, off, ge, B, 3, 2, 2, 1.0, 16, None, None, 1, False, 1, grad_layout=1,
-                                 xcd_scratch=scratch, host_offsets=ho, xcd_counters=cnt)
-            res.append(ge)
-            if mode == "copies" and float(scratch.abs().max()) != 0.0:
-                ok = False
-            if mode == "owner" and not bool((cnt[8:] == 1).all()):
-                ok = False                       # some XCD received no workgroup: its table lines were never written
-        err = max(float((res[0] - r).abs().max() / res[0].abs().max().clamp_min(1e-20)) for r in res[1:])
-        ok = ok and err < 1e-4
-        if not ok:
-            import warnings
-            warnings.warn("dreamwaltz_g_amd grid encoder: XCD-private gradient accumulation failed its self-test (rel. err %.2e); "
-                          "using device-scope atomics" % err)
-    _xcd_checked[key] = ok
-    return ok
-
-
-_xcd_counters = {}
-
-
-def xcd_counters_for(device):
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    if key not in _xcd_counters:
-        _xcd_counters[key] = torch.zeros(16, dtype=torch.int32, device=device)
-    return _xcd_counters[key]
-
-
 _INPLACE_OK = [True]
 
 
@@ -143,6 +78,11 @@ class table_grad_inplace:
 
     def __exit__(self, *exc):
         _INPLACE_OK[0] = self.prev
+
+# The autograd backward takes the slab-binned path from this many points (round 5; 16384 before): it is the DETERMINISTIC one (64-bit
+# fixed-point sums), and a training step's table gradient should reproduce bit for bit at every avatar size; below that the handful of
+# float atomics of the device-scope path cost less than the slab path's five dependent launches
+SLAB_MIN_POINTS = 2048
 
 _SLAB_WS = {}     # (device, stream) -> byte workspace of the slab-binned backward (grown on demand; backwards on one stream are ordered,
                   # a workspace replaced by a bigger one is only released by the caching allocator in that stream's order)
@@ -165,32 +105,18 @@ def slab_workspace_for(device, B, L, total_entries):
 
 
 def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs,
-                         gridtype, align_corners, interp, grad_layout=0, xcd_scratch=None, host_offsets=None, xcd_counters=None,
-                         slab_workspace=None, accumulate=False):
+                         gridtype, align_corners, interp, grad_layout=0, host_offsets=None, slab_workspace=None, accumulate=False):
+    """slab_workspace given: the slab-binned table gradient (overwriting a zeroed grad_embeddings, or adding into it with `accumulate`);
+    else the float-atomics path."""
     _need_cuda(inputs)
     p = _lib.ptr
     ho = host_offsets if host_offsets is not None else _host_offsets_of(offsets)
     if slab_workspace is not None:
-        fn = _lib.lib().dwg_grid_encode_backward_slabs_accumulate if accumulate else _lib.lib().dwg_grid_encode_backward_slabs
-        _lib.check(fn(p(grad), p(inputs), p(embeddings), p(offsets), p(grad_embeddings), B, D,
+        _lib.check(_lib.lib().dwg_grid_encode_backward_slabs(p(grad), p(inputs), p(embeddings), p(offsets), p(grad_embeddings), B, D,
                                                              C, L, ctypes.c_float(S), H, p(dy_dx), p(grad_inputs), gridtype,
                                                              int(bool(align_corners)), interp, grad_layout,
                                                              ctypes.cast(ho, ctypes.c_void_p), p(slab_workspace), slab_workspace.numel(),
-                                                             _st(inputs)), "dwg_grid_encode_backward_slabs")
-        return
-    if xcd_counters is not None:
-        _lib.check(_lib.lib().dwg_grid_encode_backward_owner(p(grad), p(inputs), p(embeddings), p(offsets), p(grad_embeddings), B, D,
-                                                             C, L, ctypes.c_float(S), H, p(dy_dx), p(grad_inputs), gridtype,
-                                                             int(bool(align_corners)), interp, grad_layout,
-                                                             ctypes.cast(ho, ctypes.c_void_p), p(xcd_counters), _st(inputs)),
-                   "dwg_grid_encode_backward_owner")
-        return
-    if xcd_scratch is not None:
-        _lib.check(_lib.lib().dwg_grid_encode_backward_xcd(p(grad), p(inputs), p(embeddings), p(offsets), p(grad_embeddings), B, D,
-                                                           C, L, ctypes.c_float(S), H, p(dy_dx), p(grad_inputs), gridtype,
-                                                           int(bool(align_corners)), interp, grad_layout,
-                                                           ctypes.cast(ho, ctypes.c_void_p), p(xcd_scratch), _st(inputs)),
-                   "dwg_grid_encode_backward_xcd")
+                                                             int(bool(accumulate)), _st(inputs)), "dwg_grid_encode_backward_slabs")
         return
     _lib.check(_lib.lib().dwg_grid_encode_backward(p(grad), p(inputs), p(embeddings), p(offsets), p(grad_embeddings), B, D,
                                                    C, L, ctypes.c_float(S), H, p(dy_dx), p(grad_inputs), gridtype,
@@ -229,37 +155,20 @@ class _grid_encode(Function):
         B, D, C, L, S, H, gridtype, interpolation = ctx.dims
         grad = grad.contiguous().float()
         grad_inputs = torch.empty_like(inputs) if dy_dx is not None else None
-        # big batches: XCD-private accumulation of the table gradient (8 copies + one reduce pass beat memory-side atomics)
-        import os
-        # the slab-binned path from 2048 points (round 5; 16384 before): it is the DETERMINISTIC one (64-bit fixed-point sums), and a training
-        # step's table gradient should reproduce bit for bit at every avatar size; below that the handful of float atomics of the
-        # device-scope path cost less than the slab path's five dependent launches
-        mode = os.environ.get("DWG_GRID_XCD_MODE", "slabs") if B >= int(os.environ.get("DWG_GRID_SLAB_MIN_POINTS", "2048")) else "device"
-        if mode in ("owner", "copies") and not xcd_path_ok(inputs.device):
-            mode = "device"
-        if mode == "slabs" and not slab_path_ok(B, L, int(embeddings.shape[0])):
-            mode = "device"
-        scratch = xcd_scratch_for(embeddings) if mode == "copies" else None
-        slab_ws = slab_workspace_for(inputs.device, B, L, int(embeddings.shape[0])) if mode == "slabs" else None
+        slabs = B >= SLAB_MIN_POINTS and slab_path_ok(B, L, int(embeddings.shape[0]))
+        slab_ws = slab_workspace_for(inputs.device, B, L, int(embeddings.shape[0])) if slabs else None
         # The table is a leaf Parameter whose .grad is its slice of the flat gradient buffer (optim.FlatBuffers marks such parameters:
         # `_dwg_flat`): the slab pass ADDS straight into it and autograd is handed None -- instead of a zeroed 50 MB temporary that autograd
         # then adds to .grad (a 50 MB fill and a 150 MB add per backward).  Opt-in PER PARAMETER: a frozen table, a table whose .grad was
         # rebound, a table of another optimizer or one autograd did not ask a gradient for gets the gradient returned the ordinary way
         # (FlatBuffers.owns_grad).  `torch.autograd.grad(out, [table])` on a flat-buffer table cannot be told from `.backward()` here: such
-        # a caller wraps the forward in `table_grad_inplace(False)`.  DWG_GRID_GRAD_INPLACE=0: never in place.
+        # a caller wraps the forward in `table_grad_inplace(False)`.
         flat = getattr(embeddings, "_dwg_flat", None)
-        in_place = (mode == "slabs" and flat is not None and ctx.needs_input_grad[1] and flat.owns_grad(embeddings)
-                    and ctx.inplace_ok and os.environ.get("DWG_GRID_GRAD_INPLACE", "1") != "0")
+        in_place = slabs and flat is not None and ctx.needs_input_grad[1] and flat.owns_grad(embeddings) and ctx.inplace_ok
         grad_embeddings = embeddings.grad if in_place else torch.zeros_like(embeddings)
-        counters = xcd_counters_for(inputs.device) if (mode == "owner" and grad_embeddings.data_ptr() % 128 == 0) else None
-        try:
-            grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs,
-                                 gridtype, ctx.align_corners, interpolation, grad_layout=1, xcd_scratch=scratch,
-                                 host_offsets=ctx.host_offsets, xcd_counters=counters, slab_workspace=slab_ws, accumulate=in_place)
-        except Exception:
-            if scratch is not None:
-                scratch.zero_()        # a failed launch must not leave partial sums for the next call
-            raise
+        grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs,
+                             gridtype, ctx.align_corners, interpolation, grad_layout=1, host_offsets=ctx.host_offsets,
+                             slab_workspace=slab_ws, accumulate=in_place)
         if in_place:
             flat.touch(embeddings)      # autograd never sees this gradient: record the parameter's participation for the optimizer
         return grad_inputs, (None if in_place else grad_embeddings), None, None, None, None, None, None, None, None

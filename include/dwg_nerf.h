@@ -68,7 +68,7 @@ size_t dwg_nerf_field_backward_workspace_bytes(const dwg_nerf_field_desc* desc, 
 
 /* dsigma [M] fp32, dalbedo [M, out_dim - 1] in the forward's albedo dtype.  Points are processed in chunks: per chunk one launch
  * recomputes the field, adds its tiles' weight gradients into per-workgroup partials and writes d_enc [chunk, 2L] fp32, which the
- * slab-binned table gradient (dwg_grid_encode_backward_slabs_accumulate) adds into grads->embeddings.  One more launch sums the
+ * slab-binned table gradient (dwg_grid_encode_backward_slabs, accumulate = 1) adds into grads->embeddings.  One more launch sums the
  * partials in a fixed order.  workspace: dwg_nerf_field_backward_workspace_bytes(desc, M) bytes, 256-byte aligned. */
 int dwg_nerf_field_backward(const dwg_nerf_field_desc* desc, const float* x, uint64_t M, const float* dsigma, const void* dalbedo,
                             const dwg_nerf_field_grads* grads, void* workspace, size_t workspace_bytes, dwg_stream_t stream);
