@@ -372,13 +372,13 @@ int dwg_lbs_vertex_transform_backward_shape_ws(int32_t Vp, int32_t J, int32_t n_
                                                const float* joint_shape_dirs, float* g_A_transl_scratch, float* g_shape, float* workspace,
                                                dwg_stream_t stream_) {
     if (Vp < 0 || J <= 0 || J > MAXJ || n_shape <= 0 || n_shape > 64 * MAXS_PER_LANE) return DWG_E_ARG;
-    if (!A || !lbs_weights_sub || !shapedirs_sub || !g_out || !pose || !parents || !joint_shape_dirs || !g_A_transl_scratch || !g_shape)
-        return DWG_E_ARG;
+    if (!A || !pose || !parents || !joint_shape_dirs || !g_A_transl_scratch || !g_shape) return DWG_E_ARG;
     hipStream_t stream = (hipStream_t)stream_;
-    if (Vp == 0) {
+    if (Vp == 0) {          // (the per-vertex arrays of an empty subset are empty: their addresses may be NULL)
         if (hipMemsetAsync(g_shape, 0, sizeof(float) * (size_t)n_shape, stream) != hipSuccess) return DWG_E_LAUNCH;
         return DWG_OK;
     }
+    if (!lbs_weights_sub || !shapedirs_sub || !g_out) return DWG_E_ARG;
     if (!workspace) return DWG_E_ARG;          // up to 64 workgroups, one row of partial sums each
     int blocks = dwg_cdiv(Vp, 4); if (blocks > 64) blocks = 64;
     DWG_LAUNCH("lbs_vertex_transform_bwd", k_vertex_transform_bwd, dim3(blocks), dim3(256), 0, stream, Vp, J, n_shape, A, lbs_weights_sub,

@@ -287,7 +287,15 @@ int dwg_meshbind_backward_verts_gather(int32_t Vp, int32_t Fp, int32_t n_per_tri
                                        const float* g_scales, const float* g_quats, float* g_bary, float* g_scale_params, float* corner_rows,
                                        float* g_verts_cnl, float* g_verts_obs, float* g_vnormals_obs, dwg_stream_t stream_) {
     if (Vp < 0 || Fp < 0 || n_per_tri <= 0) return DWG_E_ARG;
-    if (Fp == 0 || Vp == 0) return DWG_OK;
+    if (Vp == 0) return DWG_OK;
+    if (Fp == 0) {
+        // no face, no Gaussian: the vertex gradients are zero, and they are documented as OVERWRITTEN -- the caller hands over uninitialised
+        // buffers (meshbind.py) and dwg_mesh_vertex_normals_backward adds nothing for Fp == 0 either.  (Fp > 0 launches nothing extra.)
+        float* outs[3] = {g_verts_cnl, g_verts_obs, g_vnormals_obs};
+        for (float* o : outs)
+            if (o && hipMemsetAsync(o, 0, sizeof(float) * 3 * (size_t)Vp, (hipStream_t)stream_) != hipSuccess) return DWG_E_LAUNCH;
+        return DWG_OK;
+    }
     if (!bary || !scale_params || !verts_obs || !vnormals_obs || !triangles || !g_bary || !g_scale_params) return DWG_E_ARG;
     if (!vf_offsets || !vf_faces || !corner_rows || !g_verts_obs || !g_vnormals_obs) return DWG_E_ARG;
     if (g_pos_cnl && !verts_cnl) return DWG_E_ARG;

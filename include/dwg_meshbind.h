@@ -52,7 +52,8 @@ int dwg_meshbind_backward_verts(int32_t Fp, int32_t n_per_tri, const float* bary
 /* dwg_meshbind_backward_verts WITHOUT float atomics (round 6; `learn_hand_betas` is on in sub-stage 2.1 of the shipped recipe,
  * scripts/train_w_expr.sh:66): the per-Gaussian kernel writes one row {g position, g normal, g canonical position} per (Gaussian, corner)
  * into `corner_rows` (Fp * n_per_tri * 27 floats) and a per-vertex pass adds the rows of the vertex's incident faces (vf_offsets /
- * vf_faces: the table dwg_mesh_vertex_normals takes) in table order.  g_verts_* [Vp,3] are OVERWRITTEN (g_verts_cnl may be NULL);
+ * vf_faces: the table dwg_mesh_vertex_normals takes) in table order.  g_verts_* [Vp,3] are OVERWRITTEN (g_verts_cnl may be NULL), with
+ * zeros when Fp == 0;
  * dwg_mesh_vertex_normals_backward then accumulates into g_verts_obs, also by a per-vertex gather.  The same bits on every run. */
 int dwg_meshbind_backward_verts_gather(int32_t Vp, int32_t Fp, int32_t n_per_tri, const float* bary, const float* scale_params,
                                        const float* verts_cnl, const float* verts_obs, const float* vnormals_obs, const int32_t* triangles,

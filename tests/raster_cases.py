@@ -128,12 +128,14 @@ def check_images(st, name, note=None):
         note_parity(note, st)
 
 
-def note_parity(name, st):
+def note_parity(name, st, file=None):
     """One row of gpurun_out/parity_raster.json (copied to profiles/rNN_parity_raster.json at round end)."""
     import json
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     path = os.path.join(root, "gpurun_out", "parity_raster.json")
+    if file is not None:            # another suite's report, in the same measured-output directory
+        path = os.path.join(os.path.dirname(path), file)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     d = json.load(open(path)) if os.path.exists(path) else {}
     d[str(name)] = st
