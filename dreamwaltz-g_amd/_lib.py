@@ -199,6 +199,13 @@ SIGNATURES = {
                                                ctypes.c_float, _i32, _vp, _vp]),
     "dwg_condition_workspace_bytes": (_sz, [_i32, _i32]),
     "dwg_condition_draw": (ctypes.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    # include/dwg_depthmap.h
+    "dwg_depthmap_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dwg_depthmap_cast": (ctypes.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "dwg_depthmap_image": (ctypes.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dwg_pretrain_loss_workspace_bytes": (_sz, [_i64]),
+    "dwg_pretrain_loss_forward": (ctypes.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dwg_pretrain_loss_backward": (ctypes.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # include/dwg_graph.h
     "dwg_graph_begin_capture": (ctypes.c_int, [_vp]),
     "dwg_graph_end_capture": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),

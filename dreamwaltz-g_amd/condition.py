@@ -1,12 +1,15 @@
 """OpenPose-style condition image of the posed body ON THE GPU -- host-side mirror of the reference's
 `core/human/smpl_condition.py` (`SMPL2Condition`, `OcclusionCulling`) and `utils/open3d.py:8-19` (`build_ray_casting_scene`) for
-condition types 'pose' / 'openpose', over `csrc/condition.hip` (include/dwg_condition.h).
+condition types 'pose' / 'openpose', over `csrc/condition.hip` (include/dwg_condition.h), and for 'depth_raw' -- the condition of the
+NeRF pretrain recipe (scripts/pretrain_nerf.sh) -- with `export_depth` / `export_normal_raw` (`utils/open3d.py:21-45` cast_rays) over
+`csrc/depthmap.hip` (include/dwg_depthmap.h).
 
 Same names, arguments and error behaviour as the reference seam; what differs, deliberately:
   * the "ray casting scene" is the mesh itself as it lies in HBM (no BVH is built for a mesh that moves every step);
   * `export_pose` returns a CUDA uint8 tensor [H, W, 3] (RGB, the reference's wire format) instead of a PIL image --
     `ConditionImage.to_pil()` gives the PIL image where one is wanted, `export_pose_chw` gives the float [1, 3, H, W] in [0, 1]
     that `ControlNetScoreDistillation.prepare_image` would make of it (controlnet.py:33-55 at equal size is the identity resize);
+  * `export_depth(raw=True)` returns a `DepthMap` (fp32 [H, W] on the device; `np.asarray(depth_map)` gives the reference's array);
   * nothing here leaves the device: no `.cpu()`, no host synchronisation.
 There is no CPU fallback: CPU tensors raise."""
 import ctypes
@@ -101,8 +104,27 @@ class ConditionImage:
         return (self.u8.permute(2, 0, 1).float() / 255.0).unsqueeze(0)
 
 
+class DepthMap:
+    """t_hit of one ray per pixel, fp32 [H, W] on the device (+inf = miss): what export_depth(raw=True) returns as an np.ndarray in the
+    reference.  `np.asarray(m)` / `np.nan_to_num(m, ...)` download it, so the reference's own consumers work on it unchanged."""
+
+    def __init__(self, t: torch.Tensor):
+        self.t = t
+
+    @property
+    def shape(self):
+        return tuple(self.t.shape)
+
+    def to_numpy(self) -> np.ndarray:
+        return self.t.detach().cpu().numpy()
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.to_numpy()
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+
 class SMPL2Condition:
-    """smpl_condition.py:145-320 for condition_type 'pose' / 'openpose'.  `cfg` carries draw_body_keypoints, draw_hand_keypoints,
+    """smpl_condition.py:145-320 for condition_type 'pose' / 'openpose' / 'depth_raw'.  `cfg` carries draw_body_keypoints, draw_hand_keypoints,
     draw_face_landmarks, openpose_left_right_flip, use_occlusion_culling, smpl_type, ignore_body_self_occlusion (PromptConfig)."""
 
     def __init__(self, cfg) -> None:
@@ -115,6 +137,7 @@ class SMPL2Condition:
         else:
             self.occlusion_culling = None
         self._ws = {}
+        self._depth_ws = {}
 
     # -- the two launches ------------------------------------------------------------------------------------------------
     def pose_rows(self, keypoints: torch.Tensor, ray_casting_scene: Optional[RayCastingScene], extrinsic: torch.Tensor,
@@ -175,16 +198,99 @@ class SMPL2Condition:
         rows = self.pose_rows(keypoints, ray_casting_scene, camera_params['extrinsic'], camera_params['intrinsics'])
         return self.draw(rows, camera_params['height'], camera_params['width'], out_u8=False, out_chw=True)[1]
 
+    # -- the depth map (csrc/depthmap.hip) ---------------------------------------------------------------------------------
+    def cast_depth(self, ray_casting_scene: RayCastingScene, extrinsic: torch.Tensor, intrinsics: torch.Tensor, height: int, width: int,
+                   normals: bool = False, minmax: bool = False):
+        """utils/open3d.py:21-45 cast_rays: one pinhole ray per pixel -> (t_hit fp32 [H,W], primitive normals fp32 [H,W,3] | None,
+        workspace).  `minmax` leaves the extrema of 1 / t_hit in the workspace for `_depth_image(..., from_cast=True)`."""
+        if not isinstance(ray_casting_scene, RayCastingScene):
+            raise RuntimeError("dreamwaltz_g_amd.condition runs on the GPU only (HIP kernels); the scene is build_ray_casting_scene's")
+        if not (torch.is_tensor(extrinsic) and torch.is_tensor(intrinsics)):
+            raise RuntimeError("dreamwaltz_g_amd.condition runs on the GPU only (HIP kernels); the camera matrices are tensors")
+        verts, tris = ray_casting_scene.vertices, ray_casting_scene.triangles
+        dev = verts.device
+        height, width = int(height), int(width)
+        ext = extrinsic.detach().to(dev).float().reshape(4, 4).contiguous()
+        intr = intrinsics.detach().to(dev).float().reshape(3, 3).contiguous()
+        V, F = int(verts.shape[0]), int(tris.shape[0])
+        L = _lib.lib()
+        key = (str(dev), height, width, F)
+        if key not in self._depth_ws:
+            self._depth_ws[key] = torch.empty(max(int(L.dwg_depthmap_workspace_bytes(height, width, F)), 64), dtype=torch.uint8, device=dev)
+        ws = self._depth_ws[key]
+        t = torch.empty(height, width, dtype=torch.float32, device=dev)
+        n = torch.empty(height, width, 3, dtype=torch.float32, device=dev) if normals else None
+        p = _lib.ptr
+        _lib.check(L.dwg_depthmap_cast(height, width, p(ext), p(intr), V, p(verts) if F else None, F, p(tris) if F else None, p(t), p(n),
+                                       1 if minmax else 0, p(ws), ws.numel(), _stream(dev)), "dwg_depthmap_cast")
+        return t, n, ws
+
+    def depth_image(self, t_hit: torch.Tensor, out_u8: bool = True, out_chw: bool = False, _ws=None):
+        """export_depth's inverse + normalise + uint8 statements (smpl_condition.py:242-248) from a t_hit map [H,W] ->
+        (uint8 [H,W,3] | None, float [1,3,H,W] | None)."""
+        if not t_hit.is_cuda:
+            raise RuntimeError("dreamwaltz_g_amd.condition runs on the GPU only (HIP kernels); got a CPU tensor")
+        dev = t_hit.device
+        t_hit = t_hit.detach().float().contiguous()
+        H, W = int(t_hit.shape[0]), int(t_hit.shape[1])
+        ws = _ws
+        if ws is None:                                                   # the extrema are taken here; any workspace of this device will do
+            key = (str(dev), "image")
+            if key not in self._depth_ws:
+                self._depth_ws[key] = torch.empty(64, dtype=torch.uint8, device=dev)
+            ws = self._depth_ws[key]
+        u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if out_u8 else None
+        chw = torch.empty(1, 3, H, W, dtype=torch.float32, device=dev) if out_chw else None
+        p = _lib.ptr
+        _lib.check(_lib.lib().dwg_depthmap_image(H, W, p(t_hit), 0 if _ws is None else 1, p(u8), p(chw), p(ws), ws.numel(), _stream(dev)),
+                   "dwg_depthmap_image")
+        return u8, chw
+
+    @staticmethod
+    def _depth_flags(inverse, normalize):
+        if not (inverse and normalize):
+            raise NotImplementedError("export_depth(inverse=%r, normalize=%r): without both, the reference casts inf to uint8, which is "
+                                      "platform-defined; only the defaults (and raw=True) are restated" % (inverse, normalize))
+
+    def export_depth(self, ray_casting_scene, inverse=True, normalize=True, raw=False, **camera_params):
+        """smpl_condition.py:237-249; camera_params as export_pose's.  raw=True -> DepthMap, else the ConditionImage."""
+        if not raw:
+            self._depth_flags(inverse, normalize)
+        t, _, ws = self.cast_depth(ray_casting_scene, camera_params['extrinsic'], camera_params['intrinsics'], camera_params['height'],
+                                   camera_params['width'], minmax=not raw)
+        if raw:
+            return DepthMap(t)
+        return ConditionImage(self.depth_image(t, _ws=ws)[0])
+
+    def export_depth_chw(self, ray_casting_scene, inverse=True, normalize=True, **camera_params) -> torch.Tensor:
+        """The same image as the float [1,3,H,W] in [0,1] ControlNet consumes (the twin of export_pose_chw)."""
+        self._depth_flags(inverse, normalize)
+        t, _, ws = self.cast_depth(ray_casting_scene, camera_params['extrinsic'], camera_params['intrinsics'], camera_params['height'],
+                                   camera_params['width'], minmax=True)
+        return self.depth_image(t, out_u8=False, out_chw=True, _ws=ws)[1]
+
+    def export_normal_raw(self, ray_casting_scene, raw=True, **camera_params) -> torch.Tensor:
+        """smpl_condition.py:264-269 with raw=True: primitive normals fp32 [H,W,3] (zero where the ray misses)."""
+        if not raw:
+            raise NotImplementedError("export_normal_raw(raw=False): the reference casts negative floats to uint8 there, which is "
+                                      "platform-defined")
+        return self.cast_depth(ray_casting_scene, camera_params['extrinsic'], camera_params['intrinsics'], camera_params['height'],
+                               camera_params['width'], normals=True)[1]
+
     def __call__(self, smpl_outputs, triangles, camera_params: dict, condition_type: str, condition_height: int,
-                 condition_width: int) -> ConditionImage:
-        """smpl_condition.py:271-320 (numpy-style branch, 'pose' / 'openpose')."""
-        if condition_type not in ('pose', 'openpose'):
-            raise NotImplementedError("condition_type %r: only the OpenPose skeleton image is on the SDS hot path" % (condition_type,))
+                 condition_width: int):
+        """smpl_condition.py:271-320 (numpy-style branch): 'pose' / 'openpose' -> ConditionImage, 'depth_raw' -> DepthMap."""
+        if condition_type not in ('pose', 'openpose', 'depth_raw'):
+            raise NotImplementedError("condition_type %r: the OpenPose skeleton image ('pose' / 'openpose') and the raw depth map "
+                                      "('depth_raw') are native; 'depth', 'normal' and 'mesh' are not" % (condition_type,))
         extrinsic = camera_params['extrinsic'][0]
         intrinsics = camera_params['intrinsics'][0]
         assert extrinsic.dim() == 2 and extrinsic.numel() == 16
         assert intrinsics.dim() == 2 and intrinsics.numel() == 9
         intrinsics = adjust_intrinsics_size(intrinsics, width=condition_width, height=condition_height)
+        if condition_type == 'depth_raw':
+            return self.export_depth(build_ray_casting_scene(smpl_outputs.vertices.detach(), triangles), raw=True, intrinsics=intrinsics,
+                                     extrinsic=extrinsic, width=condition_width, height=condition_height)
         scene = build_ray_casting_scene(smpl_outputs.vertices.detach(), triangles) if self.occlusion_culling is not None else None
         return self.export_pose(smpl_outputs.joints.detach(), scene, intrinsics=intrinsics, extrinsic=extrinsic, width=condition_width,
                                 height=condition_height)

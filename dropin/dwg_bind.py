@@ -23,6 +23,11 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              on the reference's own network (B7 when bound).  CPU vertices and unknown sigma_loss_types
                                              go to the original method.  The samples are drawn from torch's CUDA generator: the same
                                              distribution as trimesh's, not the same draws.  DWG_BIND_SIGMA=0: nothing is bound
+  B9  core.trainer.Trainer.pretrain_forward (trainer.py:1242-1279)   -> dreamwaltz_g_amd.pretrain.pretrain_forward: the pretrain recipe's
+                                             two MSE terms against the SMPL-X depth map as one fused forward and one fused backward
+                                             launch; the map stays on the device when the loader hands a condition.DepthMap (INTEGRATION
+                                             B9), an np.ndarray is uploaded.  visual_outputs is built only when time_to_snapshot.  CPU
+                                             renders go to the original method.  DWG_BIND_PRETRAIN=0: nothing is bound
   B3  core.system.avatar.build_gaussian_avatar (avatar.py:1642-1714)  -> the reference builds ITS avatar (point cloud, nearest triangles,
                                              inverse LBS, LBS weights ...), then `DreamWaltzG.from_reference(ref)` adopts every Parameter
                                              and buffer by name; non-DreamWaltzG gs_types are returned untouched (reference path)
@@ -38,6 +43,7 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
 
 Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's field network (B7) on the reference path
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
+             DWG_BIND_PRETRAIN = 0                    leave Trainer.pretrain_forward (B9) on the reference path (numpy on the host)
              DWG_BIND_DTYPE = f32x | f32 | f16 | bf16  storage type of the denoiser / VAE plans.  Unset: the precision the reference loaded its
                                                      pipeline in -- torch.float32 (its default, core/guidance/basic.py:233) -> f32x (fp32-grade
                                                      split precision on the 16-bit MFMA pipe), torch.float16 (`--guide.dtype fp16`,
@@ -133,6 +139,11 @@ def _sigma_covered(trainer, data):
 
 
 def _patch_trainer_module(mod):
+    _patch_trainer_sigma(mod)
+    _patch_trainer_pretrain(mod)
+
+
+def _patch_trainer_sigma(mod):
     if os.environ.get("DWG_BIND_SIGMA", "1") == "0":
         return
     cls = mod.Trainer
@@ -150,6 +161,44 @@ def _patch_trainer_module(mod):
     setattr(calc_sigma_loss, _PATCHED, True)
     calc_sigma_loss.__wrapped__ = orig
     cls.calc_sigma_loss = calc_sigma_loss
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# B9: the NeRF pretrain step against the SMPL-X depth map
+# --------------------------------------------------------------------------------------------------------------------------------------
+class _RenderedOnce:
+    """Stands for the trainer inside pretrain_forward (the native one or the wrapped original) once the render has been made."""
+
+    def __init__(self, trainer, render_outputs):
+        self._trainer, self._render_outputs = trainer, render_outputs
+
+    def render(self, data):
+        return self._render_outputs
+
+    def __getattr__(self, name):
+        return getattr(self._trainer, name)
+
+
+def _patch_trainer_pretrain(mod):
+    if os.environ.get("DWG_BIND_PRETRAIN", "1") == "0":
+        return
+    cls = mod.Trainer
+    orig = cls.pretrain_forward
+    if getattr(orig, _PATCHED, False):
+        return
+    import functools
+
+    @functools.wraps(orig)
+    def pretrain_forward(self, data):
+        once = _RenderedOnce(self, self.render(data=data))
+        if not getattr(once._render_outputs.get('depth'), 'is_cuda', False):
+            return orig(once, data)                                # a CPU render: the reference's own statements fit it
+        _pkg()
+        from dreamwaltz_g_amd.pretrain import pretrain_forward as native
+        return native(once, data)
+    setattr(pretrain_forward, _PATCHED, True)
+    pretrain_forward.__wrapped__ = orig
+    cls.pretrain_forward = pretrain_forward
 
 
 # --------------------------------------------------------------------------------------------------------------------------------------
@@ -364,3 +413,5 @@ def uninstall():
         cls = getattr(mod, "Trainer", None)
         if cls is not None and getattr(cls.__dict__.get("calc_sigma_loss"), _PATCHED, False):
             cls.calc_sigma_loss = cls.calc_sigma_loss.__wrapped__
+        if cls is not None and getattr(cls.__dict__.get("pretrain_forward"), _PATCHED, False):
+            cls.pretrain_forward = cls.pretrain_forward.__wrapped__
