@@ -109,6 +109,12 @@ SIGNATURES = {
     "dwg_sigma_distance_workspace_bytes": (_sz, [_i32, _i32]),
     "dwg_sigma_point_mesh_distance": (ctypes.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dwg_sigma_keep_mask": (ctypes.c_int, [_i32, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp]),
+    # include/dwg_avatar_init.h
+    "dwg_avinit_barycentric": (ctypes.c_int, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dwg_avinit_lbs_interp": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dwg_avinit_knn": (ctypes.c_int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "dwg_avinit_knn_weights": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp]),
+    "dwg_avinit_smooth": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     # include/dwg_raymarch.h
     "dwg_raymarch_near_far_from_aabb": (ctypes.c_int, [_vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp]),
     "dwg_raymarch_sph_from_ray": (ctypes.c_int, [_vp, _vp, _f32, _u32, _vp, _vp]),

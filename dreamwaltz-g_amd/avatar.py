@@ -412,7 +412,8 @@ class DreamWaltzG(nn.Module):
         """The HIP-backed avatar for the object the reference's `build_gaussian_avatar` returned (avatar.py:1642-1714 -> DreamWaltzG.__init__
         avatar.py:1098-1244): same Gaussians, same networks, same body -- every Parameter / buffer is adopted BY NAME from `ref`
         (its state_dict() loads into this object key for key), the constructor-time work of the reference (NeRF point cloud, nearest
-        triangles, inverse LBS of the initial positions, LBS-weight smoothing) is NOT repeated.  dropin/dwg_bind.py calls this so that
+        triangles, inverse LBS of the initial positions, LBS-weight smoothing) is NOT repeated here: `from_point_cloud` is its native
+        counterpart, and under the binding the reference's constructor reaches the same kernels (B11).  dropin/dwg_bind.py calls this so that
         main.py reaches the kernels without an edit; `cfg` defaults to `ref.cfg` (non-default render flags are rejected loudly)."""
         cfg = cfg if cfg is not None else getattr(ref, "cfg", None)
         if type(ref.lbs_model).__name__ != "GeneralLinearBlendSkinning":
@@ -455,6 +456,57 @@ class DreamWaltzG(nn.Module):
         av.cfg = cfg
         av.__dict__["reference"] = ref       # NOT a registered sub-module (no state_dict keys): construction-time attributes the trainer
                                              # may still read (canonical_vertices, canonical_triangles, ...) resolve through __getattr__
+        return av
+
+    @classmethod
+    def from_point_cloud(cls, lbs_model, points, canonical_vertices, canonical_triangles, smpl_canonical_inputs,
+                         mesh_binding_gaussians=None, cfg=None, **learn_flags) -> "DreamWaltzG":
+        """The avatar for a NeRF-stage point cloud, built on the device: the native counterpart of the reference constructor's tail
+        (avatar.py:1176-1245).  points [N, 3] fp32 (canonical-pose space) and the canonical body mesh (canonical_vertices [V, 3] fp32,
+        canonical_triangles [F, 3] int) on one HIP device.  In the reference's order: nearest triangles (avatar_init.find_nearest_triangles);
+        with cfg.render.prune_points_close_to_mesh the per-part prune against each mesh-bound part's `predefined_triangle_indices` (the hands'
+        threshold x 10); LBS weights interpolated from lbs_model.lbs_weights and smoothed as cfg.render.lbs_weight_smooth[_K, _N] say;
+        inverse LBS of the points under the canonical transforms; scales init_scale, identity quaternions.  The learn_* flags, init_offset /
+        init_scale / max_scale and nerf.bound come from cfg when given (the constructor's defaults otherwise); **learn_flags (any keyword of
+        the constructor) override them.  `nearest_triangles_buffer` stays on the object, on the points' device."""
+        from . import avatar_init as ai
+        r = getattr(cfg, "render", None)
+        mesh = dict(mesh_binding_gaussians or {})
+        points = points.detach()
+        ntb = ai.find_nearest_triangles(points, canonical_vertices, canonical_triangles)
+        if r is not None and getattr(r, "prune_points_close_to_mesh", False):
+            dist = getattr(r, "prune_dists_close_to_mesh", None)
+            for part, m in mesh.items():
+                if part not in ("hands", "face"):
+                    raise NotImplementedError("prune_points_close_to_mesh for the body part %r (avatar.py:1195-1199 knows hands and face)" % part)
+                tri = getattr(m, "predefined_triangle_indices", None)
+                if tri is None:
+                    raise RuntimeError("prune_points_close_to_mesh: mesh_binding_gaussians[%r] carries no predefined_triangle_indices" % part)
+                threshold = None if dist is None else (dist * 10 if part == "hands" else dist)
+                points, ntb = ai.prune_points_close_to_mesh(points, ntb, tri, threshold=threshold)
+        lbs_weights = ai.initialize_lbs_weights(lbs_model.lbs_weights, ntb, positions=points,
+                                                smooth=bool(getattr(r, "lbs_weight_smooth", False)),
+                                                smooth_K=getattr(r, "lbs_weight_smooth_K", None), smooth_N=getattr(r, "lbs_weight_smooth_N", None))
+        kw = {}
+        if r is not None:
+            for k in ("learn_positions", "learn_scales", "learn_quaternions", "learn_lbs_weights", "learn_hand_betas", "learn_face_betas",
+                      "init_offset", "init_scale", "max_scale"):
+                if hasattr(r, k):
+                    kw[k] = getattr(r, k)
+        if hasattr(getattr(cfg, "nerf", None), "bound"):
+            kw["nerf_bound"] = float(cfg.nerf.bound)
+        kw.update(learn_flags)
+        n, dev = points.shape[0], points.device
+        init_scale = float(kw.get("init_scale", 0.001))
+        quaternions = torch.zeros(n, 4, device=dev)
+        quaternions[:, 0] = 1.0                                  # matrix_to_quaternion(eye(3)): (w, x, y, z) = (1, 0, 0, 0)
+        canonical = {k: (v.detach().to(dev) if torch.is_tensor(v) else v) for k, v in smpl_canonical_inputs.items()}
+        av = cls(lbs_model, points, torch.full((n, 3), init_scale, device=dev), quaternions, lbs_weights, canonical, mesh,
+                 nearest_vertex_indices=ntb['nearest_vertex_indices'], cfg=cfg, **kw).to(dev)
+        with torch.no_grad():                                    # the blended inverse needs the avatar's own (normalised) weights
+            av._positions.copy_(av.inverse_lbs_transform(points, av.lbs_model.forward(**canonical)[-1]))
+        av.nearest_triangles_buffer = ntb
+        av.cfg = cfg
         return av
 
     def __getattr__(self, name):

@@ -28,6 +28,11 @@ class RenderConfig:
     learn_lbs_weights: bool = False
     learn_hand_betas: bool = False
     learn_face_betas: bool = False
+    lbs_weight_smooth: bool = False                  # configs/__init__.py:113-115; both shipped GS recipes pass True (train_w_expr.sh:67)
+    lbs_weight_smooth_K: Optional[int] = 30
+    lbs_weight_smooth_N: Optional[int] = 5000
+    prune_points_close_to_mesh: bool = True          # configs/__init__.py:191-192
+    prune_dists_close_to_mesh: Optional[float] = 0.01
     learn_mesh_bary_coords: bool = True
     learn_mesh_vertex_coords: bool = False
     learn_mesh_scales: bool = True

@@ -31,6 +31,14 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
   B3  core.system.avatar.build_gaussian_avatar (avatar.py:1642-1714)  -> the reference builds ITS avatar (point cloud, nearest triangles,
                                              inverse LBS, LBS weights ...), then `DreamWaltzG.from_reference(ref)` adopts every Parameter
                                              and buffer by name; non-DreamWaltzG gs_types are returned untouched (reference path)
+  B11 core.system.avatar.find_nearest_triangles (avatar.py:766-806), knn_points (avatar.py:24-34) and
+      LBSUtils.initialize_lbs_weights (avatar.py:865-911)            -> dreamwaltz_g_amd.avatar_init: the constructor-time geometry of
+                                             that avatar (and of every reset_by_state_dict) on the device instead of libigl, pytorch3d
+                                             and a torch loop: closest faces and barycentric coordinates, exact K nearest neighbours,
+                                             the interpolated LBS weights and their smooth_N Jacobi sweeps.  All three are resolved at call
+                                             time, so build_gaussian_avatar, reset_by_state_dict and the module's other knn_points callers
+                                             reach them; the results come back in the reference's containers, dtypes and placements.
+                                             Without a HIP device the originals run.  DWG_BIND_INIT=0: nothing is bound
   B5  core.system.scene.build_scene (scene.py:224-245)                -> dreamwaltz_g_amd.scene.Scene around that avatar (same forward /
                                              state_dict / avatar.get_optimizer surface the Trainer uses: trainer.py:578-604,680-709,859-890).
                                              `--render.use_video_background`: the reference's VideoBackground decodes the video, and
@@ -42,6 +50,7 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              calc_gradients, tp_scheduler, pipe, decode_latents, isinstance checks) is the reference's own.
 
 Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's field network (B7) on the reference path
+             DWG_BIND_INIT = 0                        leave the avatar constructor's geometry (B11) on the reference path (igl + pytorch3d)
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
              DWG_BIND_PRETRAIN = 0                    leave Trainer.pretrain_forward (B9) on the reference path (numpy on the host)
              DWG_BIND_DTYPE = f32x | f32 | f16 | bf16  storage type of the denoiser / VAE plans.  Unset: the precision the reference loaded its
@@ -96,6 +105,92 @@ def _patch_avatar_module(mod):
     setattr(build_gaussian_avatar, _PATCHED, True)
     build_gaussian_avatar.__wrapped__ = orig
     mod.build_gaussian_avatar = build_gaussian_avatar
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# B11: the avatar constructor's geometry
+# --------------------------------------------------------------------------------------------------------------------------------------
+def _hip_device():
+    """The current HIP device, or None when the process has none (then the B11 wrappers call the reference's functions)."""
+    import torch
+    return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+
+
+def _on(dev, x, dtype):
+    import numpy as np
+    import torch
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    return torch.as_tensor(x).detach().to(device=dev, dtype=dtype)
+
+
+def _patch_avatar_init(mod):
+    if os.environ.get("DWG_BIND_INIT", "1") == "0":
+        return
+    import functools
+    orig_fnt, orig_knn = mod.find_nearest_triangles, mod.knn_points
+    utils = mod.LBSUtils
+    orig_init = utils.__dict__["initialize_lbs_weights"]
+    orig_init = getattr(orig_init, "__func__", orig_init)
+    if getattr(orig_fnt, _PATCHED, False):
+        return
+
+    @functools.wraps(orig_fnt)
+    def find_nearest_triangles(points, vertices, triangles, device=None):
+        dev = _hip_device()
+        if dev is None:
+            return orig_fnt(points, vertices, triangles, device=device)
+        import torch
+        _pkg()
+        from dreamwaltz_g_amd import avatar_init
+        # torch.tensor(x, device=None) of the reference lands on the CPU
+        return avatar_init.find_nearest_triangles(_on(dev, points, torch.float32), _on(dev, vertices, torch.float32), _on(dev, triangles, torch.int64),
+                                                  device="cpu" if device is None else device)
+
+    @functools.wraps(orig_knn)
+    def knn_points(query_points, reference_points, K=3, device=None):
+        dev = _hip_device()
+        if dev is None:
+            return orig_knn(query_points, reference_points, K=K, device=device)
+        import torch
+        _pkg()
+        from dreamwaltz_g_amd import avatar_init
+        if device is None:
+            device = query_points.device
+        res = avatar_init.knn_points(_on(dev, query_points, torch.float32), _on(dev, reference_points, torch.float32), K=K, device=device)
+        try:
+            from pytorch3d.ops.knn import _KNN
+        except Exception:
+            return res                                            # same field names
+        return _KNN(dists=res.dists, idx=res.idx, knn=None)
+
+    @functools.wraps(orig_init)
+    def initialize_lbs_weights(lbs_model, nearest_triangles_buffer, positions=None, smooth=False, smooth_K=None, smooth_N=None, use_sqrt=True,
+                               valid_dist_threshold=0.01):
+        dev = _hip_device()
+        if dev is None:
+            return orig_init(lbs_model, nearest_triangles_buffer, positions=positions, smooth=smooth, smooth_K=smooth_K, smooth_N=smooth_N,
+                             use_sqrt=use_sqrt, valid_dist_threshold=valid_dist_threshold)
+        import torch
+        _pkg()
+        from dreamwaltz_g_amd import avatar_init
+        table = lbs_model.lbs_weights
+        out = avatar_init.initialize_lbs_weights(_on(dev, table, torch.float32), nearest_triangles_buffer,
+                                                 positions=None if positions is None else _on(dev, positions, torch.float32), smooth=smooth,
+                                                 smooth_K=smooth_K, smooth_N=smooth_N, use_sqrt=use_sqrt, valid_dist_threshold=valid_dist_threshold)
+        return out.to(table.device)
+
+    for f, orig in ((find_nearest_triangles, orig_fnt), (knn_points, orig_knn), (initialize_lbs_weights, orig_init)):
+        setattr(f, _PATCHED, True)
+        f.__wrapped__ = orig
+    mod.find_nearest_triangles = find_nearest_triangles
+    mod.knn_points = knn_points
+    utils.initialize_lbs_weights = staticmethod(initialize_lbs_weights)
+
+
+def _patch_avatar_hooks(mod):
+    _patch_avatar_module(mod)
+    _patch_avatar_init(mod)
 
 
 # --------------------------------------------------------------------------------------------------------------------------------------
@@ -340,7 +435,7 @@ def _patch_guidance_module(mod):
 # --------------------------------------------------------------------------------------------------------------------------------------
 # post-import hooks
 # --------------------------------------------------------------------------------------------------------------------------------------
-HOOKS = {"core.system.avatar": _patch_avatar_module, "core.system.scene": _patch_scene_module,
+HOOKS = {"core.system.avatar": _patch_avatar_hooks, "core.system.scene": _patch_scene_module,
          "core.guidance.controlnet": _patch_guidance_module, "core.nerf.nerf_model": _patch_nerf_module,
          "core.trainer": _patch_trainer_module}
 
@@ -403,10 +498,14 @@ def uninstall():
         mod = sys.modules.get(name)
         if mod is None:
             continue
-        for attr in ("build_gaussian_avatar", "build_scene", "build_NeRFNetwork"):
+        for attr in ("build_gaussian_avatar", "build_scene", "build_NeRFNetwork", "find_nearest_triangles", "knn_points"):
             f = getattr(mod, attr, None)
             if f is not None and getattr(f, _PATCHED, False):
                 setattr(mod, attr, f.__wrapped__)
+        cls = getattr(mod, "LBSUtils", None)
+        f = getattr(cls.__dict__.get("initialize_lbs_weights"), "__func__", None) if cls is not None else None
+        if f is not None and getattr(f, _PATCHED, False):
+            cls.initialize_lbs_weights = staticmethod(f.__wrapped__)
         cls = getattr(mod, "ControlNetScoreDistillation", None)
         if cls is not None and getattr(cls.__init__, _PATCHED, False):
             cls.__init__ = cls.__init__.__wrapped__
