@@ -14,7 +14,6 @@
 //     (two 8-byte reads per fragment) instead of shuffling P between lanes.
 //   * per-query rescale of O is a per-lane scalar multiply (each lane owns one query column of O^T).
 #include "dwg_common.h"
-#include <cstdlib>
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_nn.h"
 
@@ -288,12 +287,11 @@ int dwg_attention_forward(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t 
     hipStream_t stream = (hipStream_t)stream_;
     // algorithmic flops of the launch (QK^T and PV on the logical head size; the padded tile columns are not counted)
     const double flops = 4.0 * B * H * (double)Nq * Nk * d;
-    static const bool no_lrow = getenv("DWG_ATTN_NO_LROW") != nullptr;       // A/B switch: softmax denominator summed on the VALU
     if (d <= 32) DWG_LAUNCH_W("flash_attn_d32", "k_flash_fwd<32, 32, 0>", flops, (k_flash_fwd<32, 32>), grid, block, 0, stream, p);
-    else if (d == 40 && !no_lrow) DWG_LAUNCH_W("flash_attn_d48", "k_flash_fwd<48, 64, 40>", flops, (k_flash_fwd<48, 64, 40>), grid, block, 0, stream, p);
+    else if (d == 40) DWG_LAUNCH_W("flash_attn_d48", "k_flash_fwd<48, 64, 40>", flops, (k_flash_fwd<48, 64, 40>), grid, block, 0, stream, p);
     else if (d <= 48) DWG_LAUNCH_W("flash_attn_d48", "k_flash_fwd<48, 64, 0>", flops, (k_flash_fwd<48, 64>), grid, block, 0, stream, p);
     else if (d <= 64) DWG_LAUNCH_W("flash_attn_d64", "k_flash_fwd<64, 64, 0>", flops, (k_flash_fwd<64, 64>), grid, block, 0, stream, p);
-    else if (d == 80 && !no_lrow) DWG_LAUNCH_W("flash_attn_d96", "k_flash_fwd<96, 96, 80>", flops, (k_flash_fwd<96, 96, 80>), grid, block, 0, stream, p);
+    else if (d == 80) DWG_LAUNCH_W("flash_attn_d96", "k_flash_fwd<96, 96, 80>", flops, (k_flash_fwd<96, 96, 80>), grid, block, 0, stream, p);
     else if (d <= 96) DWG_LAUNCH_W("flash_attn_d96", "k_flash_fwd<96, 96, 0>", flops, (k_flash_fwd<96, 96>), grid, block, 0, stream, p);
     else DWG_LAUNCH_W("flash_attn_d160", "k_flash_fwd<160, 160, 0>", flops, (k_flash_fwd<160, 160>), grid, block, 0, stream, p);
     DWG_RETURN_IF_LAUNCH_FAILED();

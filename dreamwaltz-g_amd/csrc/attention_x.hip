@@ -11,7 +11,6 @@
 // Used by the "f32x" denoiser plans for every attention site of the SD-1.5 UNet / ControlNet (boundary B4, controlnet.py:98-114); the
 // reference runs these sites in fp32 (configs/__init__.py:236,241) through diffusers' scaled_dot_product_attention.
 #include "dwg_common.h"
-#include <cstdlib>
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_nn.h"
 #include "dwg_xfmt.h"
@@ -35,10 +34,8 @@ struct AttnXP {
     int dvw;                               //      k_flash_merge_x combines the ranges in split order
 };
 
-// DK = head dim padded to a multiple of 16, DV = padded to a multiple of 32.  LD > 0: the head dim is exactly LD < DV and row LD of the hi
-// plane of V^T holds ONES (lo plane: zeros), so the PV MFMAs accumulate the softmax denominator (of the split P the MFMAs use) in
-// accumulator row LD of both sets -- see attention.hip.
-template <int DK, int DV, int LD, int MINB>
+// DK = head dim padded to a multiple of 16, DV = padded to a multiple of 32.
+template <int DK, int DV, int MINB>
 __global__ __launch_bounds__(256, MINB) void k_flash_fwd_x(AttnXP p) {
     constexpr int KT = 32;
     constexpr int LDK = DK + 8;
@@ -92,7 +89,6 @@ __global__ __launch_bounds__(256, MINB) void k_flash_fwd_x(AttnXP p) {
     constexpr int NKC = (KT * (DK / 8) + 255) / 256, NVC = (KT * (DV / 8) + 255) / 256;
     dwg_x8 kreg[NKC], vreg[NVC];
     int kkey[NKC], vkey[NVC];
-    bool vone[NVC];
     const dwg_xs* kptr[NKC]; const dwg_xs* vptr[NVC];
     int klds[NKC], vlds[NVC];              // LDS offsets in halves (hi plane; the lo plane sits at a constant distance), -1: none
 #pragma unroll
@@ -110,20 +106,19 @@ __global__ __launch_bounds__(256, MINB) void k_flash_fwd_x(AttnXP p) {
         const int key = c % KT, dc = (c / KT) * 8;
         const bool on = c < KT * (DV / 8) && dc < p.d;
         vkey[i] = on ? key : (1 << 30);
-        vone[i] = LD > 0 && c < KT * (DV / 8) && dc == LD;
         vptr[i] = V + (long long)key * p.ldv + dc;
         vlds[i] = c < KT * (DV / 8) ? dc * LDV + key : -1;
     }
     auto fetch = [&](int k0) {
-        dwg_x8 z, one0;
+        dwg_x8 z;
 #pragma unroll
-        for (int e = 0; e < 8; e++) { z.hi[e] = (HT)0.f; z.lo[e] = (HT)0.f; one0.hi[e] = (HT)(e == 0 ? 1.f : 0.f); one0.lo[e] = (HT)0.f; }
+        for (int e = 0; e < 8; e++) { z.hi[e] = (HT)0.f; z.lo[e] = (HT)0.f; }
 #pragma unroll
         for (int i = 0; i < NKC; i++)
             kreg[i] = (long long)k0 + kkey[i] < p.Nk ? dwg_x8::load(kptr[i] + (long long)k0 * p.ldk) : z;
 #pragma unroll
         for (int i = 0; i < NVC; i++)
-            vreg[i] = (long long)k0 + vkey[i] < p.Nk ? dwg_x8::load(vptr[i] + (long long)k0 * p.ldv) : (vone[i] ? one0 : z);
+            vreg[i] = (long long)k0 + vkey[i] < p.Nk ? dwg_x8::load(vptr[i] + (long long)k0 * p.ldv) : z;
     };
     // K / V staging is software-pipelined through registers (tile t + 1 in flight while tile t is multiplied) -- except at d = 160, whose two
     // accumulator sets leave no registers for it: there the tile is fetched right before it is staged (8x8 / 16x16 latents: a few tiles)
@@ -177,18 +172,18 @@ __global__ __launch_bounds__(256, MINB) void k_flash_fwd_x(AttnXP p) {
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             s[r] = __builtin_amdgcn_exp2f(fmaf(s[r], p.scale_log2, -m_new));
-            if constexpr (LD == 0) rs += s[r];
+            rs += s[r];
         }
-        if constexpr (LD == 0) rs += __shfl_xor(rs, 32);
+        rs += __shfl_xor(rs, 32);
         if (__any(m_new != m_run)) {
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
 #pragma unroll
             for (int j = 0; j < NVB; j++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) { acc[j][r] *= alpha; acx[j][r] *= alpha; }
-            if constexpr (LD == 0) acc_l *= alpha;
+            acc_l *= alpha;
         }
-        if constexpr (LD == 0) acc_l += rs;
+        acc_l += rs;
         m_run = m_new;
         // P^T as B operand, split into its planes: step st uses registers 8 st .. 8 st + 7 of this lane
         h8 ph[2], pl[2];
@@ -222,13 +217,7 @@ __global__ __launch_bounds__(256, MINB) void k_flash_fwd_x(AttnXP p) {
     for (int j = 0; j < NVB; j++)
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[j][r] = fmaf(acx[j][r], DWG_X_LO_INV, acc[j][r]);
-    float l_run;
-    if constexpr (LD > 0) {
-        constexpr int W = LD % 32, R = (W & 3) + 4 * (W >> 3), HL = (W >> 2) & 1;
-        l_run = __shfl(acc[LD / 32][R], ql + 32 * HL);
-    } else {
-        l_run = acc_l;
-    }
+    const float l_run = acc_l;
     if (p.nsplit > 1) {
         // partial result of this key range: unnormalised O (both sets joined), the running maximum (log2 domain, scaled) and the denominator
         const int q = q0 + ql;
@@ -615,15 +604,10 @@ __global__ __launch_bounds__(256) void k_flash_merge_x(AttnXP p, int BH, int DV)
 
 // key ranges for a launch: none while the query blocks alone fill the chip or there are few key tiles; else enough ranges for ~512 workgroups,
 // at least two 32-key tiles per range, at most eight
-static int attn_kt(int d) {               // keys per tile of the kernel that serves head size d
-    static const int v2 = getenv("DWG_ATTN_V2") ? atoi(getenv("DWG_ATTN_V2")) : 1;
-    return (v2 && (d == 40 || d == 80)) ? 64 : 32;
-}
+static int attn_kt(int d) { return (d == 40 || d == 80) ? 64 : 32; }       // keys per tile of the kernel that serves head size d
 static int attn_splits(int B, int H, int Nq, int Nk, int kt) {
-    static const int off = getenv("DWG_ATTN_SPLIT") ? atoi(getenv("DWG_ATTN_SPLIT")) : -1;      // 0 / 1: never; n > 1: force n ranges
     const int base = dwg_cdiv(Nq, 128) * B * H, ntiles = dwg_cdiv(Nk, kt);
-    if (off == 0 || off == 1) return 1;
-    int sp = off > 1 ? off : (base >= 256 ? 1 : dwg_cdiv(512, base));
+    int sp = base >= 256 ? 1 : dwg_cdiv(512, base);
     if (sp > 8) sp = 8;
     if (sp > ntiles / 2) sp = ntiles / 2;
     return sp < 2 ? 1 : sp;
@@ -668,16 +652,13 @@ int dwg_attention_forward_x_ws(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int
     dim3 grid(dwg_cdiv(Nq, 128), B * H, sp), block(256);
     hipStream_t stream = (hipStream_t)stream_;
     const double flops = 4.0 * B * H * (double)Nq * Nk * d;     // QK^T and PV on the logical head size, one multiply-add per product
-    static const int v2 = getenv("DWG_ATTN_V2") ? atoi(getenv("DWG_ATTN_V2")) : 1;       // 0: the round-4 kernels at every head size
-    if (v2 && d == 40) launch_flash_x2<40, 64, 2>(p, grid, stream, "flash_attn_d40", "k_flash_fwd_x2<40, 64, 2>", flops);
-    else if (v2 && d == 80) launch_flash_x2<80, 64, 1>(p, grid, stream, "flash_attn_d80", "k_flash_fwd_x2<80, 64, 1>", flops);
-    else if (d <= 32) DWG_LAUNCH_W("flash_attn_d32", "k_flash_fwd_x<32, 32, 0, 2>", flops, (k_flash_fwd_x<32, 32, 0, 2>), grid, block, 0, stream, p);
-    else if (d == 40) DWG_LAUNCH_W("flash_attn_d48", "k_flash_fwd_x<48, 64, 40, 2>", flops, (k_flash_fwd_x<48, 64, 40, 2>), grid, block, 0, stream, p);
-    else if (d <= 48) DWG_LAUNCH_W("flash_attn_d48", "k_flash_fwd_x<48, 64, 0, 2>", flops, (k_flash_fwd_x<48, 64, 0, 2>), grid, block, 0, stream, p);
-    else if (d <= 64) DWG_LAUNCH_W("flash_attn_d64", "k_flash_fwd_x<64, 64, 0, 2>", flops, (k_flash_fwd_x<64, 64, 0, 2>), grid, block, 0, stream, p);
-    else if (d == 80) DWG_LAUNCH_W("flash_attn_d96", "k_flash_fwd_x<96, 96, 80, 1>", flops, (k_flash_fwd_x<96, 96, 80, 1>), grid, block, 0, stream, p);
-    else if (d <= 96) DWG_LAUNCH_W("flash_attn_d96", "k_flash_fwd_x<96, 96, 0, 1>", flops, (k_flash_fwd_x<96, 96, 0, 1>), grid, block, 0, stream, p);
-    else DWG_LAUNCH_W("flash_attn_d160", "k_flash_fwd_x<160, 160, 0, 1>", flops, (k_flash_fwd_x<160, 160, 0, 1>), grid, block, 0, stream, p);
+    if (d == 40) launch_flash_x2<40, 64, 2>(p, grid, stream, "flash_attn_d40", "k_flash_fwd_x2<40, 64, 2>", flops);
+    else if (d == 80) launch_flash_x2<80, 64, 1>(p, grid, stream, "flash_attn_d80", "k_flash_fwd_x2<80, 64, 1>", flops);
+    else if (d <= 32) DWG_LAUNCH_W("flash_attn_d32", "k_flash_fwd_x<32, 32, 2>", flops, (k_flash_fwd_x<32, 32, 2>), grid, block, 0, stream, p);
+    else if (d <= 48) DWG_LAUNCH_W("flash_attn_d48", "k_flash_fwd_x<48, 64, 2>", flops, (k_flash_fwd_x<48, 64, 2>), grid, block, 0, stream, p);
+    else if (d <= 64) DWG_LAUNCH_W("flash_attn_d64", "k_flash_fwd_x<64, 64, 2>", flops, (k_flash_fwd_x<64, 64, 2>), grid, block, 0, stream, p);
+    else if (d <= 96) DWG_LAUNCH_W("flash_attn_d96", "k_flash_fwd_x<96, 96, 1>", flops, (k_flash_fwd_x<96, 96, 1>), grid, block, 0, stream, p);
+    else DWG_LAUNCH_W("flash_attn_d160", "k_flash_fwd_x<160, 160, 1>", flops, (k_flash_fwd_x<160, 160, 1>), grid, block, 0, stream, p);
     DWG_RETURN_IF_LAUNCH_FAILED();
     if (sp > 1) {
         const long long n = (long long)B * H * Nq * (d / 4);

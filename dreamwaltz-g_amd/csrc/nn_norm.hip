@@ -4,7 +4,6 @@
 // same math through torch.nn.functional.group_norm / layer_norm / gelu / softmax inside diffusers.
 // Access pattern: every kernel walks the tensor in 16-byte (8 x bf16) chunks, whole rows per wave, so HBM sees full lines.
 #include "dwg_common.h"
-#include <cstdlib>
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_nn.h"
 #include "dwg_xfmt.h"
@@ -47,7 +46,7 @@ template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void k_gn_reduce(int HW, int C, int G, int pix_per_block, const T* __restrict__ x,
                                                    const T* __restrict__ dy, const float* __restrict__ stats,
                                                    const float* __restrict__ gamma, const float* __restrict__ beta, int silu,
-                                                   float eps, float* __restrict__ sums /*[B][G][2]*/, int deep) {
+                                                   float eps, float* __restrict__ sums /*[B][G][2]*/) {
     extern __shared__ __attribute__((aligned(16))) float lds[];   // [rows][Cb*2] partials for the current channel pass
     __shared__ float gacc[64 * 2];
     __shared__ float gstat[64 * 2];
@@ -80,10 +79,10 @@ __global__ __launch_bounds__(256) void k_gn_reduce(int HW, int C, int G, int pix
             }
             // Long pixel ranges (the VAE's 128^2 .. 512^2 tensors: tens of trips) keep FOUR independent 16-byte loads in flight per thread:
             // with one load per trip the pass is bound by memory latency (~1.5 TB/s measured), not by HBM.  Short ranges (every denoiser
-            // tensor: 1-2 trips) take the plain loop below -- unrolling THAT one made all of them slower (rejected list).
+            // tensor: 1-2 trips) take the plain loop after it -- unrolling THAT one made all of them slower (rejected list).
             int p = p0 + prow;
             if (!BWD) {
-                for (; deep && p + 3 * rows < p1; p += 4 * rows) {
+                for (; p + 3 * rows < p1; p += 4 * rows) {
                     const T* xp = x + ((size_t)b * HW + p) * C + (size_t)cc * 8;
                     const size_t st = (size_t)rows * C;
                     const V8<T> x0 = V8<T>::load(xp), x1 = V8<T>::load(xp + st),
@@ -94,7 +93,12 @@ __global__ __launch_bounds__(256) void k_gn_reduce(int HW, int C, int G, int pix
                         s1[e] += (a + bq) + (c + d); s2[e] += (a * a + bq * bq) + (c * c + d * d);
                     }
                 }
-            } else if (deep && p < p1) {
+                for (; p < p1; p += rows) {
+                    const V8<T> xv = V8<T>::load(x + ((size_t)b * HW + p) * C + (size_t)cc * 8);
+#pragma unroll
+                    for (int e = 0; e < 8; e++) { float v = xv.get(e); s1[e] += v; s2[e] += v * v; }
+                }
+            } else if (p < p1) {
                 // backward statistics: the next trip's two loads are issued before this trip's arithmetic (software pipeline; unrolling the
                 // arithmetic itself costs 70 more registers and halves the occupancy)
                 size_t off = ((size_t)b * HW + p) * C + (size_t)cc * 8;
@@ -112,24 +116,6 @@ __global__ __launch_bounds__(256) void k_gn_reduce(int HW, int C, int G, int pix
                         s1[e] += g; s2[e] += g * xh;
                     }
                     xc = xn; dc = dn; off += st;
-                }
-            }
-            for (; p < p1; p += rows) {
-                size_t off = ((size_t)b * HW + p) * C + (size_t)cc * 8;
-                V8<T> xv = V8<T>::load(x + off);
-                if (!BWD) {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) { float v = xv.get(e); s1[e] += v; s2[e] += v * v; }
-                } else {
-                    V8<T> dv = V8<T>::load(dy + off);
-#pragma unroll
-                    for (int e = 0; e < 8; e++) {
-                        float xh = (xv.get(e) - mu[e]) * rs[e];
-                        float g = dv.get(e);
-                        if (silu) g *= silu_grad(xh * ga[e] + be[e]);
-                        g *= ga[e];
-                        s1[e] += g; s2[e] += g * xh;
-                    }
                 }
             }
         }
@@ -325,7 +311,7 @@ __global__ __launch_bounds__(256) void k_gn_apply(int HW, int C, int G, int pix_
                                                   const float* __restrict__ bsums, const float* __restrict__ gamma,
                                                   const float* __restrict__ beta, int silu, float eps,
                                                   T* __restrict__ out, const float* __restrict__ partials, int pchunks,
-                                                  float* __restrict__ sums_out, const T* __restrict__ residual, int deep) {
+                                                  float* __restrict__ sums_out, const T* __restrict__ residual) {
     __shared__ float gstat[64 * 4];
     __shared__ float tot[128];
     const int b = blockIdx.y, tid = threadIdx.x;
@@ -378,7 +364,7 @@ __global__ __launch_bounds__(256) void k_gn_apply(int HW, int C, int G, int pix_
         int p = p0 + prow;
         if (!BWD) {
             // long pixel ranges: four independent loads in flight per thread (see k_gn_reduce)
-            for (; deep && p + 3 * rows < p1; p += 4 * rows) {
+            for (; p + 3 * rows < p1; p += 4 * rows) {
                 V8<T> xv[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) xv[u] = V8<T>::load(xp + u * step);
@@ -395,7 +381,7 @@ __global__ __launch_bounds__(256) void k_gn_apply(int HW, int C, int G, int pix_
                 xp += 4 * step; op += 4 * step;
             }
         } else {
-            for (; deep && p + rows < p1; p += 2 * rows) {
+            for (; p + rows < p1; p += 2 * rows) {
                 V8<T> xv[2], dv[2], rv[2];
 #pragma unroll
                 for (int u = 0; u < 2; u++) {
@@ -553,9 +539,6 @@ __global__ __launch_bounds__(256) void k_softmax_rows_bwd(int rows, int n, float
     for (int j = lane; j < n; j += 64) st1<T>(ds, j, scale * ld1<T>(p, j) * (dp[j] - dot));
 }
 
-// DWG_GN_SHALLOW=1: the round-2 loops (one load in flight per thread) -- A/B switch for the long-range paths
-static int gn_deep() { static const int v = getenv("DWG_GN_SHALLOW") ? 0 : 1; return v; }
-
 static int gn_geometry(int HW, int C, int G, int* pix_per_block, int* chunks, size_t* lds) {
     if (C % 8 || G <= 0 || G > 64 || C % G) return DWG_E_ARG;
     int ppb = HW / 256; if (ppb < 16) ppb = 16; if (ppb > 256) ppb = 256;
@@ -564,19 +547,16 @@ static int gn_geometry(int HW, int C, int G, int* pix_per_block, int* chunks, si
     return DWG_OK;
 }
 // reduction pass: ~64K elements per workgroup, at most GN_MAX_CHUNKS partials per image
-#define GN_MAX_CHUNKS_DEEP 2048     // 512^2 x 128-channel VAE tensors: 2048 workgroups of the statistics pass (8 per CU) keep HBM busy
-#define GN_MAX_CHUNKS (gn_deep() ? GN_MAX_CHUNKS_DEEP : 512)
+#define GN_MAX_CHUNKS 2048         // 512^2 x 128-channel VAE tensors: 2048 workgroups of the statistics pass (8 per CU) keep HBM busy
 #define GN_FOLD_MAX_CHUNKS 32      // up to this many partials per output the apply pass sums them itself (no finalize launch)
 static void gn_reduce_geometry(int HW, int C, int* pix_per_block, int* chunks) {
     long long ppb = 16384 / C; if (ppb < 8) ppb = 8;
-    // small images (the denoiser's <= 64x64 levels): at most DWG_GN_SMALL_CHUNKS partials per image, so that the apply pass can sum
-    // them itself and the finalize launch disappears (these layers are launch-latency-bound, not bandwidth-bound)
-    static const int small_chunks = getenv("DWG_GN_SMALL_CHUNKS") ? atoi(getenv("DWG_GN_SMALL_CHUNKS")) : 0;
-    if (small_chunks > 0 && HW <= 4096 && ppb * small_chunks < HW) ppb = (HW + small_chunks - 1) / small_chunks;
     int ch = (int)((HW + ppb - 1) / ppb);
     if (ch > GN_MAX_CHUNKS) { ch = GN_MAX_CHUNKS; ppb = (HW + ch - 1) / ch; ch = (int)((HW + ppb - 1) / ppb); }
     *pix_per_block = (int)ppb; *chunks = ch;
 }
+// finalize folded into the apply pass: few partials, and four threads per (group, statistic) fit one workgroup
+static bool gn_fold(int rchunks, int G) { return rchunks <= GN_FOLD_MAX_CHUNKS && 2 * G * 4 <= 256; }
 
 }  // namespace
 
@@ -592,7 +572,7 @@ static void gn_reduce_geometry(int HW, int C, int* pix_per_block, int* chunks) {
 
 extern "C" {
 
-size_t dwg_groupnorm_workspace_floats(int32_t B, int32_t G) { return (size_t)(B > 0 ? B : 1) * GN_MAX_CHUNKS_DEEP * (G > 0 ? G : 1) * 2; }
+size_t dwg_groupnorm_workspace_floats(int32_t B, int32_t G) { return (size_t)(B > 0 ? B : 1) * GN_MAX_CHUNKS * (G > 0 ? G : 1) * 2; }
 
 int dwg_groupnorm_forward_dt(int32_t dtype, int32_t B, int32_t HW, int32_t C, int32_t G, const void* x, const float* gamma, const float* beta,
                              float eps, int32_t fuse_silu, void* y, float* stats, float* workspace, dwg_stream_t stream_) {
@@ -606,17 +586,16 @@ int dwg_groupnorm_forward_dt(int32_t dtype, int32_t B, int32_t HW, int32_t C, in
     {
         // small images: one launch for the whole layer (k_gn_small) when a bundle of gb whole groups is a whole number of 16-byte chunks and
         // a workgroup's two walks over it stay short (<= 24 trips per thread)
-        static const bool no_small = getenv("DWG_GN_NO_SMALL") != nullptr;
         const int cg = C / G;
         int gb = 0;
         for (int c = 1; c <= 8 && !gb; c *= 2) if ((c * cg) % 8 == 0 && G % c == 0) gb = c;
-        static const int small_max = getenv("DWG_GN_SMALL_MAX") ? atoi(getenv("DWG_GN_SMALL_MAX")) : 6144;     // chunks per workgroup walk
+        const int small_max = 6144;     // chunks per workgroup walk
         // ... and only for the small batches it was built for (B <= 4, tensor <= 8 MB: L2-resident).  A bundle is an 80-240-byte slice of every
         // pixel row, so the walks touch partial cache lines that neighbouring bundles touch again -- free out of L2, several times the traffic
         // beyond it -- and with 8x the batch the three-launch path has all the parallelism it needs: the batched 8-view step (batch 16) fell
-        // from 92 to 68 views/s with this kernel on (A/B, DWG_GN_NO_SMALL), so it keeps the three-launch path
+        // from 92 to 68 views/s with this kernel on (A/B), so it keeps the three-launch path
         const long long tensor_bytes = (long long)B * HW * C * (dtype == DWG_DTYPE_F32 || dtype == DWG_DTYPE_F32X ? 4 : 2);
-        if (!no_small && gb && B <= 4 && HW <= 1024 && (long long)HW * (gb * cg / 8) <= small_max && gb * cg / 8 <= 64 && tensor_bytes <= (8ll << 20)) {
+        if (gb && B <= 4 && HW <= 1024 && (long long)HW * (gb * cg / 8) <= small_max && gb * cg / 8 <= 64 && tensor_bytes <= (8ll << 20)) {
             const int nb = gb * cg, tp = 256 / (nb / 8);
             const size_t sl = (size_t)(2 * tp * nb + 2 * nb) * sizeof(float);
             DWG_DT_SWITCH(dtype,
@@ -626,15 +605,14 @@ int dwg_groupnorm_forward_dt(int32_t dtype, int32_t B, int32_t HW, int32_t C, in
             return DWG_OK;
         }
     }
-    static const int fold_max = getenv("DWG_GN_FOLD") ? atoi(getenv("DWG_GN_FOLD")) : GN_FOLD_MAX_CHUNKS;
-    const bool fold = rchunks <= fold_max && 2 * G * 4 <= 256;     // finalize folded into the apply pass
+    const bool fold = gn_fold(rchunks, G);
     DWG_DT_SWITCH(dtype,
         DWG_LAUNCH("gn_stats", (k_gn_reduce<T, false>), dim3(rchunks, B), dim3(256), lds, stream, HW, C, G, rppb, (const T*)x,
-                   (const T*)nullptr, (const float*)nullptr, gamma, beta, 0, eps, workspace, gn_deep());
+                   (const T*)nullptr, (const float*)nullptr, gamma, beta, 0, eps, workspace);
         if (!fold) DWG_LAUNCH("gn_finalize", k_gn_finalize, dim3((2 * G + 3) / 4, B), dim3(256), 0, stream, rchunks, G, (const float*)workspace, stats);
         DWG_LAUNCH("gn_apply", (k_gn_apply<T, false>), dim3(chunks, B), dim3(256), 0, stream, HW, C, G, ppb, (const T*)x,
                    (const T*)nullptr, (const float*)stats, (const float*)nullptr, gamma, beta, fuse_silu, eps, (T*)y,
-                   fold ? (const float*)workspace : (const float*)nullptr, rchunks, stats, (const T*)nullptr, gn_deep()))
+                   fold ? (const float*)workspace : (const float*)nullptr, rchunks, stats, (const T*)nullptr))
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }
@@ -654,15 +632,14 @@ int dwg_groupnorm_backward_dt(int32_t dtype, int32_t B, int32_t HW, int32_t C, i
     int rppb, rchunks;
     gn_reduce_geometry(HW, C, &rppb, &rchunks);
     hipStream_t stream = (hipStream_t)stream_;
-    static const int fold_max = getenv("DWG_GN_FOLD") ? atoi(getenv("DWG_GN_FOLD")) : GN_FOLD_MAX_CHUNKS;
-    const bool fold = rchunks <= fold_max && 2 * G * 4 <= 256;
+    const bool fold = gn_fold(rchunks, G);
     DWG_DT_SWITCH(dtype,
         DWG_LAUNCH("gn_bwd_stats", (k_gn_reduce<T, true>), dim3(rchunks, B), dim3(256), lds, stream, HW, C, G, rppb, (const T*)x,
-                   (const T*)dy, stats, gamma, beta, fuse_silu, eps, workspace, gn_deep());
+                   (const T*)dy, stats, gamma, beta, fuse_silu, eps, workspace);
         if (!fold) DWG_LAUNCH("gn_finalize", k_gn_finalize, dim3((2 * G + 3) / 4, B), dim3(256), 0, stream, rchunks, G, (const float*)workspace, scratch);
         DWG_LAUNCH("gn_bwd_apply", (k_gn_apply<T, true>), dim3(chunks, B), dim3(256), 0, stream, HW, C, G, ppb, (const T*)x,
                    (const T*)dy, stats, (const float*)scratch, gamma, beta, fuse_silu, eps, (T*)dx,
-                   fold ? (const float*)workspace : (const float*)nullptr, rchunks, scratch, (const T*)residual, gn_deep()))
+                   fold ? (const float*)workspace : (const float*)nullptr, rchunks, scratch, (const T*)residual))
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

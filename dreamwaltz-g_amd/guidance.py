@@ -15,7 +15,6 @@ pipe.unet.config.sample_size.  Device RNG draw order per call is the reference's
 latent noise.  Test-only keyword extensions: noise=, posterior_noise= (fixed draws for parity tests).
 """
 import ctypes
-import os
 import types
 from typing import Dict, List, Optional, Union
 
@@ -45,12 +44,11 @@ def _st(t):
 
 
 def _fused_ok(*ts):
-    """The one-launch forms of the latent algebra (csrc/sds.hip, include/dwg_sds.h) take fp32 CUDA tensors; DWG_SDS_TORCH=1 keeps the
-    element-wise torch statements (experiments / A-B)."""
-    return not _SDS_TORCH and all(t is not None and t.is_cuda and t.dtype == torch.float32 for t in ts)
+    """The one-launch forms of the latent algebra (csrc/sds.hip, include/dwg_sds.h) take fp32 CUDA tensors; CPU and non-fp32
+    tensors keep the element-wise torch statements."""
+    return all(t is not None and t.is_cuda and t.dtype == torch.float32 for t in ts)
 
 
-_SDS_TORCH = os.environ.get("DWG_SDS_TORCH", "0") == "1"
 _WEIGHT_CODE = {None: 0, 'sjc': 0, 'dreamfusion': 1, 'latent-nerf': 2, 'ism': 3}
 
 
@@ -273,8 +271,7 @@ class ControlNetScoreDistillation:
         batch_size = inputs.size(0)
         prefetch = kwargs.pop('_prefetch', None)
         # (a step being captured into ONE graph keeps the prelude on the capturing stream, in front of the main plan: sd15.DenoiserPlan.run)
-        early = (prefetch is not None and inputs.is_cuda and inputs.size(1) == 3 and os.environ.get("DWG_DENOISER_PREFETCH", "1") != "0"
-                 and not torch.cuda.is_current_stream_capturing())
+        early = (prefetch is not None and inputs.is_cuda and inputs.size(1) == 3 and not torch.cuda.is_current_stream_capturing())
         if early and posterior_noise is None:
             shape = (batch_size, self.vae_cfg.latent_channels, self.latent_hw, self.latent_hw)
             posterior_noise = torch.randn(shape, device=inputs.device, dtype=inputs.dtype, generator=generator)        # RNG draw #1

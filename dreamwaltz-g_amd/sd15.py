@@ -332,7 +332,6 @@ class Plan:
                 raise RuntimeError("plan op failed with DWG error %s" % rc)
 
     def buf(self, *shape, dtype=None, zero=False):
-        import os
         dtype = self.dtype if dtype is None else dtype
         zero = zero or os.environ.get("DWG_PLAN_ZERO") == "1"
         t = (torch.zeros if zero else torch.empty)(*shape, device=self.device, dtype=dtype)
@@ -779,31 +778,20 @@ class Builder:
         launches of ~12 us each in the UNet, 7 in the ControlNet -> 1 + 1); a block's k and v are column slices of its output."""
         batches = self.__dict__.setdefault("_text_kv", {})
         key = text.data_ptr()
-        base = getattr(text, "_base", None)
-        if key not in batches and base is not None and base.data_ptr() in batches and batches[base.data_ptr()] is not None \
-                and base.dim() == text.dim() and base.shape[1:] == text.shape[1:] and text.is_contiguous():
-            # a batch-row slice of a text whose projections exist already (the halves of a split decoder; a prelude that ran on the whole
-            # batch): the same rows of that output
-            r0 = (text.data_ptr() - base.data_ptr()) // (base.stride(0) * base.element_size())
-            out, offs, _ = batches[base.data_ptr()]
-            batches[key] = (out[r0:r0 + text.shape[0]], offs, text)
         if key not in batches:
-            if os.environ.get("DWG_TEXT_KV_PER_BLOCK") == "1":           # experiment switch: the round-1 schedule
-                batches[key] = None
-            else:
-                suffix = ".attn2.to_k.weight"
-                blocks = sorted(n[:-len(suffix)] for n in self.w.sd if n.endswith(suffix) and self.w.sd[n].shape[1] == text.shape[-1])
-                names = []
-                for b_ in blocks:
-                    names += [b_ + ".attn2.to_k", b_ + ".attn2.to_v"]
-                out = self.linear(text, self.w.lin(*names), tag="attn_kv")
-                offs, o = {}, 0
-                for b_ in blocks:
-                    c = int(self.w.sd[b_ + suffix].shape[0])
-                    offs[b_] = (o, c); o += 2 * c
-                batches[key] = (out, offs, text)
+            suffix = ".attn2.to_k.weight"
+            blocks = sorted(n[:-len(suffix)] for n in self.w.sd if n.endswith(suffix) and self.w.sd[n].shape[1] == text.shape[-1])
+            names = []
+            for b_ in blocks:
+                names += [b_ + ".attn2.to_k", b_ + ".attn2.to_v"]
+            out = self.linear(text, self.w.lin(*names), tag="attn_kv")
+            offs, o = {}, 0
+            for b_ in blocks:
+                c = int(self.w.sd[b_ + suffix].shape[0])
+                offs[b_] = (o, c); o += 2 * c
+            batches[key] = (out, offs, text)
         ent = batches[key]
-        if ent is None or t not in ent[1]:
+        if t not in ent[1]:
             return self.linear(text, self.w.lin(t + ".attn2.to_k", t + ".attn2.to_v"), tag="attn_kv")
         o, c = ent[1][t]
         return ent[0][..., o:o + 2 * c]
@@ -929,44 +917,19 @@ class DenoiserPlan:
         for i in range(len(cfg.block_out_channels)):
             for j in range(cfg.layers_per_block + 1):
                 up_names.append("up_blocks.%d.resnets.%d" % (i, j))
-        # ---- ControlNet body on branch 1: hint embedding (batch 1) + its own encoder.  It only shares INPUTS with the UNet
-        # encoder, and below 64x64 neither fills the chip alone, so the two run as parallel paths (side stream / graph branch).
-        import os
-        par = os.environ.get("DWG_SERIAL_DENOISER") != "1"
-        # DWG_DENOISER_SPLIT: 0 (default) = every chain on the whole CFG batch; 1 = the DECODER split by batch half -- it is ONE chain, and its
-        # memory-bound layers (GroupNorm, LayerNorm, split-K reduces) otherwise have nothing to run under: the halves are two independent
-        # chains (side stream / graph branch) with half the rows per launch; 2 = the encoders split by half as well (four chains).
-        # Measured (DESIGN.md "Measured (round 6)"): 1 is 0.9 % faster per step (25.58 -> 25.35 ms) at 18 % more launches, each of them a less
-        # efficient half-batch launch (kernel time summed over the step 26.8 -> 28.9 ms) -- wall time is bought with chip time, so it stays opt-in
-        split = int(os.environ.get("DWG_DENOISER_SPLIT", "0")) if (par and B % 2 == 0) else 0
-        if split >= 2 and self.views != 1:
-            split = 1                                   # (the four-chain form shares ONE view's hint embedding between the halves)
         nb = len(cfg.block_out_channels)
 
-        class _Rows:
-            """A _TimeEmbed seen through a slice of the batch rows."""
-            def __init__(self, temb, rows):
-                self.temb, self.rows = temb, rows
-
-            def bias_for(self, name):
-                tb, ld = self.temb.bias_for(name)
-                return (tb[self.rows], ld)
-
-        def decoder(h, skips, rows, first=0, last=None):
-            """up blocks first .. last - 1 on the batch rows `rows` (+ the output convolution when the last block is included)"""
-            last = nb if last is None else last
+        def decoder(h, skips):
+            """the up blocks and the output convolution"""
             skips = list(skips)
-            tu = _Rows(self.temb_u, rows)
-            for i in range(first, last):
+            for i in range(nb):
                 for j in range(cfg.layers_per_block + 1):
                     pre = "up_blocks.%d.resnets.%d" % (i, j)
-                    h = bu.resnet(bu.cat(h, skips.pop()), pre, tu.bias_for(pre))
+                    h = bu.resnet(bu.cat(h, skips.pop()), pre, self.temb_u.bias_for(pre))
                     if rev_attn[i]:
-                        h = bu.transformer(h, "up_blocks.%d.attentions.%d" % (i, j), self.text[rows], cfg.heads)
+                        h = bu.transformer(h, "up_blocks.%d.attentions.%d" % (i, j), self.text, cfg.heads)
                 if i != nb - 1:
                     h = bu.conv(h, "up_blocks.%d.upsamplers.0.conv" % i, upsample=2)
-            if last < nb:
-                return h, skips
             n = bu.groupnorm(h, "conv_norm_out", 1e-5, True)
             return bu.conv(n, "conv_out", out_dtype=torch.float32)
 
@@ -981,8 +944,6 @@ class DenoiserPlan:
             for k in range(2 * (len(cfg.cond_channels) - 1)):
                 hnt = b_.conv(hnt, "%s.blocks.%d" % (e, k), stride=2 if k % 2 == 1 else 1, act="silu")
             return b_.conv(hnt, e + ".conv_out")
-        self.eps_halves = None
-        whole = slice(0, B)
         # ---- the prelude plan: two independent chains (ControlNet side / UNet side)
         suffix = ".attn2.to_k"
         first_block = lambda w_: sorted(n[:-len(suffix + ".weight")] for n in w_.sd if n.endswith(suffix + ".weight"))[0]     # noqa: E731
@@ -996,49 +957,18 @@ class DenoiserPlan:
         self.pre.join(1)
         bu.__dict__["_text_kv"] = pu.__dict__["_text_kv"]       # the main plan's cross-attentions read the prelude's projections
         bc.__dict__["_text_kv"] = pc.__dict__["_text_kv"]
-        if split < 2:
-            if par:
-                p.fork(1)
-            with p.on_branch(1 if par else 0):
-                cskips, cmid = _build_encoder(bc, cfg, self.latents, self.temb_c, self.text, hint=hnt)
-            skips, mid = _build_encoder(bu, cfg, self.latents, self.temb_u, self.text)
-            if par:
-                p.join(1)
-            skips, h = zero_convs(cskips, cmid, skips, mid)
-            if split == 1:
-                # the low-resolution up blocks stay on the whole batch: their launches are bound by the WEIGHTS they stream (59 - 118 MB per
-                # 3 x 3 convolution of the 1280-channel levels), which two half-batch chains would read twice
-                first = min(nb - 1, max(0, int(os.environ.get("DWG_DECODER_SPLIT_FROM", "2"))))
-                if first > 0:
-                    h, skips = decoder(h, skips, whole, 0, first)
-                lo, hi = slice(0, B // 2), slice(B // 2, B)
-                p.fork(1)
-                with p.on_branch(1):
-                    e1 = decoder(h[hi], [t[hi] for t in skips], hi, first)
-                e0 = decoder(h[lo], [t[lo] for t in skips], lo, first)
-                p.join(1)
-                self.eps_halves, self.eps = (e0, e1), None
-            else:
-                self.eps = decoder(h, skips, whole)
-        else:
-            # four encoder chains (UNet / ControlNet x batch half), then one zero-convolution + decoder chain per half
-            lo, hi = slice(0, B // 2), slice(B // 2, B)
-            for br in (1, 2, 3):
-                p.fork(br)
-            enc = {}
-            for br, (bld, w_, temb, rows, hint) in {0: (bu, wu, self.temb_u, lo, None), 1: (bc, wc, self.temb_c, lo, hnt),
-                                                    2: (bu, wu, self.temb_u, hi, None), 3: (bc, wc, self.temb_c, hi, hnt)}.items():
-                with p.on_branch(br):
-                    enc[br] = _build_encoder(bld, cfg, self.latents[rows], _Rows(temb, rows), self.text[rows], hint=hint)
-            p.join(1)                                   # the lower half's chain (branch 0) needs its ControlNet encoder
-            p.ops.append(("fork", 3, 2))                # ... and the upper half's (branch 2) its own
-            outs = {}
-            for br, cn, rows in ((2, 3, hi), (0, 1, lo)):
-                with p.on_branch(br):
-                    sk, hh = zero_convs(enc[cn][0], enc[cn][1], enc[br][0], enc[br][1])
-                    outs[br] = decoder(hh, sk, rows)
-            p.join(2)
-            self.eps_halves, self.eps = (outs[0], outs[2]), None
+        # ---- ControlNet body on branch 1: hint embedding (batch 1) + its own encoder.  It only shares INPUTS with the UNet
+        # encoder, and below 64x64 neither fills the chip alone, so the two run as parallel paths (side stream / graph branch).
+        # Every chain runs on the whole CFG batch: splitting the decoder by batch half into two parallel chains measured 0.9 % faster per
+        # step (25.58 -> 25.35 ms) at 18 % more launches, each a less efficient half-batch launch (kernel time summed over the step
+        # 26.8 -> 28.9 ms) -- wall time bought with chip time (DESIGN.md "Measured (round 6)")
+        p.fork(1)
+        with p.on_branch(1):
+            cskips, cmid = _build_encoder(bc, cfg, self.latents, self.temb_c, self.text, hint=hnt)
+        skips, mid = _build_encoder(bu, cfg, self.latents, self.temb_u, self.text)
+        p.join(1)
+        skips, h = zero_convs(cskips, cmid, skips, mid)
+        self.eps = decoder(h, skips)
 
     def _store_prelude_inputs(self, t, text, cond_nchw):
         p = self.plan
@@ -1097,8 +1027,6 @@ class DenoiserPlan:
             self.pre.run()
         self._pre_ready, self._pre_event = False, None
         self.plan.run()
-        if self.eps_halves is not None:
-            return torch.cat(self.eps_halves, dim=0).permute(0, 3, 1, 2)
         return self.eps.permute(0, 3, 1, 2)   # [B,4,h,w] view (fp32)
 
 
@@ -1151,11 +1079,7 @@ class VAEEncoderPlan:
                 name = "encoder.down_blocks.%d.downsamplers.0.conv" % i
                 Hin = h.shape[1]
                 h = f.conv(h, name, stride=2, pad=0, out_hw=(Hin // 2, Hin // 2))      # F.pad(0,1,0,1) + conv stride 2
-                if os.environ.get("DWG_VAE_DILATED_DGRAD") == "1":     # zero-dilated input, all 9 taps: 4x the multiply-adds
-                    tape.append(lambda d, name=name, Hin=Hin: r.conv(d, None, weight=w.conv(name, True), bias=False, stride=1,
-                                                                     pad_tl=(2, 2), out_hw=(Hin, Hin), in_dilation=2))
-                else:
-                    tape.append(lambda d, name=name: r.conv_dgrad_s2(d, name))
+                tape.append(lambda d, name=name: r.conv_dgrad_s2(d, name))
         h = resnet_f(h, "encoder.mid_block.resnets.0")
         h = self._attention(f, r, w, h, "encoder.mid_block.attentions.0", tape)
         h = resnet_f(h, "encoder.mid_block.resnets.1")
@@ -1269,11 +1193,10 @@ class VAEEncoderPlan:
 
     def _fused_io(self, t):
         """f32x plans: the boundary conversions (2 v - 1 + NHWC + pack; max |g| + power-of-two pre-scale + NHWC + pack; unpack + NCHW + scale
-        back) are one HIP launch each instead of 4 / ~14 / 3 element-wise torch launches (DWG_VAE_FUSED_IO=0: the torch statements)."""
+        back) are one HIP launch each instead of 4 / ~14 / 3 element-wise torch launches; other inputs take the torch statements."""
         image = t.dim() == 4 and t.shape[1] == 3 and tuple(t.shape[-2:]) == (self.hw, self.hw)
         grad = t.dim() == 4 and t.shape[1] == 8 and tuple(t.shape[-2:]) == tuple(self.moments.shape[1:3])
-        return (self.fwd.is_x and t.is_cuda and t.dtype == torch.float32 and (image or grad) and t.shape[0] == self.B
-                and os.environ.get("DWG_VAE_FUSED_IO", "1") != "0")
+        return self.fwd.is_x and t.is_cuda and t.dtype == torch.float32 and (image or grad) and t.shape[0] == self.B
 
     # the backward pass is LINEAR in the incoming gradient: it is run on 2^k x the gradient, k chosen on the device so that max |g| lands in
     # [GRAD_TARGET / 2, GRAD_TARGET], and the result is scaled back by 2^-k -- both exact.  Without it the 16-bit storage types see the
@@ -1287,10 +1210,9 @@ class VAEEncoderPlan:
         g = dmoments_nchw
         if self._fused_io(g):
             g = g.detach().contiguous()
-            prescale = os.environ.get("DWG_VAE_GRAD_PRESCALE", "1") != "0"
             inv = torch.empty(1, device=self.device, dtype=torch.float32)
             h, w_ = int(self.moments.shape[1]), int(self.moments.shape[2])
-            _lib.check(self.bwd._lib.dwg_vae_grad_prescale_pack(self.B, h * w_, _lib.ptr(g), float(self.GRAD_TARGET if prescale else 0.0),
+            _lib.check(self.bwd._lib.dwg_vae_grad_prescale_pack(self.B, h * w_, _lib.ptr(g), self.GRAD_TARGET,
                                                                 _lib.ptr(self.dmoments), _lib.ptr(inv), self._st()), "dwg_vae_grad_prescale_pack")
             self.bwd.run()
             out = torch.empty(self.B, 3, self.hw, self.hw, device=self.device, dtype=torch.float32)
@@ -1298,7 +1220,7 @@ class VAEEncoderPlan:
                        "dwg_vae_dx_unpack")
             return out
         inv = None
-        if self.bwd.dtype_name in ("f32x", "f16") and os.environ.get("DWG_VAE_GRAD_PRESCALE", "1") != "0":
+        if self.bwd.dtype_name in ("f32x", "f16"):
             amax = g.detach().abs().amax()
             k = torch.floor(torch.log2(self.GRAD_TARGET / amax.clamp_min(1e-30))).clamp(-60.0, 100.0)
             k = torch.where(amax > 0, k, torch.zeros_like(k))

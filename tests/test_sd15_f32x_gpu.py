@@ -115,12 +115,14 @@ def test_f32x_transformer_block(c, hw):
 
 
 def test_f32x_attention_kernel_alone_long_and_ragged():
-    """The fused kernel against softmax(QK^T/sqrt(d))V in float64: 4096 keys at d = 40 (the 64x64 level), ragged 77 keys, d = 80 / 160."""
+    """The fused kernel against softmax(QK^T/sqrt(d))V in float64: 4096 keys at d = 40 (the 64x64 level), ragged 77 keys, d = 80 / 160; the
+    64-key-tile kernel of d = 40 / 80 with a masked tail tile at d = 80 and a ragged last query block, and with one tile that is also the tail."""
     import ctypes
     from dreamwaltz_g_amd import _lib, xfmt
     L = _lib.lib()
     worst = {}
-    for (Bn, Hh, Nq, Nk, d) in [(1, 8, 4096, 4096, 40), (2, 8, 300, 77, 40), (2, 8, 1024, 1024, 80), (2, 8, 256, 77, 160), (1, 2, 64, 64, 160)]:
+    for (Bn, Hh, Nq, Nk, d) in [(1, 8, 4096, 4096, 40), (2, 8, 300, 77, 40), (2, 8, 1024, 1024, 80), (2, 8, 256, 77, 160), (1, 2, 64, 64, 160),
+                                (1, 2, 130, 77, 80), (1, 2, 40, 33, 40)]:
         g = torch.Generator().manual_seed(Nq + d)
         q = torch.randn(Bn, Nq, Hh * d, generator=g); k = torch.randn(Bn, Nk, Hh * d, generator=g); v = torch.randn(Bn, Nk, Hh * d, generator=g)
         qx, kx, vx = xfmt.pack(q).cuda(), xfmt.pack(k).cuda(), xfmt.pack(v).cuda()

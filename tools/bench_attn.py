@@ -1,4 +1,4 @@
-"""Times the fused f32x attention at the step's shapes (HIP events over a captured chain of launches):  DWG_ATTN_V2=0|1 python tools/bench_attn.py
+"""Times the fused f32x attention at the step's shapes (HIP events over a captured chain of launches):  python tools/bench_attn.py
 Prints  B H Nq Nk d  us  TF/s (algorithmic: 4 B H Nq Nk d flops)  and the rel-L2 error against float64 of the first (small) case."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
