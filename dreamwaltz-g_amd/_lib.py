@@ -98,6 +98,15 @@ SIGNATURES = {
     "dwg_nerf_field_backward_workspace_bytes": (_sz, [ctypes.POINTER(NerfFieldDescC), ctypes.c_uint64]),
     "dwg_nerf_field_backward": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _vp, _vp,
                                                ctypes.POINTER(NerfFieldGradsC), _vp, _sz, _vp]),
+    # include/dwg_pointcloud.h
+    "dwg_pc_lattice_sigma": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "dwg_pc_select_workspace_bytes": (_sz, [ctypes.c_uint64]),
+    "dwg_pc_select_above": (ctypes.c_int, [ctypes.c_uint64, _vp, _f32, _vp, ctypes.c_uint64, _vp, _vp, _sz, _vp]),
+    "dwg_pc_select_flags": (ctypes.c_int, [ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _vp, _vp, _sz, _vp]),
+    "dwg_pc_lattice_points": (ctypes.c_int, [ctypes.c_uint64, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "dwg_pc_fd_points": (ctypes.c_int, [ctypes.c_uint64, _vp, _f32, _f32, _vp, _vp]),
+    "dwg_pc_finish": (ctypes.c_int, [ctypes.c_uint64, _u32, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "dwg_pc_outside_boxes": (ctypes.c_int, [ctypes.c_uint64, _vp, _u32, _vp, _vp, _vp]),
     # include/dwg_background.h
     "dwg_video_composite_forward": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "dwg_video_composite_backward": (ctypes.c_int, [_i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -468,7 +468,8 @@ class DreamWaltzG(nn.Module):
         threshold x 10); LBS weights interpolated from lbs_model.lbs_weights and smoothed as cfg.render.lbs_weight_smooth[_K, _N] say;
         inverse LBS of the points under the canonical transforms; scales init_scale, identity quaternions.  The learn_* flags, init_offset /
         init_scale / max_scale and nerf.bound come from cfg when given (the constructor's defaults otherwise); **learn_flags (any keyword of
-        the constructor) override them.  `nearest_triangles_buffer` stays on the object, on the points' device."""
+        the constructor) override them.  `nearest_triangles_buffer` stays on the object, on the points' device.
+        `pointcloud.export_point_cloud(...).points` (B12) is such a tensor: it feeds this constructor without a host round trip."""
         from . import avatar_init as ai
         r = getattr(cfg, "render", None)
         mesh = dict(mesh_binding_gaussians or {})

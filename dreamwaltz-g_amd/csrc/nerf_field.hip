@@ -14,7 +14,9 @@
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_gridenc.h"
 #include "../../include/dwg_nerf.h"
+#include "../../include/dwg_pointcloud.h"
 #include "gridenc_common.h"
+#include "pointcloud_index.h"
 
 namespace {
 
@@ -112,13 +114,30 @@ __device__ void load_weights(const NfP& p, T* lds, float* bias) {
 }
 
 
+// Where a tile's x comes from: component i (0 .. 3 NF_TILE - 1) of the tile that starts at point p0.
+struct XPoints {                            // x [M, 3] in memory
+    const float* __restrict__ x;
+    __device__ __forceinline__ float operator()(uint64_t p0, uint32_t i) const { return x[p0 * 3 + i]; }
+};
+struct XLattice {                           // the lattice of dwg_pointcloud.h: flat index -> chunk -> (ix, iy, iz) -> the axis tables
+    PcLattice l;
+    const float* __restrict__ ax;
+    const float* __restrict__ ay;
+    const float* __restrict__ az;
+    __device__ __forceinline__ float operator()(uint64_t p0, uint32_t i) const {
+        const uint32_t pt = i / 3u, k = i - 3u * pt;
+        uint32_t ix, iy, iz;
+        pc_lattice_decode(l, (uint32_t)p0 + pt, ix, iy, iz);
+        return k == 0 ? ax[ix] : k == 1 ? ay[iy] : az[iz];
+    }
+};
+
 // x of the tile -> sx, the encoder's (x + bound) / (2 bound) -> sxn, the 64 x L lookups -> enc, then the layers; points at or past
 // `mend` are encoded from x = 0 (their outputs are never stored).  Ends with a barrier: every layer output is in LDS.
-template <typename T>
-__device__ void field_tile(const NfP& p, const float* __restrict__ x, uint64_t mend, uint64_t p0, T* lds, const float* bias, float* sx,
-                           float* sxn) {
+template <typename T, typename XS>
+__device__ void field_tile(const NfP& p, const XS& x, uint64_t mend, uint64_t p0, T* lds, const float* bias, float* sx, float* sxn) {
     for (uint32_t i = threadIdx.x; i < NF_TILE * 3; i += 256) {
-        const float v = p0 + i / 3 < mend ? x[p0 * 3 + i] : 0.f;
+        const float v = p0 + i / 3 < mend ? x(p0, i) : 0.f;
         sx[i] = v;
         sxn[i] = (v + p.bound) * p.inv2b;       // torch evaluates the division by the Python scalar 2 bound as a product with its inverse
     }
@@ -179,6 +198,13 @@ __device__ __forceinline__ void lds_carve(const NfP& p, unsigned char* smem, T*&
     red = sxn + NF_TILE * 3;
 }
 
+// density of a point from the last layer's first output h0 (es = exp(sigma_scale), read by `scaling` only)
+__device__ __forceinline__ float nf_sigma(const NfP& p, float h0, const float* x, float es) {
+    if (p.raw) return h0;
+    const float xv = h0 + nf_prior(p, x[0], x[1], x[2]);
+    return p.act == 0 ? expf(xv) : p.act == 1 ? nf_softplus(xv) : nf_softplus(xv * es - 1.f);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_nf_fwd(NfP p, const float* __restrict__ x, uint64_t M, uint64_t ntiles, float* __restrict__ sigma,
                                                 T* __restrict__ albedo) {
@@ -190,18 +216,12 @@ __global__ __launch_bounds__(256) void k_nf_fwd(NfP p, const float* __restrict__
     const uint32_t W = p.W;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t p0 = tile * NF_TILE;
-        field_tile(p, x, M, p0, lds, bias, sx, sxn);
+        field_tile(p, XPoints{x}, M, p0, lds, bias, sx, sxn);
         const uint32_t t = threadIdx.x;
         if (t < NF_TILE && p0 + t < M) {
             const uint64_t pt = p0 + t;
             const T* o = lds + p.aoff[p.nl] + t * p.ast[p.nl];
-            const float h0 = (float)o[0];
-            float s = h0;
-            if (!p.raw) {
-                const float xv = h0 + nf_prior(p, sx[3 * t], sx[3 * t + 1], sx[3 * t + 2]);
-                s = p.act == 0 ? expf(xv) : p.act == 1 ? nf_softplus(xv) : nf_softplus(xv * es - 1.f);
-            }
-            sigma[pt] = s;
+            sigma[pt] = nf_sigma(p, (float)o[0], sx + 3 * t, es);
             T* a = albedo + pt * (W - 1u);
             for (uint32_t c = 1; c < W; c++) {
                 float v = (float)o[c];
@@ -210,6 +230,40 @@ __global__ __launch_bounds__(256) void k_nf_fwd(NfP p, const float* __restrict__
             }
         }
         __syncthreads();
+    }
+}
+
+// Density only, at the points of a lattice (dwg_pc_lattice_sigma): k_nf_fwd with the tile's x staged from the axis tables and without the
+// albedo.  minmax [DWG_PC_MINMAX_PAIRS][2]: this workgroup's (min, max) of the densities it wrote (NaN skipped), and (+inf, -inf) in the
+// pairs no workgroup owns (gridDim.x <= DWG_PC_MINMAX_PAIRS).
+template <typename T>
+__global__ __launch_bounds__(256) void k_nf_lattice(NfP p, XLattice x, uint64_t M, uint64_t ntiles, float* __restrict__ sigma,
+                                                    float* __restrict__ minmax) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* lds; float *bias, *sx, *sxn, *red;
+    lds_carve(p, smem, lds, bias, sx, sxn, red);
+    load_weights(p, lds, bias);
+    const float es = p.act == 2 ? expf(*p.sigma_scale) : 0.f;
+    float lo = INFINITY, hi = -INFINITY;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t p0 = tile * NF_TILE;
+        field_tile(p, x, M, p0, lds, bias, sx, sxn);
+        const uint32_t t = threadIdx.x;
+        if (t < NF_TILE && p0 + t < M) {
+            const T* o = lds + p.aoff[p.nl] + t * p.ast[p.nl];
+            const float s = nf_sigma(p, (float)o[0], sx + 3 * t, es);
+            sigma[p0 + t] = s;
+            lo = fminf(lo, s); hi = fmaxf(hi, s);
+        }
+        __syncthreads();
+    }
+    // the tile loop ended with a barrier: sx / sxn are free
+    if (threadIdx.x < NF_TILE) { sx[threadIdx.x] = lo; sxn[threadIdx.x] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < NF_TILE; i++) { lo = fminf(lo, sx[i]); hi = fmaxf(hi, sxn[i]); }
+        minmax[2u * blockIdx.x] = lo; minmax[2u * blockIdx.x + 1u] = hi;
+        for (uint32_t j = blockIdx.x + gridDim.x; j < (uint32_t)DWG_PC_MINMAX_PAIRS; j += gridDim.x) { minmax[2u * j] = INFINITY; minmax[2u * j + 1u] = -INFINITY; }
     }
 }
 
@@ -241,7 +295,7 @@ __global__ __launch_bounds__(256) void k_nf_bwd(NfP p, const float* __restrict__
     float acc_b = 0.f, acc_s = 0.f;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t p0 = m0 + tile * NF_TILE;
-        field_tile(p, x, mend, p0, lds, bias, sx, sxn);
+        field_tile(p, XPoints{x}, mend, p0, lds, bias, sx, sxn);
         // d(last layer output), rounded to the operand type where autograd hands the reference an fp16 gradient
         if (threadIdx.x < NF_TILE) {
             const uint32_t t = threadIdx.x;
@@ -522,6 +576,32 @@ int dwg_nerf_field_backward(const dwg_nerf_field_desc* desc, const float* x, uin
         DWG_LAUNCH("nerf_field_wgrad_reduce", k_nf_reduce, dim3((p.P + 255u) / 256u), dim3(256), 0, st, p, G, (const float*)partial, *grads);
         DWG_RETURN_IF_LAUNCH_FAILED();
     }
+    return DWG_OK;
+}
+
+int dwg_pc_lattice_sigma(const dwg_nerf_field_desc* desc, const float* ax, const float* ay, const float* az, uint32_t nx, uint32_t ny,
+                         uint32_t nz, uint32_t split, float* sigma, float* minmax, dwg_stream_t stream) {
+    NfP p;
+    size_t lds = 0;
+    int rc = make_params(desc, p, lds);
+    if (rc) return rc;
+    if (desc->raw || split == 0) return DWG_E_ARG;
+    const uint64_t M = (uint64_t)nx * ny * nz;
+    if (M == 0) return DWG_OK;
+    if ((uint64_t)nx * ny >= (1ull << 32) || M >= (1ull << 32)) return DWG_E_ARG;
+    if (!ax || !ay || !az || !sigma || !minmax) return DWG_E_ARG;
+    const uint64_t ntiles = (M + NF_TILE - 1) / NF_TILE;
+    const unsigned grid = (unsigned)(ntiles < DWG_PC_MINMAX_PAIRS ? ntiles : DWG_PC_MINMAX_PAIRS);
+    const XLattice x{pc_lattice(nx, ny, nz, split), ax, ay, az};
+    hipStream_t st = (hipStream_t)stream;
+    if (desc->precision) {
+        static bool attr = false; lds_opt_in(&k_nf_lattice<_Float16>, attr);
+        DWG_LAUNCH("pc_lattice_sigma", k_nf_lattice<_Float16>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, sigma, minmax);
+    } else {
+        static bool attr = false; lds_opt_in(&k_nf_lattice<float>, attr);
+        DWG_LAUNCH("pc_lattice_sigma", k_nf_lattice<float>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, sigma, minmax);
+    }
+    DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }
 

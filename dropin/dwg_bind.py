@@ -39,6 +39,15 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              time, so build_gaussian_avatar, reset_by_state_dict and the module's other knn_points callers
                                              reach them; the results come back in the reference's containers, dtypes and placements.
                                              Without a HIP device the originals run.  DWG_BIND_INIT=0: nothing is bound
+  B12 core.nerf.to_point_cloud.export_point_cloud (to_point_cloud.py:27-92) and remove_points_inside_bboxes (:95-114), both resolved at
+      call time by Trainer.init_gaussian_model (trainer.py:544)  -> dreamwaltz_g_amd.pointcloud: the density of the fused field (B7's
+                                             kernel) once per lattice point, an ordered on-device selection, and albedo + the six
+                                             finite-difference evaluations for the survivors only, instead of seven evaluations of every
+                                             lattice point, four host copies per chunk and a Python loop over the points.  The export
+                                             wrapper runs the reference's own preamble on the reference's network (update_extra_state,
+                                             the resolution and threshold defaults), returns the reference's BasicPointCloud (float64
+                                             numpy) and logs its two lines.  Without a HIP device, for a network B7 does not cover or with
+                                             CPU parameters the originals run.  DWG_BIND_POINTCLOUD=0: nothing is bound
   B5  core.system.scene.build_scene (scene.py:224-245)                -> dreamwaltz_g_amd.scene.Scene around that avatar (same forward /
                                              state_dict / avatar.get_optimizer surface the Trainer uses: trainer.py:578-604,680-709,859-890).
                                              `--render.use_video_background`: the reference's VideoBackground decodes the video, and
@@ -51,6 +60,7 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
 
 Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's field network (B7) on the reference path
              DWG_BIND_INIT = 0                        leave the avatar constructor's geometry (B11) on the reference path (igl + pytorch3d)
+             DWG_BIND_POINTCLOUD = 0                  leave the NeRF-to-Gaussian point-cloud export (B12) on the reference path
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
              DWG_BIND_PRETRAIN = 0                    leave Trainer.pretrain_forward (B9) on the reference path (numpy on the host)
              DWG_BIND_DTYPE = f32x | f32 | f16 | bf16  storage type of the denoiser / VAE plans.  Unset: the precision the reference loaded its
@@ -219,6 +229,80 @@ def _patch_nerf_module(mod):
     setattr(build_NeRFNetwork, _PATCHED, True)
     build_NeRFNetwork.__wrapped__ = orig
     mod.build_NeRFNetwork = build_NeRFNetwork
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# B12: the point-cloud export between the NeRF and the Gaussian stage
+# --------------------------------------------------------------------------------------------------------------------------------------
+def _export_covered(net):
+    """The native export takes this network: a HIP device, a field B7 covers, parameters on the device."""
+    if _hip_device() is None:
+        return False
+    _pkg()
+    from dreamwaltz_g_amd import nerf
+    if nerf.unbound_reason(net) is not None:
+        return False
+    return all(p.is_cuda for p in net.parameters())
+
+
+def _patch_pointcloud_module(mod):
+    if os.environ.get("DWG_BIND_POINTCLOUD", "1") == "0":
+        return
+    import functools
+    orig_export, orig_remove = mod.export_point_cloud, mod.remove_points_inside_bboxes
+    if getattr(orig_export, _PATCHED, False):
+        return
+
+    @functools.wraps(orig_export)
+    def export_point_cloud(self, resolution=None, split_size=128, density_thresh=None):
+        if not _export_covered(self):
+            return orig_export(self, resolution=resolution, split_size=split_size, density_thresh=density_thresh)
+        import numpy as np
+        import torch
+        from dreamwaltz_g_amd import pointcloud
+        with torch.inference_mode():                        # the reference's decorator
+            return _export(self, resolution, split_size, density_thresh, np, pointcloud)
+
+    def _export(self, resolution, split_size, density_thresh, np, pointcloud):
+        logger = mod.logger
+        logger.info(f'Extracting point cloud from NeRF...')
+        # the reference's preamble on the reference's object (to_point_cloud.py:32-46)
+        self.update_extra_state()
+        if resolution is None:
+            resolution = self.grid_size
+        if density_thresh is None:
+            if self.cuda_ray:
+                density_thresh = min(self.mean_density, self.density_thresh) \
+                    if np.greater(self.mean_density, 0) else self.density_thresh
+            else:
+                density_thresh = self.density_thresh
+        if self.density_activation == 'softplus':          # as the reference reads: on _NeRFNetwork a function against a string, False
+            density_thresh = density_thresh * 25
+        native = pointcloud.export_point_cloud_from(self, resolution=resolution, split_size=split_size, density_thresh=density_thresh)
+        pc = native.to_basic(mod.BasicPointCloud)
+        min_density = min(self.max_density, native.info["min_density"])
+        max_density = max(0.0, native.info["max_density"])
+        logger.info(f'Extracting point cloud done! Obtain {pc.points.shape[0]} points!')
+        logger.info(f'    density thresh: {density_thresh} ({min_density} ~ {max_density})')
+        return pc
+
+    @functools.wraps(orig_remove)
+    def remove_points_inside_bboxes(point_cloud, bboxes):
+        if _hip_device() is None:
+            return orig_remove(point_cloud, bboxes)
+        _pkg()
+        from dreamwaltz_g_amd import pointcloud
+        try:
+            pointcloud.parse_boxes(bboxes)
+            return pointcloud.remove_points_inside_bboxes(point_cloud, bboxes)
+        except TypeError:                                   # a nesting or point values the device test does not take: the reference's loop
+            return orig_remove(point_cloud, bboxes)
+
+    for f, orig in ((export_point_cloud, orig_export), (remove_points_inside_bboxes, orig_remove)):
+        setattr(f, _PATCHED, True)
+        f.__wrapped__ = orig
+    mod.export_point_cloud = export_point_cloud
+    mod.remove_points_inside_bboxes = remove_points_inside_bboxes
 
 
 # --------------------------------------------------------------------------------------------------------------------------------------
@@ -437,7 +521,7 @@ def _patch_guidance_module(mod):
 # --------------------------------------------------------------------------------------------------------------------------------------
 HOOKS = {"core.system.avatar": _patch_avatar_hooks, "core.system.scene": _patch_scene_module,
          "core.guidance.controlnet": _patch_guidance_module, "core.nerf.nerf_model": _patch_nerf_module,
-         "core.trainer": _patch_trainer_module}
+         "core.trainer": _patch_trainer_module, "core.nerf.to_point_cloud": _patch_pointcloud_module}
 
 
 class _HookLoader(importlib.abc.Loader):
@@ -498,7 +582,8 @@ def uninstall():
         mod = sys.modules.get(name)
         if mod is None:
             continue
-        for attr in ("build_gaussian_avatar", "build_scene", "build_NeRFNetwork", "find_nearest_triangles", "knn_points"):
+        for attr in ("build_gaussian_avatar", "build_scene", "build_NeRFNetwork", "find_nearest_triangles", "knn_points", "export_point_cloud",
+                     "remove_points_inside_bboxes"):
             f = getattr(mod, attr, None)
             if f is not None and getattr(f, _PATCHED, False):
                 setattr(mod, attr, f.__wrapped__)
