@@ -69,7 +69,6 @@ struct Params {
     int64_t in_stride;                  // ... per-Gaussian input rows, in Gaussians (0: every frame reads the same rows)
     int64_t cam_stride;                 // ... viewmatrix / projmatrix / campos, in floats (0: one camera)
     size_t geom_stride, pairs_stride, image_stride;      // ... workspaces, in bytes
-    int dbg;                            // DWG_RASTER_DEBUG bits (timing experiments; results are garbage): 1 no sort network, 2 no block masks, 4 no split
 };
 
 // header words of the geometry workspace
@@ -80,7 +79,8 @@ enum { H_K = 0, H_OVERFLOW = 1, H_KREF = 2, H_NSEG = 3 /* backward segments hand
 // Frame tags of the backward's pair-ordered partial rows (k_render_bwd / k_gather_partials) are drawn ON THE DEVICE, by the forward's scan
 // kernel, from this counter: a tag chosen by the host at launch time is a kernel argument, and kernel arguments are frozen into a captured
 // graph -- every replay of a captured step would then carry the SAME tag and rows left over from the previous replay would pass for this
-// frame's (step_graph.py / player.py replay the launches, not the host code around them).
+// frame's (step_graph.py / player.py replay the launches, not the host code around them).  Both backward kernels read header[H_TAG]: a fresh
+// tag per frame, so rows of the pair-ordered partials count only if this frame's backward wrote them (no clearing of the buffer).
 __device__ uint32_t g_frame_tag = 0x5eed0001u;
 
 struct GeomLayout {
@@ -452,7 +452,6 @@ __global__ __launch_bounds__(PB) void k_preprocess(Params p, const float* __rest
         }
     }
     // exact (Gaussian, block) pair count of this splat (its rows of the pair-ordered backward partials) + the supertile histogram
-    if (p.dbg & 8) sp.by1 = sp.by0;
     const uint32_t ng = for_each_supertile(sp, [&](int sy, int sx) {
         const int s = sy * p.stiles_x + sx;
         if (use_lds_hist) atomicAdd(&hist[s], 1u); else atomicAdd(&super_count[s], 1u);
@@ -480,7 +479,7 @@ __global__ __launch_bounds__(PB) void k_preprocess(Params p, const float* __rest
         for (int w = 0; w < PB / 64; w++) k += krs[w];
         kref_part[blockIdx.x] = (uint32_t)k;
     }
-    if (use_lds_hist && !(p.dbg & 32))
+    if (use_lds_hist)
         for (int t = threadIdx.x; t < S; t += PB) { uint32_t c = hist[t]; if (c) atomicAdd(&super_count[t], c); }
 }
 
@@ -631,12 +630,11 @@ struct LdsSlotMem {
 
 // sorts keys_in[0, n) ascending; on return (behind a barrier) key e is at lds[sort_slot(e)]
 template <int THREADS, int EPT>
-__device__ __forceinline__ void sort_in_lds(const uint64_t* __restrict__ keys_in, int n, uint64_t* __restrict__ lds, int skip) {
+__device__ __forceinline__ void sort_in_lds(const uint64_t* __restrict__ keys_in, int n, uint64_t* __restrict__ lds) {
     constexpr int N = THREADS * EPT;
     const int tid = threadIdx.x;
     for (int e = tid; e < N; e += THREADS) lds[sort_slot(e)] = e < n ? keys_in[e] : ~0ull;      // coalesced in, +inf above n
     __syncthreads();
-    if (skip) return;
     uint64_t v[EPT];
 #pragma unroll
     for (int r = 0; r < EPT; r++) v[r] = lds[sort_slot(tid * EPT + r)];
@@ -824,9 +822,9 @@ __global__ __launch_bounds__(256) void k_chunk_sort(Params p, const uint32_t* __
     if (!find_chunk(p, (int)blockIdx.x, chunk_start, super_start, header, cap, &r)) return;
     uint64_t* lds = reinterpret_cast<uint64_t*>(smem_raw);
     uint64_t* kc = keys + r.sa + r.a;
-    if (r.n <= 256) sort_in_lds<256, 1>(kc, r.n, lds, p.dbg & 1);
-    else if (r.n <= 512) sort_in_lds<256, 2>(kc, r.n, lds, p.dbg & 1);
-    else sort_in_lds<256, 4>(kc, r.n, lds, p.dbg & 1);
+    if (r.n <= 256) sort_in_lds<256, 1>(kc, r.n, lds);
+    else if (r.n <= 512) sort_in_lds<256, 2>(kc, r.n, lds);
+    else sort_in_lds<256, 4>(kc, r.n, lds);
     for (int e = threadIdx.x; e < r.n; e += 256) kc[e] = lds[sort_slot(e)];
 }
 
@@ -916,21 +914,19 @@ __global__ __launch_bounds__(256) void k_rank_merge(Params p, const uint32_t* __
         const int e = threadIdx.x + u * 256;
         if (e >= r.n) break;
         uint32_t mask = 0;
-        if (!(p.dbg & 2)) {
-            const float4 a = ra[u], b = rb[u];
-            const BlockSpan sp = block_span(a.x, a.y, b.x, b.y, b.z, a.w, (int)(rc[u].x & 0xffff), (int)(rc[u].x >> 16), (int)(rc[u].y & 0xffff),
-                                            (int)(rc[u].y >> 16), p.tiles_x, p.tiles_y);
+        const float4 a = ra[u], b = rb[u];
+        const BlockSpan sp = block_span(a.x, a.y, b.x, b.y, b.z, a.w, (int)(rc[u].x & 0xffff), (int)(rc[u].x >> 16), (int)(rc[u].y & 0xffff),
+                                        (int)(rc[u].y >> 16), p.tiles_x, p.tiles_y);
 #pragma unroll
-            for (int rr = 0; rr < ST; rr++) {
-                const int by = sy * ST + rr;
-                if (by >= sp.by0 && by < sp.by1) {
-                    int xa, xb;
-                    block_row(sp, by, &xa, &xb);
-                    const int lo = max(xa, sx * ST), hi = min(xb, sx * ST + ST);
-                    if (hi > lo) mask |= ((1u << (hi - lo)) - 1u) << (rr * ST + lo - sx * ST);
-                }
+        for (int rr = 0; rr < ST; rr++) {
+            const int by = sy * ST + rr;
+            if (by >= sp.by0 && by < sp.by1) {
+                int xa, xb;
+                block_row(sp, by, &xa, &xb);
+                const int lo = max(xa, sx * ST), hi = min(xb, sx * ST + ST);
+                if (hi > lo) mask |= ((1u << (hi - lo)) - 1u) << (rr * ST + lo - sx * ST);
             }
-        } else mask = 1u;
+        }
         cand[r.sa + pos[u]] = ((uint64_t)mask << 32) | (uint32_t)key[u];
     }
 }
@@ -1099,7 +1095,7 @@ __global__ __launch_bounds__(64) void k_render_bwd(Params p, const int32_t* __re
                                                    const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ tile_count,
                                                    const uint32_t* __restrict__ tile_neff,
                                                    const uint32_t* __restrict__ sorted, const uint2* __restrict__ rect,
-                                                   const uint32_t* __restrict__ goff, uint32_t tag, const float4* __restrict__ rec0,
+                                                   const uint32_t* __restrict__ goff, const float4* __restrict__ rec0,
                                                    const float4* __restrict__ rec1, const float4* __restrict__ rec2,
                                                    int64_t cap, const float* __restrict__ ckpt, const float* __restrict__ final_T,
                                                    const int* __restrict__ n_contrib, const float* __restrict__ craw,
@@ -1122,7 +1118,7 @@ __global__ __launch_bounds__(64) void k_render_bwd(Params p, const int32_t* __re
     }
     const int64_t seg = blockIdx.x;
     if (seg >= (int64_t)header[H_NSEG] || seg >= cap_segs || header[H_OVERFLOW]) return;    // a truncated frame is redone by the caller
-    tag = (uint32_t)header[H_TAG];                             // the frame's tag (the argument is unused: see g_frame_tag)
+    const uint32_t tag = (uint32_t)header[H_TAG];              // the frame's tag (see g_frame_tag)
     const int tile = (int)seg_tile[seg];
     if ((unsigned)tile >= (unsigned)(p.tiles_x * p.tiles_y)) return;
     const int sidx = (int)(seg - (int64_t)seg_start[tile]);
@@ -1253,17 +1249,18 @@ __global__ __launch_bounds__(64) void k_render_bwd(Params p, const int32_t* __re
 // rows per wave-instruction, neighbouring Gaussians' rows being neighbours in memory) and ends up holding piece h of the sum -- no
 // cross-lane reduction, no LDS, no barrier.  (Tried first: a thread per Gaussian reading its own rows -- 64 scattered lines per instruction,
 // 53 us at 50 k Gaussians; streaming a workgroup's whole run through LDS -- the chunk loop's length is set by the big splats in the run,
-// 150-960 us.)  Big splats (> GBIG rows; 64 by default: the quad path costs a wave its LONGEST quad, a dependent trip per four rows, and the pair
+// 150-960 us.)  Big splats (> GBIG = 64 rows: the quad path costs a wave its LONGEST quad, a dependent trip per four rows, and the pair
 // counts are heavy-tailed -- at 192 the launch was its tail, waves parked 0.82 of the time) are summed by their whole wave, lane-strided over
 // the rows, and joined by a fixed tree.
+constexpr int GBIG = 64;
 __global__ __launch_bounds__(256) void k_gather_partials(int G, const uint32_t* __restrict__ goff, const float* __restrict__ part, int64_t cap,
-                                                         const int32_t* __restrict__ header, uint32_t tag, float* __restrict__ gacc, int GBIG,
+                                                         const int32_t* __restrict__ header, float* __restrict__ gacc,
                                                          size_t geom_stride, size_t pairs_stride) {
     goff = frame_ptr(goff, geom_stride); header = frame_ptr(header, geom_stride); part = frame_ptr(part, pairs_stride);     // frame blockIdx.y
     gacc += (size_t)blockIdx.y * (size_t)G * GSTRIDE;
     const int i = blockIdx.x * 64 + (threadIdx.x >> 2), h = threadIdx.x & 3, lane = threadIdx.x & 63;
     const bool ok = !header[H_OVERFLOW];                       // a truncated frame is redone by the caller: zeros
-    tag = (uint32_t)header[H_TAG];
+    const uint32_t tag = (uint32_t)header[H_TAG];
     const int64_t capc = cap > 0 ? cap : 0;
     int64_t q0 = 0, q1 = 0;
     if (i < G && ok) { q0 = min((int64_t)goff[i], capc); q1 = min((int64_t)goff[i + 1], capc); }
@@ -1558,27 +1555,19 @@ static int make_params(const dwg_raster_settings* cfg, const dwg_raster_frames* 
     p->visit_order = cfg->visit_order;
     p->in_stride = fr ? fr->gaussian_stride : 0; p->cam_stride = fr ? fr->camera_stride : 0;
     p->geom_stride = p->pairs_stride = p->image_stride = 0;      // set by the callers that know the capacity
-    static const int dbg = getenv("DWG_RASTER_DEBUG") ? atoi(getenv("DWG_RASTER_DEBUG")) : 0;
-    p->dbg = dbg;
     return DWG_OK;
 }
 
 }  // namespace
 
 // Workgroup-private LDS supertile histograms (one global atomic per workgroup and supertile instead of one per (Gaussian, supertile)
-// pair) up to 16384 supertiles (4096^2 pixels); DWG_RASTER_LDS_MAXS lowers the limit (experiment switch).
+// pair) up to LDS_HIST_MAX_S supertiles (4096^2 pixels).
+constexpr int LDS_HIST_MAX_S = 16384;
+static int lds_hist_ok(int S) { return S <= LDS_HIST_MAX_S; }
+
 // Threads per workgroup of the two per-Gaussian binning kernels: 1024 from 128 k Gaussians (a quarter of the (workgroup, supertile) global
 // atomics of 256-thread workgroups: scatter 52 -> 26 us on 300 k shuffled Gaussians), 256 below (small frames need the workgroup count).
-static int binning_block(int G) {
-    static const int forced = getenv("DWG_RASTER_PB") ? atoi(getenv("DWG_RASTER_PB")) : 0;
-    if (forced == 256 || forced == 1024) return forced;
-    return G >= (1 << 17) ? 1024 : 256;
-}
-
-static int lds_hist_ok(int S) {
-    static const int lds_max_s = getenv("DWG_RASTER_LDS_MAXS") ? atoi(getenv("DWG_RASTER_LDS_MAXS")) : 16384;
-    return S <= lds_max_s && S <= 16384;
-}
+static int binning_block(int G) { return G >= (1 << 17) ? 1024 : 256; }
 
 extern "C" {
 
@@ -1635,10 +1624,10 @@ int dwg_raster_forward_bin_frames(const dwg_raster_settings* cfg, const dwg_rast
     }
     static bool attr_set = false;
     if (!attr_set) {      // 64 KiB of histogram + the static camera words is over the 64 KiB default limit
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_preprocess<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_preprocess<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_super<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_super<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_preprocess<256>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_MAX_S * 4);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_preprocess<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_MAX_S * 4);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_super<256>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_MAX_S * 4);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_super<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_MAX_S * 4);
         attr_set = true;
     }
     if (G > 0) {
@@ -1753,13 +1742,9 @@ int dwg_raster_backward_frames(const dwg_raster_settings* cfg, const dwg_raster_
     const int64_t cap_segs = seg_capacity(pair_capacity > 0 ? pair_capacity : 1, p.H, p.W);
     const char* ws = (const char*)ws_geom; const char* wp = (const char*)ws_pairs; const char* wi = (const char*)ws_image;
     // per-pair partials in pair-row order (no atomics), then each Gaussian's contiguous rows summed into ws_grad [F][G][GSTRIDE]
-    // a fresh tag per backward: rows of the pair-ordered partials count only if this frame wrote them (no clearing of the buffer)
-    // (the tag itself is header[H_TAG], drawn on the device by the forward's scan kernel: see g_frame_tag)
-    const uint32_t tag = 0u;
-    static const int gbig = getenv("DWG_RASTER_GBIG") ? atoi(getenv("DWG_RASTER_GBIG")) : 64;      // experiment switch (see k_gather_partials)
 #define DWG_BWD_ARGS p, (const int32_t*)(ws + L.header), cap_segs, (const uint32_t*)(wp + PL.seg_tile), (const uint32_t*)(ws + L.seg_start),   \
         (const uint32_t*)(ws + L.tile_start), (const uint32_t*)(ws + L.tile_count), (const uint32_t*)(ws + L.tile_neff), (const uint32_t*)(wp + PL.sorted), \
-        (const uint2*)(ws + L.rect), (const uint32_t*)(ws + L.goff), tag, (const float4*)(ws + L.rec0), (const float4*)(ws + L.rec1),           \
+        (const uint2*)(ws + L.rect), (const uint32_t*)(ws + L.goff), (const float4*)(ws + L.rec0), (const float4*)(ws + L.rec1),                \
         (const float4*)(ws + L.rec2), pair_capacity, (const float*)(wp + PL.ckpt), (const float*)(wi + IL.final_T),                              \
         (const int*)(wi + IL.n_contrib), (const float*)(wi + IL.craw), dL_dout_color, dL_dout_depth, dL_dout_alpha,                              \
         (float*)(const_cast<char*>(wp) + PL.part)
@@ -1767,7 +1752,7 @@ int dwg_raster_backward_frames(const dwg_raster_settings* cfg, const dwg_raster_
     else DWG_LAUNCH("raster_render_bwd", k_render_bwd<false>, dim3((unsigned)cap_segs, F), dim3(64), 0, stream, DWG_BWD_ARGS);
 #undef DWG_BWD_ARGS
     DWG_LAUNCH("raster_gather_bwd", k_gather_partials, dim3(dwg_cdiv(G, 64), F), dim3(256), 0, stream, G, (const uint32_t*)(ws + L.goff),
-               (const float*)(wp + PL.part), pair_capacity, (const int32_t*)(ws + L.header), tag, (float*)ws_grad, gbig, p.geom_stride, p.pairs_stride);
+               (const float*)(wp + PL.part), pair_capacity, (const int32_t*)(ws + L.header), (float*)ws_grad, p.geom_stride, p.pairs_stride);
     DWG_LAUNCH("raster_preprocess_bwd", k_preprocess_bwd, dim3(dwg_cdiv(G, 256), F), dim3(256), 0, stream, p, means3D, shs, colors_precomp,
                scales, rotations, cov3D_precomp, (const uint2*)(ws + L.rect), (const float4*)(ws + L.rec2),
                (const float*)ws_grad, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacities, dL_dscales,

@@ -112,6 +112,23 @@ def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _workspace_sizes(G, H, W, cap):
+    """Bytes of one frame's (geometry, pair, image) workspaces at pair capacity `cap` (dwg_raster_workspace_sizes)."""
+    gb, pb, ib = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(_lib.lib().dwg_raster_workspace_sizes(G, H, W, cap, ctypes.byref(gb), ctypes.byref(pb), ctypes.byref(ib)),
+               "dwg_raster_workspace_sizes")
+    return gb.value, pb.value, ib.value
+
+
+def _frames_structs(cameras, F, G, per_frame, H, W, tanfovx, tanfovy, bg, sh_degree, scale_modifier, M, device, keep):
+    """(dwg_raster_settings, dwg_raster_frames) of a chain of F frames: the first camera row's matrices, and the strides from frame to frame."""
+    rs = GaussianRasterizationSettings(H, W, tanfovx, tanfovy, bg, scale_modifier, cameras.reshape(-1)[0:16],
+                                       cameras.reshape(-1)[16:32], sh_degree, cameras.reshape(-1)[32:35], False, False)
+    cfg = _settings_struct(rs, device, M, keep)
+    fr = _lib.RasterFramesC(F, G if per_frame else 0, 35 if (cameras.dim() == 2 and cameras.shape[0] == F and F > 1) else 0)
+    return cfg, fr
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -141,11 +158,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             if visit_order.dtype != torch.int32 or visit_order.device != device or visit_order.numel() != G or not visit_order.is_contiguous():
                 raise ValueError("visit_order: a contiguous int32 permutation of the %d Gaussians on %s" % (G, device))
             cfg.visit_order = visit_order.data_ptr()
-        gb, pb, ib = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.check(L.dwg_raster_workspace_sizes(G, H, W, 0, ctypes.byref(gb), ctypes.byref(pb), ctypes.byref(ib)),
-                   "dwg_raster_workspace_sizes")
-        ws_geom = torch.empty(gb.value, dtype=torch.uint8, device=device)
-        ws_image = torch.empty(ib.value, dtype=torch.uint8, device=device)
+        geom_bytes, _, image_bytes = _workspace_sizes(G, H, W, 0)
+        ws_geom = torch.empty(geom_bytes, dtype=torch.uint8, device=device)
+        ws_image = torch.empty(image_bytes, dtype=torch.uint8, device=device)
         radii = torch.empty(G, dtype=torch.int32, device=device)         # k_preprocess writes every entry (0 for what it culls)
         st = _stream(device)
         p = _lib.ptr
@@ -166,9 +181,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 pair_state.seed(K)
                 pair_state.last_num_pairs, pair_state.last_num_pairs_ref = K, int(hdr[2])
                 cap = pair_state.cap
-        _lib.check(L.dwg_raster_workspace_sizes(G, H, W, cap, ctypes.byref(gb), ctypes.byref(pb), ctypes.byref(ib)),
-                   "dwg_raster_workspace_sizes")
-        ws_pairs = torch.empty(pb.value, dtype=torch.uint8, device=device)
+        ws_pairs = torch.empty(_workspace_sizes(G, H, W, cap)[1], dtype=torch.uint8, device=device)
         color = torch.empty(3, H, W, dtype=torch.float32, device=device)
         depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
         alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
@@ -256,14 +269,11 @@ class _RasterizeFrames(torch.autograd.Function):
         G = int(means3D.shape[-2])
         M = int(shs.shape[-2]) if shs is not None else 0
         keep = []
-        rs = GaussianRasterizationSettings(H, W, float(tanfovx), float(tanfovy), bg, float(scale_modifier), cameras.reshape(-1)[0:16],
-                                           cameras.reshape(-1)[16:32], int(sh_degree), cameras.reshape(-1)[32:35], False, False)
-        cfg = _settings_struct(rs, device, M, keep)
-        fr = _lib.RasterFramesC(F, G if per_frame else 0, 35 if (cameras.dim() == 2 and cameras.shape[0] == F and F > 1) else 0)
-        gb, pb, ib = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.check(L.dwg_raster_workspace_sizes(G, H, W, 0, ctypes.byref(gb), ctypes.byref(pb), ctypes.byref(ib)), "dwg_raster_workspace_sizes")
-        ws_geom = torch.empty(F * gb.value, dtype=torch.uint8, device=device)
-        ws_image = torch.empty(F * ib.value, dtype=torch.uint8, device=device)
+        cfg, fr = _frames_structs(cameras, F, G, per_frame, H, W, float(tanfovx), float(tanfovy), bg, int(sh_degree), float(scale_modifier), M,
+                                  device, keep)
+        geom_bytes, _, image_bytes = _workspace_sizes(G, H, W, 0)
+        ws_geom = torch.empty(F * geom_bytes, dtype=torch.uint8, device=device)
+        ws_image = torch.empty(F * image_bytes, dtype=torch.uint8, device=device)
         radii = torch.empty(F, G, dtype=torch.int32, device=device)          # k_preprocess writes every entry (0 for what it culls)
         st, p = _stream(device), _lib.ptr
         _lib.check(L.dwg_raster_forward_bin_frames(ctypes.byref(cfg), ctypes.byref(fr), G, p(means3D), p(shs), p(colors_precomp), p(opac),
@@ -275,13 +285,12 @@ class _RasterizeFrames(torch.autograd.Function):
         elif pair_state is not None and pair_state.cap > 0:
             cap = pair_state.cap               # no host synchronisation (PairCapacity): every frame of the chain gets the state's capacity
         else:                                  # one read-back of the F pair counts sizes the shared capacity exactly
-            hdrs = ws_geom.view(F, gb.value)[:, :16].contiguous().view(torch.int32)
+            hdrs = ws_geom.view(F, geom_bytes)[:, :16].contiguous().view(torch.int32)
             cap = max(int(hdrs[:, 0].max().item()), 1)
             if pair_state is not None:
                 pair_state.seed(cap)
                 cap = pair_state.cap
-        _lib.check(L.dwg_raster_workspace_sizes(G, H, W, cap, ctypes.byref(gb), ctypes.byref(pb), ctypes.byref(ib)), "dwg_raster_workspace_sizes")
-        ws_pairs = torch.empty(F * pb.value, dtype=torch.uint8, device=device)
+        ws_pairs = torch.empty(F * _workspace_sizes(G, H, W, cap)[1], dtype=torch.uint8, device=device)
         color = torch.empty(F, 3, H, W, dtype=torch.float32, device=device)
         depth = torch.empty(F, 1, H, W, dtype=torch.float32, device=device)
         alpha = torch.empty(F, 1, H, W, dtype=torch.float32, device=device)
@@ -322,10 +331,8 @@ class _RasterizeFrames(torch.autograd.Function):
                 z = lambda t: None if t is None else torch.zeros_like(t)     # noqa: E731
                 return (z(means3D), z(opac), z(colors_precomp), z(shs), z(scales), z(rotations), z(cov3D)) + (None,) * 11
         keep = []
-        rs = GaussianRasterizationSettings(H, W, tanfovx, tanfovy, bg_t if bg_t is not None else ctx.bg, scale_modifier, cameras.reshape(-1)[0:16],
-                                           cameras.reshape(-1)[16:32], sh_degree, cameras.reshape(-1)[32:35], False, False)
-        cfg = _settings_struct(rs, device, M, keep)
-        fr = _lib.RasterFramesC(F, G if per_frame else 0, 35 if (cameras.dim() == 2 and cameras.shape[0] == F and F > 1) else 0)
+        cfg, fr = _frames_structs(cameras, F, G, per_frame, H, W, tanfovx, tanfovy, bg_t if bg_t is not None else ctx.bg, sh_degree, scale_modifier,
+                                  M, device, keep)
         g_color = torch.zeros(F, 3, H, W, device=device) if g_color is None else _f32c(g_color)
         g_depth = None if g_depth is None else _f32c(g_depth)
         g_alpha = None if g_alpha is None else _f32c(g_alpha)

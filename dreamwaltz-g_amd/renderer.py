@@ -3,7 +3,6 @@ same constructor, same `build_gaussian_rasterizer(data)` / `compute_colors` / `c
 `render(data, gaussians, return_2d_radii, rasterizer)` contract and output dict, bound to the HIP rasterizer (rasterizer.py)
 instead of the CUDA package."""
 import ctypes
-import os
 from typing import Optional
 
 import torch
@@ -66,7 +65,7 @@ class _ChainCounts:
 
 class GaussianRenderer:
     def __init__(self, sh_levels=4, bg_color=(0.0, 0.0, 0.0), compute_color_in_rasterizer=True,
-                 compute_covariance_in_rasterizer=True, async_pair_count=False, reorder_every: Optional[int] = None) -> None:
+                 compute_covariance_in_rasterizer=True, async_pair_count=False, reorder_every: int = 0) -> None:
         self.sh_levels = sh_levels
         self.bg_color = torch.tensor(bg_color, dtype=torch.float32)
         self.compute_color_in_rasterizer = compute_color_in_rasterizer
@@ -79,9 +78,7 @@ class GaussianRenderer:
         self.last_rasterizer = None
         # Binning order (rasterizer.morton_order): refreshed from the current positions every `reorder_every` frames per Gaussian
         # count (0, the default since round 5: never -- index order, coalesced reads; the supertile histograms merge their atomics either way);
-        # the images do not depend on it.  DWG_RASTER_REORDER=<frames> switches the refresh on.
-        if reorder_every is None:
-            reorder_every = int(os.environ.get("DWG_RASTER_REORDER", "0"))
+        # the images do not depend on it.  The argument (or the attribute) is the only way to switch the refresh on.
         self.reorder_every = int(reorder_every)
         self._visit_orders = {}
 

@@ -118,9 +118,9 @@ class SDSTrainer:
         # The views' animate + rasterizer passes are independent chains of small, latency-bound launches: each runs on its OWN stream (and
         # so does its backward: autograd replays a node on its forward's stream), so that one view's tails and dependent launches overlap
         # with the other views' work -- "V views per launch" in effect, for the whole per-view chain and not only the rasterizer.  The
-        # first batched step runs on one stream (caches of constant canonical-pose results are filled there).  DWG_VIEW_STREAMS=0: off.
+        # first batched step runs on one stream (caches of constant canonical-pose results are filled there), and so does a model that is not on a GPU.
         dev = getattr(self.model, "device", None)
-        multi = (dev is not None and torch.device(dev).type == "cuda" and self._views_warm and os.environ.get("DWG_VIEW_STREAMS", "1") != "0")
+        multi = (dev is not None and torch.device(dev).type == "cuda" and self._views_warm)
         main = torch.cuda.current_stream(dev) if multi else None
         if multi:
             while len(self._view_streams) < len(views):
@@ -152,8 +152,8 @@ class SDSTrainer:
     def _views_on_one_chain(self, views):
         """The batched step rasterizes its V views on ONE launch chain, forward and backward (Scene.forward_views; round 6) when the views
         agree on image size and field of view and nothing needs the per-view rasterizer objects (densification statistics).
-        DWG_VIEW_FRAMES=0: every view runs its own seven + three launches (the round-5 path)."""
-        if os.environ.get("DWG_VIEW_FRAMES", "1") == "0" or not hasattr(self.model, "forward_views") or getattr(self.model, "avatars", None) is not None:
+        Otherwise every view runs its own seven + three launches (the round-5 path)."""
+        if not hasattr(self.model, "forward_views") or getattr(self.model, "avatars", None) is not None:
             return False
         if self.densifiers is not None or not all(torch.is_tensor(v.get('extrinsic')) and v['extrinsic'].is_cuda for v in views):
             return False

@@ -224,6 +224,7 @@ def test_renderer_refreshes_its_binning_order_on_schedule():
     c = r._visit_order_for(torch.rand(50, 3))              # another Gaussian count: its own entry
     assert c.numel() == 50 and r._visit_order_for(p.flip(0)) is b
     assert GaussianRenderer(reorder_every=0).reorder_every == 0
+    assert GaussianRenderer().reorder_every == 0               # the default: index order, whatever the environment says
 
 
 def test_frozen_pair_capacity_never_waits():
