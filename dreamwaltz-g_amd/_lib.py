@@ -107,6 +107,11 @@ SIGNATURES = {
     "dwg_pc_fd_points": (ctypes.c_int, [ctypes.c_uint64, _vp, _f32, _f32, _vp, _vp]),
     "dwg_pc_finish": (ctypes.c_int, [ctypes.c_uint64, _u32, _vp, _vp, _f32, _vp, _vp, _vp]),
     "dwg_pc_outside_boxes": (ctypes.c_int, [ctypes.c_uint64, _vp, _u32, _vp, _vp, _vp]),
+    # include/dwg_occupancy.h
+    "dwg_occ_lattice_sigma": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "dwg_occ_lattice_points": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "dwg_occ_update_workspace_bytes": (_sz, [_u32, _u32]),
+    "dwg_occ_update": (ctypes.c_int, [_vp, _vp, _u32, _u32, _f32, _f32, _vp, _vp, _vp, _sz, _vp]),
     # include/dwg_background.h
     "dwg_video_composite_forward": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "dwg_video_composite_backward": (ctypes.c_int, [_i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -130,6 +135,7 @@ SIGNATURES = {
     "dwg_raymarch_morton3d": (ctypes.c_int, [_vp, _u32, _vp, _vp]),
     "dwg_raymarch_morton3d_invert": (ctypes.c_int, [_vp, _u32, _vp, _vp]),
     "dwg_raymarch_packbits": (ctypes.c_int, [_vp, _u32, _f32, _vp, _vp]),
+    "dwg_raymarch_packbits_dev": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp]),
     "dwg_raymarch_flatten_rays": (ctypes.c_int, [_vp, _u32, _u32, _vp, _vp]),
     "dwg_raymarch_train_workspace_bytes": (_sz, [_u32]),
     "dwg_raymarch_march_rays_train": (ctypes.c_int, [_vp, _vp, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32,

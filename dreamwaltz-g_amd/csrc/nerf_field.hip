@@ -14,8 +14,11 @@
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_gridenc.h"
 #include "../../include/dwg_nerf.h"
+#include "../../include/dwg_occupancy.h"
 #include "../../include/dwg_pointcloud.h"
 #include "gridenc_common.h"
+#include "morton.h"
+#include "occupancy_common.h"
 #include "pointcloud_index.h"
 
 namespace {
@@ -129,6 +132,14 @@ struct XLattice {                           // the lattice of dwg_pointcloud.h: 
         uint32_t ix, iy, iz;
         pc_lattice_decode(l, (uint32_t)p0 + pt, ix, iy, iz);
         return k == 0 ? ax[ix] : k == 1 ? ay[iy] : az[iz];
+    }
+};
+
+struct XOccupancy {                         // the jittered cell points of dwg_occupancy.h: flat cell index -> (cascade, ix, iy, iz) -> occ_point
+    OccLattice l;
+    __device__ __forceinline__ float operator()(uint64_t p0, uint32_t i) const {
+        const uint32_t pt = i / 3u;
+        return occ_point(l, (uint32_t)p0 + pt, i - 3u * pt);
     }
 };
 
@@ -264,6 +275,33 @@ __global__ __launch_bounds__(256) void k_nf_lattice(NfP p, XLattice x, uint64_t 
         for (int i = 1; i < NF_TILE; i++) { lo = fminf(lo, sx[i]); hi = fmaxf(hi, sxn[i]); }
         minmax[2u * blockIdx.x] = lo; minmax[2u * blockIdx.x + 1u] = hi;
         for (uint32_t j = blockIdx.x + gridDim.x; j < (uint32_t)DWG_PC_MINMAX_PAIRS; j += gridDim.x) { minmax[2u * j] = INFINITY; minmax[2u * j + 1u] = -INFINITY; }
+    }
+}
+
+// Density only, at the jittered cell points of the occupancy grid (dwg_occ_lattice_sigma): k_nf_lattice with that source and the store
+// at the cell's Morton index.  M = C H^3 is a multiple of NF_TILE, so a tile is whole and lies in one cascade.
+template <typename T>
+__global__ __launch_bounds__(256) void k_nf_occupancy(NfP p, XOccupancy x, uint64_t M, uint64_t ntiles, uint32_t blob, float* __restrict__ tmp_grid) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* lds; float *bias, *sx, *sxn, *red;
+    lds_carve(p, smem, lds, bias, sx, sxn, red);
+    load_weights(p, lds, bias);
+    const float es = p.act == 2 ? expf(*p.sigma_scale) : 0.f;
+    const uint32_t lg3 = 3u * x.l.lg;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t p0 = tile * NF_TILE;
+        field_tile(p, x, M, p0, lds, bias, sx, sxn);
+        const uint32_t t = threadIdx.x;
+        if (t < NF_TILE && p0 + t < M) {
+            const T* o = lds + p.aoff[p.nl] + t * p.ast[p.nl];
+            float s = nf_sigma(p, (float)o[0], sx + 3 * t, es);
+            if (blob) s += occ_blob(sx[3 * t], sx[3 * t + 1], sx[3 * t + 2]);
+            const uint32_t g = (uint32_t)p0 + t, c = g >> lg3;
+            uint32_t ix, iy, iz;
+            occ_decode(x.l.lg, g & ((1u << lg3) - 1u), ix, iy, iz);
+            tmp_grid[((size_t)c << lg3) + morton3d(ix, iy, iz)] = s;
+        }
+        __syncthreads();
     }
 }
 
@@ -600,6 +638,32 @@ int dwg_pc_lattice_sigma(const dwg_nerf_field_desc* desc, const float* ax, const
     } else {
         static bool attr = false; lds_opt_in(&k_nf_lattice<float>, attr);
         DWG_LAUNCH("pc_lattice_sigma", k_nf_lattice<float>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, sigma, minmax);
+    }
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_occ_lattice_sigma(const dwg_nerf_field_desc* desc, const float* axis, const float* noise, const float* scale, const float* half,
+                          uint32_t C, uint32_t H, uint32_t random_sigmas, float* tmp_grid, dwg_stream_t stream) {
+    NfP p;
+    size_t lds = 0;
+    int rc = make_params(desc, p, lds);
+    if (rc) return rc;
+    uint32_t lg = 0;
+    if (desc->raw || !occ_limits(C, H, lg)) return DWG_E_ARG;
+    if (!axis || !noise || !scale || !half || !tmp_grid) return DWG_E_ARG;
+    const uint64_t M = (uint64_t)C << (3u * lg);
+    const uint64_t ntiles = M / NF_TILE;                    // H >= 4: H^3 is a multiple of 64
+    const unsigned grid = (unsigned)(ntiles < 4096 ? ntiles : 4096);
+    const XOccupancy x{OccLattice{axis, noise, scale, half, lg}};
+    const uint32_t blob = random_sigmas ? 1u : 0u;
+    hipStream_t st = (hipStream_t)stream;
+    if (desc->precision) {
+        static bool attr = false; lds_opt_in(&k_nf_occupancy<_Float16>, attr);
+        DWG_LAUNCH("occ_lattice_sigma", k_nf_occupancy<_Float16>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, blob, tmp_grid);
+    } else {
+        static bool attr = false; lds_opt_in(&k_nf_occupancy<float>, attr);
+        DWG_LAUNCH("occ_lattice_sigma", k_nf_occupancy<float>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, blob, tmp_grid);
     }
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;

@@ -16,6 +16,7 @@
 #include "dwg_common.h"
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_raymarch.h"
+#include "morton.h"
 
 #pragma clang fp contract(off)
 
@@ -29,25 +30,6 @@ constexpr int kScanBlock = kScanThreads * kScanItems;
 constexpr int kRaysPerWave = 4;                     // composite: consecutive rays owned by one wave
 
 __device__ __forceinline__ float clampf_(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
-
-__device__ __forceinline__ uint32_t expand_bits(uint32_t v) {
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
-}
-__device__ __forceinline__ uint32_t morton3d(uint32_t x, uint32_t y, uint32_t z) {
-    return expand_bits(x) | (expand_bits(y) << 1) | (expand_bits(z) << 2);
-}
-__device__ __forceinline__ uint32_t morton3d_invert(uint32_t x) {
-    x = x & 0x49249249u;
-    x = (x | (x >> 2)) & 0xc30c30c3u;
-    x = (x | (x >> 4)) & 0x0f00f00fu;
-    x = (x | (x >> 8)) & 0xff0000ffu;
-    x = (x | (x >> 16)) & 0x0000ffffu;
-    return x;
-}
 
 // level from a magnitude: frexp exponent clamped to [0, C-1] ([0.5,1) -> 0, [1,2) -> 1, ...)
 __device__ __forceinline__ int mip_level(float mx, float maxc) {

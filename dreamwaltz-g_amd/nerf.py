@@ -6,6 +6,7 @@
                                  sigma_net weight and bias and sigma_scale -- only those autograd asks for.
   bind_nerf_network(ref)         rebinds common_forward and local_geometry_forward of a constructed reference _NeRFNetwork to
                                  nerf_field; the reference's own Parameters are read in place (optimizer, checkpoints untouched).
+                                 With cuda_ray it also rebinds update_extra_state to the native occupancy update (occupancy.py, B13).
 Precision follows autocast: under torch.autocast(fp16) the kernels mirror the reference's fp16 rounding points (f16 MFMA, fp32
 accumulation), otherwise they compute in exact f32.  The arithmetic is csrc/nerf_field.hip; no CPU fallback.  Every buffer is checked
 (CUDA, contiguous, dtype, size) and a violation raises RuntimeError before any launch.
@@ -288,14 +289,82 @@ def bind_nerf_network(ref):
     local_geometry_forward.__wrapped__ = orig_local
     ref.common_forward = common_forward
     ref.local_geometry_forward = local_geometry_forward
+    _bind_update_extra_state(ref)
     ref._dwg_nerf_bound = True
     ref._dwg_nerf_unbound = None
     return None
 
 
+def _occupancy_covered(ref):
+    """The native occupancy update (boundary B13, occupancy.py) takes this network's render state: cuda_ray with density_grid /
+    density_bitfield buffers within dwg_occupancy.h's limits."""
+    from . import occupancy
+    if not getattr(ref, "cuda_ray", False) or not hasattr(type(ref), "update_extra_state"):
+        return False
+    grid, bits = getattr(ref, "density_grid", None), getattr(ref, "density_bitfield", None)
+    H, C = getattr(ref, "grid_size", None), getattr(ref, "cascade", None)
+    if not isinstance(grid, torch.Tensor) or not isinstance(bits, torch.Tensor) or not isinstance(H, int) or not isinstance(C, int):
+        return False
+    if not occupancy.within_limits(C, H) or not float(ref.bound) > 0 or C != occupancy.cascades(float(ref.bound)):
+        return False
+    return (grid.dtype == torch.float32 and tuple(grid.shape) == (C, H ** 3) and bits.dtype == torch.uint8 and bits.numel() == C * H ** 3 // 8)
+
+
+def _bind_update_extra_state(ref):
+    """Install update_extra_state(decay, S, random_sigmas) on a bound network: occupancy.OccupancyGrid.update on the reference's own
+    buffers (state_dict and checkpoints untouched), then mean_density / min_density / max_density / iter_density from one stats() read
+    and the reference's step-counter statements as they are (nerf_renderer.py:149-153; mean_count's .item() is the second, 4-byte,
+    read).  The original method takes the calls the kernels do not: not cuda_ray, a chunked update (S below grid_size: the chunked order
+    of the draws is not restated), buffers or parameters on the CPU, bf16 autocast."""
+    if "update_extra_state" in ref.__dict__ or not _occupancy_covered(ref):
+        return
+    from . import occupancy
+    orig_update = ref.update_extra_state
+
+    def _grid():
+        g = getattr(ref, "_dwg_occupancy", None)
+        if (g is None or g.density_grid.data_ptr() != ref.density_grid.data_ptr() or g.density_bitfield.data_ptr() != ref.density_bitfield.data_ptr()
+                or g.density_thresh != float(ref.density_thresh)):
+            g = occupancy.OccupancyGrid(ref.grid_size, ref.bound, ref.density_thresh, density_grid=ref.density_grid,
+                                        density_bitfield=ref.density_bitfield)
+            object.__setattr__(ref, "_dwg_occupancy", g)
+        return g
+
+    def _native(S):
+        if not ref.cuda_ray or (S is not None and S < ref.grid_size):
+            return False
+        grid, bits = ref.density_grid, ref.density_bitfield
+        if not (grid.is_cuda and bits.is_cuda and grid.is_contiguous() and bits.is_contiguous() and grid.data_ptr() % 16 == 0):
+            return False
+        if not (ref.encoder.embeddings.is_cuda and ref.sigma_scale.is_cuda):
+            return False
+        if torch.is_autocast_enabled():
+            dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
+            return dt == torch.float16
+        return True
+
+    def update_extra_state(decay=0.95, S=None, random_sigmas=False):
+        if not _native(S):
+            return orig_update(decay=decay, S=S, random_sigmas=random_sigmas)
+        g = _grid()
+        g.update(ref.encoder, ref.sigma_net, ref.sigma_scale, density_activation=ref.opt.density_activation,
+                 density_prior=ref.density_prior_type, decay=decay, random_sigmas=random_sigmas)
+        st = g.stats()
+        ref.mean_density, ref.min_density, ref.max_density = st["mean_density"], st["min_density"], st["max_density"]
+        ref.iter_density += 1
+        ### update step counter
+        total_step = min(16, ref.local_step)
+        if total_step > 0:
+            ref.mean_count = int(ref.step_counter[:total_step, 0].sum().item() / total_step)
+        ref.local_step = 0
+
+    update_extra_state.__wrapped__ = orig_update
+    ref.update_extra_state = update_extra_state
+
+
 def unbind_nerf_network(ref):
     """Undo bind_nerf_network (the instance attributes go; the class methods show through again)."""
-    for name in ("common_forward", "local_geometry_forward"):
+    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "_dwg_occupancy"):
         if name in ref.__dict__:
             del ref.__dict__[name]
     ref._dwg_nerf_bound = False

@@ -34,6 +34,10 @@ int dwg_raymarch_morton3d(const int32_t* coords /*[N,3]*/, uint32_t N, int32_t* 
 int dwg_raymarch_morton3d_invert(const int32_t* indices /*[N]*/, uint32_t N, int32_t* coords /*[N,3]*/, dwg_stream_t stream);
 /* bit i of byte j = grid[8j + i] > density_thresh; N = C*H^3/8 bytes */
 int dwg_raymarch_packbits(const float* grid /*[8N]*/, uint32_t N, float density_thresh, uint8_t* bitfield /*[N]*/, dwg_stream_t stream);
+/* the same with the threshold read from device memory (density_thresh [1] fp32; NaN sets no bit): the last stage of dwg_occ_update
+ * (dwg_occupancy.h), usable on its own.  grid 16-byte aligned. */
+int dwg_raymarch_packbits_dev(const float* grid /*[8N]*/, uint32_t N, const float* density_thresh /*[1]*/, uint8_t* bitfield /*[N]*/,
+                              dwg_stream_t stream);
 /* res[rays[n,0] + i] = n for i < rays[n,1]; rays whose range leaves [0, M) are skipped */
 int dwg_raymarch_flatten_rays(const int32_t* rays /*[N,2]*/, uint32_t N, uint32_t M, int32_t* res /*[M]*/, dwg_stream_t stream);
 
