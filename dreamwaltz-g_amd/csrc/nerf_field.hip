@@ -14,12 +14,14 @@
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_gridenc.h"
 #include "../../include/dwg_nerf.h"
+#include "../../include/dwg_nerf_render.h"
 #include "../../include/dwg_occupancy.h"
 #include "../../include/dwg_pointcloud.h"
 #include "gridenc_common.h"
 #include "morton.h"
 #include "occupancy_common.h"
 #include "pointcloud_index.h"
+#include "raymarch_common.h"
 
 namespace {
 
@@ -27,6 +29,9 @@ constexpr int NF_TILE = 64;                 // points per workgroup tile (4 wave
 constexpr int NF_MAXS = 13;                 // weight-gradient blocks per wave: (16 + 16 + 16 + 4) 16x16 blocks of 4 layers / 4 waves
 constexpr int NF_BWD_WG = 1024;             // workgroups of the backward (4 per CU): the number of weight-gradient partials
 constexpr uint64_t NF_CHUNK = 1ull << 20;   // points per backward chunk (bounds the d_enc and table-gradient workspace)
+constexpr int NR_SLOTS = 256;               // inference render: ray slots per workgroup, one per thread
+constexpr int NR_ITERS = 32;                // inference render: marching iterations (refills included) of a thread per round
+constexpr uint32_t NR_DEFAULT_WG = 512;     // inference render: persistent workgroups when the caller names no number
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -141,6 +146,11 @@ struct XOccupancy {                         // the jittered cell points of dwg_o
         const uint32_t pt = i / 3u;
         return occ_point(l, (uint32_t)p0 + pt, i - 3u * pt);
     }
+};
+
+struct XStaged {                            // the pending samples of the inference render, compacted into LDS in slot order
+    const float* s;
+    __device__ __forceinline__ float operator()(uint64_t p0, uint32_t i) const { return s[(uint32_t)p0 * 3u + i]; }
 };
 
 // x of the tile -> sx, the encoder's (x + bound) / (2 bound) -> sxn, the 64 x L lookups -> enc, then the layers; points at or past
@@ -302,6 +312,128 @@ __global__ __launch_bounds__(256) void k_nf_occupancy(NfP p, XOccupancy x, uint6
             tmp_grid[((size_t)c << lg3) + morton3d(ix, iy, iz)] = s;
         }
         __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// inference render (boundary B14): march, field and composite of a ray from near to its end in one persistent launch
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct RenderP {
+    const float* rays_o;
+    const float* rays_d;
+    const float* nears;
+    const float* fars;
+    uint32_t N, max_steps;
+    float T_thresh;
+    uint32_t binarize;
+    float* weights_sum;
+    float* depth;
+    float* image;
+    int32_t* counts;
+};
+
+// The statements of k_composite_rays (raymarch.hip) for one sample, in their order and without FP contraction, as that file compiles
+// them.  Returns true when the transmittance before the sample was below T_thresh (the sample is composited all the same).
+template <int NC>
+__device__ __forceinline__ bool composite_sample(float sigma, const float (&rgb)[NC], float t, float dt, float T_thresh, bool binarize,
+                                                 float& ws, float& d, float (&col)[NC]) {
+#pragma clang fp contract(off)
+    const float real_alpha = 1.f - expf(-sigma * dt);
+    const float alpha = binarize ? (real_alpha > 0.5f ? 1.f : 0.f) : real_alpha;
+    const float T = 1.f - ws;
+    const float w = alpha * T;
+    ws = ws + w;
+    d = d + w * t;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) col[k] = col[k] + w * rgb[k];
+    return T < T_thresh;
+}
+
+// One ray per thread (NR_SLOTS slots).  A round: every thread marches its ray to the next sample (taking the workgroup's next ray from
+// the LDS cursor when its slot is free), the pending samples are compacted into `stage` in slot order, field_tile runs on every 64 of
+// them and each owner composites its sample from its row of the last layer's output.  Workgroup w of G owns the 64-ray blocks w, w + G,
+// ...: the cursor counts through them.  Which slot or round a ray lands in changes no arithmetic of the ray.
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void k_nf_render(NfP p, MarchP m, RenderP q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* lds; float *bias, *sx, *sxn, *red;
+    lds_carve(p, smem, lds, bias, sx, sxn, red);
+    float* stage = red + NF_TILE;                                               // [NR_SLOTS][3]
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(stage + NR_SLOTS * 3);          // [0..3] pending per wave, [4..7] unfinished threads per wave, [8] cursor
+    load_weights(p, lds, bias);
+    if (threadIdx.x == 0) ctl[8] = 0u;
+    __syncthreads();
+    const float es = p.act == 2 ? expf(*p.sigma_scale) : 0.f;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const bool binarize = q.binarize != 0;
+    Ray ray = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float t = 0.f, far = 0.f, ws = 0.f, d = 0.f, col[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) col[k] = 0.f;
+    uint32_t idx = 0, cnt = 0;
+    bool have = false, done = false;                                            // a ray in the slot; no ray left for this thread
+    auto finish = [&]() {
+        q.weights_sum[idx] = ws;
+        q.depth[idx] = d;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) q.image[(size_t)NC * idx + k] = col[k];
+        if (q.counts) q.counts[idx] = (int32_t)cnt;
+        have = false;
+    };
+    for (;;) {
+        bool pend = false;
+        float cx = 0.f, cy = 0.f, cz = 0.f, dt = 0.f;
+        for (int it = 0; it < NR_ITERS && !done; ++it) {
+            if (!have) {
+                const uint32_t j = atomicAdd(&ctl[8], 1u);
+                const uint64_t n = ((uint64_t)(j >> 6) * gridDim.x + blockIdx.x) * 64u + (j & 63u);
+                if (n >= q.N) { done = true; break; }
+                idx = (uint32_t)n;
+                ray = load_ray(q.rays_o + 3 * (size_t)idx, q.rays_d + 3 * (size_t)idx);
+                far = q.fars[idx];
+                t = start_t(m, q.nears[idx], 0.f);
+                ws = 0.f; d = 0.f; cnt = 0u;
+#pragma unroll
+                for (int k = 0; k < NC; ++k) col[k] = 0.f;
+                have = true;
+            }
+            if (!(t < far)) { finish(); continue; }
+            if (march_iter(m, ray, t, cx, cy, cz, dt)) { pend = true; break; }
+        }
+        const unsigned long long bp = __ballot(pend), bl = __ballot(!done);
+        if (lane == 0) { ctl[wave] = (uint32_t)__popcll(bp); ctl[4 + wave] = (uint32_t)__popcll(bl); }
+        __syncthreads();
+        uint32_t pos = 0, total = 0, unfinished = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+            const uint32_t c = ctl[i];
+            if (i < wave) pos += c;
+            total += c;
+            unfinished += ctl[4 + i];
+        }
+        if (total == 0u && unfinished == 0u) break;
+        pos += (uint32_t)__popcll(bp & ((1ull << lane) - 1ull));
+        if (pend) { stage[3 * pos] = cx; stage[3 * pos + 1] = cy; stage[3 * pos + 2] = cz; }
+        __syncthreads();
+        for (uint32_t base = 0; base < total; base += NF_TILE) {
+            field_tile(p, XStaged{stage}, (uint64_t)total, (uint64_t)base, lds, bias, sx, sxn);
+            if (pend && pos - base < (uint32_t)NF_TILE) {                       // pos < base wraps past NF_TILE
+                const uint32_t r = pos - base;
+                const T* o = lds + p.aoff[p.nl] + r * p.ast[p.nl];
+                const float sigma = nf_sigma(p, (float)o[0], sx + 3 * r, es);
+                float rgb[NC];
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {
+                    float v = (float)o[1 + k];
+                    if (p.sig) v = 1.f / (1.f + expf(-v));
+                    rgb[k] = (float)(T)v;                                       // k_nf_fwd stores the albedo in T; the loop widens that tensor
+                }
+                const bool stop = composite_sample<NC>(sigma, rgb, t, dt, q.T_thresh, binarize, ws, d, col);
+                ++cnt;
+                if (stop || cnt >= q.max_steps) finish();
+            }
+            __syncthreads();
+        }
     }
 }
 
@@ -525,6 +657,14 @@ void lds_opt_in(K* kernel, bool& done) {
 uint64_t nf_chunk(uint64_t M) { return M < NF_CHUNK ? M : NF_CHUNK; }
 uint32_t nf_bwd_groups(uint64_t M) { const uint64_t t = (M + NF_TILE - 1) / NF_TILE; return (uint32_t)(t < NF_BWD_WG ? t : NF_BWD_WG); }
 
+template <typename T, int NC>
+int launch_render(const NfP& p, const MarchP& m, const RenderP& q, unsigned grid, size_t lds, hipStream_t st) {
+    static bool attr = false; lds_opt_in(&k_nf_render<T, NC>, attr);
+    DWG_LAUNCH("nf_render", (k_nf_render<T, NC>), dim3(grid), dim3(256), lds, st, p, m, q);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -667,6 +807,29 @@ int dwg_occ_lattice_sigma(const dwg_nerf_field_desc* desc, const float* axis, co
     }
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
+}
+
+int dwg_nerf_render_infer(const dwg_nerf_field_desc* desc, const float* rays_o, const float* rays_d, const float* nears, const float* fars,
+                          uint32_t N, const uint8_t* bitfield, float bound, uint32_t contract, float dt_gamma, uint32_t max_steps, uint32_t C,
+                          uint32_t H, float T_thresh, uint32_t binarize, float* weights_sum, float* depth, float* image, int32_t* counts,
+                          uint32_t max_workgroups, dwg_stream_t stream) {
+    NfP p;
+    size_t lds = 0;
+    int rc = make_params(desc, p, lds);
+    if (rc) return rc;
+    if (!march_args_ok(bound, max_steps, C, H)) return DWG_E_ARG;
+    if (desc->raw || (desc->out_dim != 4 && desc->out_dim != 5)) return DWG_E_ARG;
+    lds += (NR_SLOTS * 3 + 16) * sizeof(float);
+    if (lds > 160 * 1024) return DWG_E_ARG;
+    if (N == 0) return DWG_OK;
+    if (!rays_o || !rays_d || !nears || !fars || !bitfield || !weights_sum || !depth || !image) return DWG_E_ARG;
+    const MarchP m = make_march(bitfield, bound, contract, dt_gamma, max_steps, C, H);
+    const RenderP q{rays_o, rays_d, nears, fars, N, max_steps, T_thresh, binarize, weights_sum, depth, image, counts};
+    const uint32_t blocks = (uint32_t)(((uint64_t)N + 63u) / 64u), cap = max_workgroups ? max_workgroups : NR_DEFAULT_WG;
+    const unsigned grid = blocks < cap ? blocks : cap;
+    hipStream_t st = (hipStream_t)stream;
+    if (desc->precision) return desc->out_dim == 4 ? launch_render<_Float16, 3>(p, m, q, grid, lds, st) : launch_render<_Float16, 4>(p, m, q, grid, lds, st);
+    return desc->out_dim == 4 ? launch_render<float, 3>(p, m, q, grid, lds, st) : launch_render<float, 4>(p, m, q, grid, lds, st);
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@
                                  sigma_net weight and bias and sigma_scale -- only those autograd asks for.
   bind_nerf_network(ref)         rebinds common_forward and local_geometry_forward of a constructed reference _NeRFNetwork to
                                  nerf_field; the reference's own Parameters are read in place (optimizer, checkpoints untouched).
-                                 With cuda_ray it also rebinds update_extra_state to the native occupancy update (occupancy.py, B13).
+                                 With cuda_ray it also rebinds update_extra_state to the native occupancy update (occupancy.py, B13)
+                                 and run_cuda to the one-launch inference render (nerf_render.py, B14).
 Precision follows autocast: under torch.autocast(fp16) the kernels mirror the reference's fp16 rounding points (f16 MFMA, fp32
 accumulation), otherwise they compute in exact f32.  The arithmetic is csrc/nerf_field.hip; no CPU fallback.  Every buffer is checked
 (CUDA, contiguous, dtype, size) and a violation raises RuntimeError before any launch.
@@ -290,6 +291,7 @@ def bind_nerf_network(ref):
     ref.common_forward = common_forward
     ref.local_geometry_forward = local_geometry_forward
     _bind_update_extra_state(ref)
+    _bind_run_cuda(ref)
     ref._dwg_nerf_bound = True
     ref._dwg_nerf_unbound = None
     return None
@@ -362,9 +364,25 @@ def _bind_update_extra_state(ref):
     ref.update_extra_state = update_extra_state
 
 
+def _bind_run_cuda(ref):
+    """Install run_cuda on a bound network with cuda_ray: nerf_render.run_cuda, which renders an evaluation view (not training, shading
+    'albedo', no perturbation, CUDA fp32 rays, no autocast or fp16 autocast) in one launch and hands every other call to the original
+    method unchanged."""
+    if "run_cuda" in ref.__dict__ or not getattr(ref, "cuda_ray", False) or not hasattr(type(ref), "run_cuda"):
+        return
+    from . import nerf_render
+    orig_run = ref.run_cuda
+
+    def run_cuda(rays_o, rays_d, *args, **kwargs):
+        return nerf_render.run_cuda(ref, orig_run, rays_o, rays_d, *args, **kwargs)
+
+    run_cuda.__wrapped__ = orig_run
+    ref.run_cuda = run_cuda
+
+
 def unbind_nerf_network(ref):
     """Undo bind_nerf_network (the instance attributes go; the class methods show through again)."""
-    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "_dwg_occupancy"):
+    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "run_cuda", "_dwg_occupancy"):
         if name in ref.__dict__:
             del ref.__dict__[name]
     ref._dwg_nerf_bound = False

@@ -14,7 +14,9 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              trainer.py:499-501), then dreamwaltz_g_amd.nerf.bind_nerf_network rebinds common_forward and
                                              local_geometry_forward of that object to the fused field kernel (grid encoding -> sigma_net ->
                                              density / albedo); density, forward and normal reach it through them; with cuda_ray it also installs
-                                             update_extra_state on the native occupancy update (B13, dreamwaltz_g_amd.occupancy).  The
+                                             update_extra_state on the native occupancy update (B13, dreamwaltz_g_amd.occupancy) and
+                                             run_cuda on the one-launch inference render (B14, dreamwaltz_g_amd.nerf_render: an evaluation
+                                             view with shading 'albedo'; shading != 'albedo' in eval stays on the reference's loop).  The
                                              network's own Parameters are read in place.  What the kernel does not cover (dual_mlp / dual_enc,
                                              density_prior smpl, a decoder_layer, a non-grid backbone) stays unbound with the reason in
                                              `_dwg_nerf_unbound`.  DWG_BIND_NERF=0: nothing is bound
