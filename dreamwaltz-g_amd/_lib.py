@@ -181,6 +181,8 @@ SIGNATURES = {
     "dwg_attention_split_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dwg_attention_forward_ws": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
                                                 _vp, _i64, _i64, _f32, _vp, _sz, _vp]),
+    "dwg_attention_forward_pairs_dt": (ctypes.c_int, [_i32] * 7 + [_vp, _i64, _i64, _i64] * 4 + [_f32, _vp]),
+    "dwg_attention_forward_pairs_ws": (ctypes.c_int, [_i32] * 7 + [_vp, _i64, _i64, _i64] * 4 + [_f32, _vp, _sz, _vp]),
     "dwg_softmax_rows_forward": (ctypes.c_int, [_i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp]),
     "dwg_softmax_rows_backward": (ctypes.c_int, [_i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "dwg_groupnorm_forward_dt": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp]),
@@ -194,6 +196,7 @@ SIGNATURES = {
     "dwg_mlp_wgrad_workspace_floats": (_sz, [_i32]),
     "dwg_mlp_wgrad": (ctypes.c_int, [_i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
     "dwg_concat_channels": (ctypes.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "dwg_concat_channels_bcast": (ctypes.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "dwg_add_bf16": (ctypes.c_int, [_i64, _vp, _vp, _vp, _vp]),
     "dwg_interleave2x2": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dwg_cast_f32_to_bf16": (ctypes.c_int, [_i64, _vp, _vp, _vp]),

@@ -39,6 +39,8 @@ struct AttnP {
     long long ldq, ldk, ldv, ldo;          // row strides (elements)
     long long bq, bk, bv, bo;              // per-image strides (elements); head h starts at column h*d
     float scale_log2;                      // softmax scale * log2(e)
+    int Bq;                                // two-level batch: image b = (r, v) = (b / Bq, b % Bq) starts at r * o? + v * b? (Bq = the image count
+    long long oq, ok, ov, oo;              //      and r = 0 for the plain entry points; oq = 0: the R entries of a view share its queries)
 };
 
 // DK = head dim padded to a multiple of 16 (contraction of QK^T), DV = padded to a multiple of 32 (rows of O^T).
@@ -58,10 +60,11 @@ __global__ __launch_bounds__(256, 2) void k_flash_fwd(AttnP p) {   // 2 waves pe
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, ql = lane & 31;
     const int img = blockIdx.y / p.H, head = blockIdx.y % p.H;
     const int q0 = blockIdx.x * 128 + wave * 32;
-    const HT* Q = p.Q + img * p.bq + (long long)head * p.d;
-    const HT* K = p.K + img * p.bk + (long long)head * p.d;
-    const HT* V = p.V + img * p.bv + (long long)head * p.d;
-    HT* O = p.O + img * p.bo + (long long)head * p.d;
+    const int ro = img / p.Bq, vi = img - ro * p.Bq;
+    const HT* Q = p.Q + ro * p.oq + vi * p.bq + (long long)head * p.d;
+    const HT* K = p.K + ro * p.ok + vi * p.bk + (long long)head * p.d;
+    const HT* V = p.V + ro * p.ov + vi * p.bv + (long long)head * p.d;
+    HT* O = p.O + ro * p.oo + vi * p.bo + (long long)head * p.d;
 
     // this lane's query row as MFMA B-operand fragments: element e of step s = Q[q][16 s + 8 half + e]
     bf16x8 qf[NKS];
@@ -236,13 +239,28 @@ __global__ __launch_bounds__(256, 2) void k_flash_fwd(AttnP p) {   // 2 waves pe
 extern "C" {
 
 #ifdef DWG_ATTN_F16_TU
+#define DWG_ATTN_PAIRS_FN dwg_attention_pairs_f16
+#else
+#define DWG_ATTN_PAIRS_FN dwg_attention_pairs_bf16
+#endif
+#define DWG_ATTN_PAIRS_ARGS                                                                                                                   \
+    int32_t R, int32_t Bq, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void *Q, int64_t ldq, int64_t bq, int64_t oq, const void *K,   \
+        int64_t ldk, int64_t bk, int64_t ok, const void *V, int64_t ldv, int64_t bv, int64_t ov, void *O, int64_t ldo, int64_t bo, int64_t oo, \
+        float scale
+
+int DWG_ATTN_PAIRS_FN(DWG_ATTN_PAIRS_ARGS, dwg_stream_t stream_);
+
+#ifdef DWG_ATTN_F16_TU
 int dwg_attention_forward_f16(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq,
                               const void* K, int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O, int64_t ldo,
                               int64_t bo, float scale, dwg_stream_t stream_) {
+    return dwg_attention_pairs_f16(1, B, H, Nq, Nk, d, Q, ldq, bq, 0, K, ldk, bk, 0, V, ldv, bv, 0, O, ldo, bo, 0, scale, stream_);
+}
 #else
 int dwg_attention_forward_f16(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq,
                               const void* K, int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O, int64_t ldo,
                               int64_t bo, float scale, dwg_stream_t stream_);         // attention_f16.hip
+int dwg_attention_pairs_f16(DWG_ATTN_PAIRS_ARGS, dwg_stream_t stream_);               // attention_f16.hip
 
 int dwg_attention_forward_x(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq,
                             const void* K, int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O, int64_t ldo,
@@ -252,6 +270,7 @@ size_t dwg_attention_split_workspace_bytes_x(int32_t B, int32_t H, int32_t Nq, i
 int dwg_attention_forward_x_ws(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq, const void* K,
                                int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O, int64_t ldo, int64_t bo, float scale,
                                void* workspace, size_t workspace_bytes, dwg_stream_t stream_);
+int dwg_attention_pairs_x_ws(DWG_ATTN_PAIRS_ARGS, void* workspace, size_t workspace_bytes, dwg_stream_t stream_);
 
 size_t dwg_attention_split_workspace_bytes(int32_t dtype, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d) {
     return dtype == DWG_DTYPE_F32X ? dwg_attention_split_workspace_bytes_x(B, H, Nq, Nk, d) : 0;
@@ -274,15 +293,36 @@ int dwg_attention_forward_dt(int32_t dtype, int32_t B, int32_t H, int32_t Nq, in
     return dwg_attention_forward(B, H, Nq, Nk, d, Q, ldq, bq, K, ldk, bk, V, ldv, bv, O, ldo, bo, scale, stream);
 }
 
+int dwg_attention_forward_pairs_ws(int32_t dtype, DWG_ATTN_PAIRS_ARGS, void* workspace, size_t workspace_bytes, dwg_stream_t stream) {
+#define DWG_ATTN_PAIRS_PASS R, Bq, H, Nq, Nk, d, Q, ldq, bq, oq, K, ldk, bk, ok, V, ldv, bv, ov, O, ldo, bo, oo, scale
+    if (dtype == DWG_DTYPE_F32X) return dwg_attention_pairs_x_ws(DWG_ATTN_PAIRS_PASS, workspace, workspace_bytes, stream);
+    if (dtype == DWG_DTYPE_F16) return dwg_attention_pairs_f16(DWG_ATTN_PAIRS_PASS, stream);
+    if (dtype != DWG_DTYPE_BF16) return DWG_E_ARG;
+    return dwg_attention_pairs_bf16(DWG_ATTN_PAIRS_PASS, stream);
+}
+
+int dwg_attention_forward_pairs_dt(int32_t dtype, DWG_ATTN_PAIRS_ARGS, dwg_stream_t stream) {
+    return dwg_attention_forward_pairs_ws(dtype, DWG_ATTN_PAIRS_PASS, nullptr, 0, stream);
+}
+
 int dwg_attention_forward(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq,
                           const void* K, int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O, int64_t ldo,
                           int64_t bo, float scale, dwg_stream_t stream_) {
+    return dwg_attention_pairs_bf16(1, B, H, Nq, Nk, d, Q, ldq, bq, 0, K, ldk, bk, 0, V, ldv, bv, 0, O, ldo, bo, 0, scale, stream_);
+}
 #endif
-    if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || d <= 0 || d % 8 || d > 160 || !Q || !K || !V || !O) return DWG_E_ARG;
-    if ((ldq | ldk | ldv | ldo | bq | bk | bv | bo) % 8) return DWG_E_ARG;   // 16-byte aligned rows
+
+// The two-level batch (include/dwg_nn.h dwg_attention_forward_pairs_dt): image (r, v) of R x Bq; grid and per-workgroup arithmetic are those of
+// the plain launch over B = R Bq images -- only the base addresses differ
+int DWG_ATTN_PAIRS_FN(DWG_ATTN_PAIRS_ARGS, dwg_stream_t stream_) {
+    if (R <= 0 || Bq <= 0 || H <= 0 || (long long)R * Bq * H > 65535) return DWG_E_ARG;          // one grid row per (image, head)
+    const int B = R * Bq;
+    if (Nq <= 0 || Nk <= 0 || d <= 0 || d % 8 || d > 160 || !Q || !K || !V || !O) return DWG_E_ARG;
+    if ((ldq | ldk | ldv | ldo | bq | bk | bv | bo | oq | ok | ov | oo) % 8) return DWG_E_ARG;   // 16-byte aligned rows
+    if (R > 1 && (ok == 0 || ov == 0 || oo == 0)) return DWG_E_ARG;          // only the queries may be shared by the outer entries
     if (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) % 16) return DWG_E_ARG;
     AttnP p{(const HT*)Q, (const HT*)K, (const HT*)V, (HT*)O, Nq, Nk, H, d, ldq, ldk, ldv, ldo, bq, bk, bv, bo,
-            scale * 1.4426950408889634f};
+            scale * 1.4426950408889634f, Bq, oq, ok, ov, oo};
     dim3 grid(dwg_cdiv(Nq, 128), B * H), block(256);
     hipStream_t stream = (hipStream_t)stream_;
     // algorithmic flops of the launch (QK^T and PV on the logical head size; the padded tile columns are not counted)

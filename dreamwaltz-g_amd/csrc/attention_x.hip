@@ -32,6 +32,8 @@ struct AttnXP {
     int nsplit;                            // > 1: the keys are split into nsplit ranges (blockIdx.z); a workgroup writes its UNNORMALISED
     float* ws;                             //      partial (O, running max, denominator) to ws[split][image*head][query][dvw] and
     int dvw;                               //      k_flash_merge_x combines the ranges in split order
+    int Bq;                                // two-level batch: image b = (r, v) = (b / Bq, b % Bq) starts at r * o? + v * b? (Bq = the image count
+    long long oq, ok, ov, oo;              //      and r = 0 for the plain entry points; oq = 0: the R entries of a view share its queries)
 };
 
 // DK = head dim padded to a multiple of 16, DV = padded to a multiple of 32.
@@ -54,10 +56,11 @@ __global__ __launch_bounds__(256, MINB) void k_flash_fwd_x(AttnXP p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, ql = lane & 31;
     const int img = blockIdx.y / p.H, head = blockIdx.y % p.H;
     const int q0 = blockIdx.x * 128 + wave * 32;
-    const dwg_xs* Q = p.Q + img * p.bq + (long long)head * p.d;
-    const dwg_xs* K = p.K + img * p.bk + (long long)head * p.d;
-    const dwg_xs* V = p.V + img * p.bv + (long long)head * p.d;
-    dwg_xs* O = p.O + img * p.bo + (long long)head * p.d;
+    const int ro = img / p.Bq, vi = img - ro * p.Bq;
+    const dwg_xs* Q = p.Q + ro * p.oq + vi * p.bq + (long long)head * p.d;
+    const dwg_xs* K = p.K + ro * p.ok + vi * p.bk + (long long)head * p.d;
+    const dwg_xs* V = p.V + ro * p.ov + vi * p.bv + (long long)head * p.d;
+    dwg_xs* O = p.O + ro * p.oo + vi * p.bo + (long long)head * p.d;
 
     // this lane's query row as MFMA B-operand fragments, both planes: element e of step s = Q[q][16 s + 8 half + e]
     h8 qh[NKS], qlo[NKS];
@@ -306,10 +309,11 @@ __global__ __launch_bounds__(256, MINB) void k_flash_fwd_x2(AttnXP p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, ql = lane & 31;
     const int img = blockIdx.y / p.H, head = blockIdx.y % p.H;
     const int q0 = blockIdx.x * 128 + wave * 32;
-    const dwg_xs* Q = p.Q + img * p.bq + (long long)head * D;
-    const dwg_xs* K = p.K + img * p.bk + (long long)head * D;
-    const dwg_xs* V = p.V + img * p.bv + (long long)head * D;
-    dwg_xs* O = p.O + img * p.bo + (long long)head * D;
+    const int ro = img / p.Bq, vi = img - ro * p.Bq;
+    const dwg_xs* Q = p.Q + ro * p.oq + vi * p.bq + (long long)head * D;
+    const dwg_xs* K = p.K + ro * p.ok + vi * p.bk + (long long)head * D;
+    const dwg_xs* V = p.V + ro * p.ov + vi * p.bv + (long long)head * D;
+    dwg_xs* O = p.O + ro * p.oo + vi * p.bo + (long long)head * D;
 
     // LDS: zeros everywhere (pad columns are multiplied), then the ones column of both V hi planes -- and, where the head size leaves a pad
     // column in the K rows (D = 40 in 48), a ones column there too: the query's element D then carries minus the running maximum INTO the
@@ -598,7 +602,8 @@ __global__ __launch_bounds__(256) void k_flash_merge_x(AttnXP p, int BH, int DV)
     const float inv = L > 0.f ? 1.f / L : 0.f;
     const float out[4] = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
     const int img = bh / p.H, head = bh % p.H;
-    dwg_xs* O = p.O + img * p.bo + (long long)head * p.d;
+    const int ro = img / p.Bq, vi = img - ro * p.Bq;
+    dwg_xs* O = p.O + ro * p.oo + vi * p.bo + (long long)head * p.d;
     dwg_x_put4(O + (long long)q * p.ldo, 4 * g, out);
 }
 
@@ -624,14 +629,14 @@ size_t dwg_attention_split_workspace_bytes_x(int32_t B, int32_t H, int32_t Nq, i
     return sp > 1 ? (size_t)sp * B * H * Nq * (attn_dv(d) + 4) * sizeof(float) : 0;
 }
 
-int dwg_attention_forward_x_ws(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq, const void* K,
-                               int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O, int64_t ldo, int64_t bo, float scale,
-                               void* workspace, size_t workspace_bytes, dwg_stream_t stream_);
+int dwg_attention_pairs_x_ws(int32_t R, int32_t Bq, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq, int64_t oq,
+                             const void* K, int64_t ldk, int64_t bk, int64_t ok, const void* V, int64_t ldv, int64_t bv, int64_t ov, void* O,
+                             int64_t ldo, int64_t bo, int64_t oo, float scale, void* workspace, size_t workspace_bytes, dwg_stream_t stream_);
 
 int dwg_attention_forward_x(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq, const void* K,
                             int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O, int64_t ldo, int64_t bo, float scale,
                             dwg_stream_t stream_) {
-    return dwg_attention_forward_x_ws(B, H, Nq, Nk, d, Q, ldq, bq, K, ldk, bk, V, ldv, bv, O, ldo, bo, scale, nullptr, 0, stream_);
+    return dwg_attention_pairs_x_ws(1, B, H, Nq, Nk, d, Q, ldq, bq, 0, K, ldk, bk, 0, V, ldv, bv, 0, O, ldo, bo, 0, scale, nullptr, 0, stream_);
 }
 
 // `workspace` (dwg_attention_split_workspace_bytes_x bytes, or NULL): with it, launches whose query blocks do not fill the chip split the
@@ -640,11 +645,23 @@ int dwg_attention_forward_x(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_
 int dwg_attention_forward_x_ws(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq, const void* K,
                                int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O, int64_t ldo, int64_t bo, float scale,
                                void* workspace, size_t workspace_bytes, dwg_stream_t stream_) {
+    return dwg_attention_pairs_x_ws(1, B, H, Nq, Nk, d, Q, ldq, bq, 0, K, ldk, bk, 0, V, ldv, bv, 0, O, ldo, bo, 0, scale, workspace, workspace_bytes,
+                                    stream_);
+}
+
+// The two-level batch (include/dwg_nn.h dwg_attention_forward_pairs_ws): image (r, v) of R x Bq; the grid, the split choice and every
+// workgroup's arithmetic are those of the plain launch over B = R Bq images -- only the base addresses differ
+int dwg_attention_pairs_x_ws(int32_t R, int32_t Bq, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq, int64_t bq, int64_t oq,
+                             const void* K, int64_t ldk, int64_t bk, int64_t ok, const void* V, int64_t ldv, int64_t bv, int64_t ov, void* O,
+                             int64_t ldo, int64_t bo, int64_t oo, float scale, void* workspace, size_t workspace_bytes, dwg_stream_t stream_) {
+    if (R <= 0 || Bq <= 0 || H <= 0 || (long long)R * Bq * H > 65535) return DWG_E_ARG;          // one grid row per (image, head)
+    const int B = R * Bq;
     if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || d <= 0 || d % 8 || d > 160 || !Q || !K || !V || !O) return DWG_E_ARG;
-    if ((ldq | ldk | ldv | ldo | bq | bk | bv | bo) % 8) return DWG_E_ARG;   // whole 8-channel groups
+    if ((ldq | ldk | ldv | ldo | bq | bk | bv | bo | oq | ok | ov | oo) % 8) return DWG_E_ARG;   // whole 8-channel groups
+    if (R > 1 && (ok == 0 || ov == 0 || oo == 0)) return DWG_E_ARG;          // only the queries may be shared by the outer entries
     if (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) % 16) return DWG_E_ARG;
     AttnXP p{(const dwg_xs*)Q, (const dwg_xs*)K, (const dwg_xs*)V, (dwg_xs*)O, Nq, Nk, H, d, ldq, ldk, ldv, ldo, bq, bk, bv, bo,
-             scale * 1.4426950408889634f, 1, nullptr, 0};
+             scale * 1.4426950408889634f, 1, nullptr, 0, Bq, oq, ok, ov, oo};
     int sp = workspace ? attn_splits(B, H, Nq, Nk, attn_kt(d)) : 1;
     const int DVp = attn_dv(d);
     if (sp > 1 && (((uintptr_t)workspace & 15) || (size_t)sp * B * H * Nq * (DVp + 4) * sizeof(float) > workspace_bytes)) sp = 1;

@@ -708,6 +708,19 @@ __global__ __launch_bounds__(256) void k_concat_channels(long long rows, int Ca,
     }
 }
 
+// the same with b broadcast over row blocks: out[r][Ca:Ca+Cb] = b[r % rows_b]
+__global__ __launch_bounds__(256) void k_concat_channels_bcast(long long rows, long long rows_b, int Ca, int Cb, const __bf16* __restrict__ a,
+                                                               const __bf16* __restrict__ b, __bf16* __restrict__ out) {
+    const int C8 = (Ca + Cb) / 8, A8 = Ca / 8;
+    const long long n = rows * C8;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        long long r = i / C8; int c = (int)(i - r * C8);
+        bf16x8_t v = c < A8 ? *reinterpret_cast<const bf16x8_t*>(a + r * Ca + (long long)c * 8)
+                            : *reinterpret_cast<const bf16x8_t*>(b + (r % rows_b) * Cb + (long long)(c - A8) * 8);
+        *reinterpret_cast<bf16x8_t*>(out + r * (Ca + Cb) + (long long)c * 8) = v;
+    }
+}
+
 // out = a + b (bf16, n % 8 == 0)
 __global__ __launch_bounds__(256) void k_add_bf16(long long n8, const __bf16* __restrict__ a, const __bf16* __restrict__ b,
                                                   __bf16* __restrict__ out) {
@@ -1072,6 +1085,15 @@ int dwg_concat_channels(int64_t rows, int32_t Ca, int32_t Cb, const void* a, con
     if (rows == 0) return DWG_OK;
     DWG_LAUNCH("concat_channels", k_concat_channels, dim3(grid_for(rows * ((Ca + Cb) / 8))), dim3(256), 0, (hipStream_t)stream,
                (long long)rows, Ca, Cb, (const __bf16*)a, (const __bf16*)b, (__bf16*)out);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_concat_channels_bcast(int64_t rows, int64_t rows_b, int32_t Ca, int32_t Cb, const void* a, const void* b, void* out, dwg_stream_t stream) {
+    if (rows < 0 || rows_b <= 0 || rows % rows_b || Ca <= 0 || Cb <= 0 || Ca % 8 || Cb % 8 || !a || !b || !out) return DWG_E_ARG;
+    if (rows == 0) return DWG_OK;
+    DWG_LAUNCH("concat_channels", k_concat_channels_bcast, dim3(grid_for(rows * ((Ca + Cb) / 8))), dim3(256), 0, (hipStream_t)stream,
+               (long long)rows, (long long)rows_b, Ca, Cb, (const __bf16*)a, (const __bf16*)b, (__bf16*)out);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

@@ -1695,6 +1695,9 @@ size_t DWG_GEMM_WS_FN(const dwg_gemm_desc* d) {
     d = &xd;
 #endif
     if (!d || d->M <= 0 || d->N <= 0 || !slabs_possible(d)) return 0;
+    dwg_gemm_desc pd = *d;                 // the descriptor the choices are made for (dwg_gemm.h plan_m)
+    if (d->plan_m > d->M) pd.M = d->plan_m;
+    d = &pd;
     int sk = splitk_of(d);
     if (d->dtype == DWG_DTYPE_HALF && d->splitk == 0 && d->act != DWG_ACT_GEGLU_PAIR) {
         int bsk = 1;
@@ -1714,7 +1717,7 @@ int DWG_GEMM_FN(const dwg_gemm_desc* d, dwg_stream_t stream_) {
     d = &xd;
 #endif
     if (!d || !d->A || !d->B || !d->C) return DWG_E_ARG;
-    if (d->M < 0 || d->N < 0 || d->K < 0 || d->batch1 < 1 || d->batch2 < 1) return DWG_E_ARG;
+    if (d->M < 0 || d->N < 0 || d->K < 0 || d->batch1 < 1 || d->batch2 < 1 || d->plan_m < 0) return DWG_E_ARG;
     if (d->M == 0 || d->N == 0) return DWG_OK;
     if (d->dtype != DWG_DTYPE_F32 && d->dtype != DWG_DTYPE_HALF) return DWG_E_ARG;
     if (d->splitk > 1 && !d->workspace && (d->out_dtype != DWG_DTYPE_F32 || d->bias || d->residual || d->act)) return DWG_E_ARG;
@@ -1746,7 +1749,9 @@ int DWG_GEMM_FN(const dwg_gemm_desc* d, dwg_stream_t stream_) {
     p.conv.A2 = d->A2; p.conv.cin1 = d->A2 ? d->conv_cin1 : d->conv_cin;
     p.bias_row_div = d->bias_row_div; p.bias_ld = d->bias_ld > 0 ? d->bias_ld : d->N;
     Plan pl;
-    const int rc = make_plan(d, p, pl);
+    dwg_gemm_desc pd = *d;                 // family, tile and split-K factor are chosen for plan_m rows (dwg_gemm.h); the launch covers M
+    if (d->plan_m > d->M) pd.M = d->plan_m;
+    const int rc = make_plan(&pd, p, pl);
     if (rc != DWG_OK) return rc;
     p.splitk = pl.splitk;
     p.ws = pl.slabs ? reinterpret_cast<float*>(d->workspace) : nullptr;

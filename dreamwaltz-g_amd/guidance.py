@@ -129,8 +129,10 @@ class ControlNetScoreDistillation:
         self.image_hw = image_hw
         down = 2 ** (len(self.vae_cfg.block_out_channels) - 1)
         self.latent_hw = image_hw // down
+        # the CFG entries of a view share everything in front of the first cross-attention (sd15.DenoiserPlan `shared_prefix`); the exact-f32
+        # plans, whose attention is three dwg_gemm launches over image x head, keep the whole CFG batch
         self.denoiser = sd15.DenoiserPlan(self.unet_cfg, unet_sd, controlnet_sd, self.device, batch=2 * self.views, latent_hw=self.latent_hw,
-                                          text_len=text_len, dtype=self.dtype_name, views=self.views,
+                                          text_len=text_len, dtype=self.dtype_name, views=self.views, shared_prefix=self.dtype_name != "f32",
                                           weights=shared.denoiser.weights if shared is not None else None)      # CLIP's 77 tokens; static
         self.vae = sd15.VAEEncoderPlan(self.vae_cfg, vae_sd, self.device, image_hw=image_hw, dtype=self.dtype_name, batch=self.views,
                                        weights=shared.vae.weights if shared is not None else None)
@@ -321,13 +323,17 @@ class ControlNetScoreDistillation:
     # -- controlnet.py:83-114 --------------------------------------------------------------------------------------------
     @torch.no_grad()
     def _predict(self, latents_model_input, text_embeddings, cond_inputs):
-        """latents [2,4,h,w], text [2,77,768], cond_inputs: list[PIL] | PIL | tensor [1 or 2,3,8h,8w] in [0,1].  The timestep is
+        """latents [2,4,h,w] (or [1,4,h,w]: the shared-prefix plans), text [2,77,768], cond_inputs: list[PIL] | PIL | tensor [1 or 2,3,8h,8w] in [0,1].  The timestep is
         self.timestep, as in the reference."""
         _, _, lh, lw = latents_model_input.shape
         # the reference repeats the condition to the CFG batch (controlnet.py:50-54: batch_size = latents.size(0)); the repeated rows are identical
         # and only the first `views` are read below (the hint embedding is computed once per view and broadcast), so they are not made
         cond = self.prepare_condition(cond_inputs, cond_height=lh * self.vae_scale_factor, cond_width=lw * self.vae_scale_factor,
                                       batch_size=self.views, dtype=torch.float32)
+        if self.denoiser.shared_prefix and latents_model_input.shape[0] == 2 * self.views:
+            # this seam's caller in the reference hands over its own repeat of the noisy latents (basic.py:570 `torch.cat([latents_noisy] * 2)`):
+            # the plan takes one copy per view
+            latents_model_input = latents_model_input[:self.views]
         self.denoiser.set_inputs(latents_model_input, self.timestep, text_embeddings, cond[:self.views])
         return self.denoiser.run()
 
@@ -368,7 +374,8 @@ class ControlNetScoreDistillation:
         if self.do_classifier_free_guidance:
             text_keys = ('neg', 'text') if self.use_negative_text else ('null', 'text')
             text_embeddings = self.prepare_text_embeddings(text_embeds_dict, text_keys)
-            latents_model_input = torch.cat([latents_noisy] * 2, dim=0)
+            # (a shared-prefix plan takes the noisy latents once per view: the repeat of basic.py:570 is what it does not compute twice)
+            latents_model_input = latents_noisy if self.denoiser.shared_prefix else torch.cat([latents_noisy] * 2, dim=0)
         else:
             raise NotImplementedError("guidance_scale <= 1 (no classifier-free guidance): the plans are built for the CFG batch of 2")
         latents_model_input = self.scheduler.scale_model_input(latents_model_input, self.timestep)

@@ -563,6 +563,13 @@ class Builder:
     def __init__(self, plan: Plan, w: Weights, groups=32, prefix="net"):
         self.p, self.w, self.groups, self.prefix = plan, w, groups, prefix
         self.L = _lib.lib()
+        self.full_batch = None      # shared-prefix plans: the batch the layers in front of the widening point stand for (_plan_rows)
+
+    def _plan_rows(self, b, m):
+        """dwg_gemm's plan_m for a product of m rows over b images: in a shared-prefix plan the layers that run on the V rows the CFG entries
+        share are planned as the 2 V-row products they replace (same kernel family, tile and split-K factor, hence the same order of the sums:
+        a view's eps is, bit for bit, what the plan over the whole CFG batch gives); 0 everywhere else."""
+        return m * self.full_batch // b if self.full_batch and b < self.full_batch and self.full_batch % b == 0 else 0
 
     # -- contractions -------------------------------------------------------------------------------------------
     def _conv_tag(self, tag, KH, Ho, stride, dil, KW=None):
@@ -594,7 +601,15 @@ class Builder:
                 b = None
         conv = (C, H, W, Ho, Wo, KH, KW, stride, pt, pl, in_dilation)
         K = KH * KW * C
-        if r_batch_bcast:   # residual is [Vr,Ho,Wo,Cout], image b of the batch adds residual b % Vr (the ControlNet hint of view b % Vr is
+        if r_batch_bcast and KH * KW == 1 and stride == 1 and pad == 0 and pad_tl is None and upsample == 1 and in_dilation == 1 and out_hw is None:
+            # a 1 x 1 convolution IS the product of the [rows, C] matrix: the plain-row loader, the Vr images of an outer entry as one batch entry
+            Vr = int(residual.shape[0])
+            assert B % Vr == 0 and bias_img is None, (B, Vr)
+            Mr = Vr * H * W
+            d = gemm.gemm_raw(x, wt, y, Mr, Cout, K, (C, 1), (K, 1), Cout, bias=b, residual=residual, ldr=Cout, act=act, batch=(B // Vr, 1),
+                              a_batch=(Mr * C, 0), c_batch=(Mr * Cout, 0), r_batch=(0, 0), name=self._conv_tag(tag, KH, Ho, stride, in_dilation, KW),
+                              run=False)
+        elif r_batch_bcast:   # residual is [Vr,Ho,Wo,Cout], image b of the batch adds residual b % Vr (the ControlNet hint of view b % Vr is
             # shared by the CFG entries of that view): a batched GEMM, one image per batch entry, batch = (B / Vr) x Vr
             Vr = int(residual.shape[0])
             assert B % Vr == 0, (B, Vr)
@@ -610,7 +625,7 @@ class Builder:
                 kw = dict(bias=b)
             d = gemm.gemm_raw(x, wt, y, B * Ho * Wo, Cout, K, (0, 1), (K, 1), Cout, residual=residual,
                               ldr=Cout if residual is not None else 0, act=act, conv=conv, conv_upsample=upsample,
-                              name=self._conv_tag(tag, KH, Ho, stride, in_dilation, KW), run=False, **kw)
+                              name=self._conv_tag(tag, KH, Ho, stride, in_dilation, KW), plan_m=self._plan_rows(B, B * Ho * Wo), run=False, **kw)
         self.p.add_gemm(d)
         return y
 
@@ -620,8 +635,19 @@ class Builder:
         N = wt.shape[0]
         Nout = N // 2 if act == "geglu_pair" else N
         y = self.p.buf(*x.shape[:-1], Nout, dtype=out_dtype)
+        if residual is not None and residual.numel() != M * Nout:
+            # the residual has M / R rows and row block r of the output adds all of them (the V-row stream of a shared-prefix plan widening to
+            # its 2 V CFG entries): batch = (R, 1) with the residual's outer stride 0
+            R = (M * Nout) // residual.numel()
+            Mr = M // R
+            assert Mr * R == M and residual.numel() == Mr * Nout and x.is_contiguous(), (M, Nout, tuple(residual.shape))
+            d = gemm.gemm_raw(x, wt, y, Mr, N, K, (K, 1), (wt.stride(0), 1), Nout, bias=bias, residual=residual, ldr=Nout, act=act, batch=(R, 1),
+                              a_batch=(Mr * K, 0), c_batch=(Mr * Nout, 0), r_batch=(0, 0), name=tag, run=False)
+            self.p.add_gemm(d)
+            return y
         d = gemm.gemm_raw(x, wt, y, M, N, K, (K, 1), (wt.stride(0), 1), Nout, bias=bias, residual=residual,
-                          ldr=Nout if residual is not None else 0, act=act, name=tag, run=False)
+                          ldr=Nout if residual is not None else 0, act=act, name=tag, plan_m=self._plan_rows(x.shape[0], M) if x.dim() > 2 else 0,
+                          run=False)
         self.p.add_gemm(d)
         return y
 
@@ -686,10 +712,23 @@ class Builder:
         return t[:numel]
 
     def attention(self, q, k, v, heads):
-        B, Nq, HD = q.shape
-        Nk, d = k.shape[1], HD // heads
+        """q [Bq, Nq, H d], k / v [B, Nk, H d] -> [B, Nq, H d].  B = R Bq with R > 1: batch row r Bq + i of k / v meets the queries of row i (the
+        CFG entries of a view share their queries where the stream of a shared-prefix plan widens)."""
+        Bq, Nq, HD = q.shape
+        B, Nk, d = k.shape[0], k.shape[1], HD // heads
         o = self.p.buf(B, Nq, HD)
         pp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        if B != Bq:
+            R = B // Bq
+            assert R * Bq == B and v.shape[0] == B, (B, Bq)
+            if self.p.dtype_name == "f32":
+                raise NotImplementedError("the exact-f32 plans run attention on dwg_gemm, whose two batch levels are image x head")
+            need = int(self.L.dwg_attention_split_workspace_bytes(self.p.dt, B, heads, Nq, Nk, d))
+            ws = self.p.buf((need + 3) // 4, dtype=torch.float32) if need > 0 else None
+            self.p.add_call(self.L.dwg_attention_forward_pairs_ws, self.p.dt, R, Bq, heads, Nq, Nk, d, pp(q), q.stride(1), q.stride(0), 0,
+                            pp(k), k.stride(1), k.stride(0), Bq * k.stride(0), pp(v), v.stride(1), v.stride(0), Bq * v.stride(0),
+                            pp(o), o.stride(1), o.stride(0), Bq * o.stride(0), float(d) ** -0.5, pp(ws) if ws is not None else None, need)
+            return o
         if self.p.dtype_name == "f32":
             # full-precision plans: S = Q K^T (batched over image x head) -> row softmax -> O = P V on the exact-f32 MFMA GEMM
             S = self._pooled("attn_S", B * heads * Nq * Nk, torch.float32)
@@ -719,6 +758,10 @@ class Builder:
         y = self.p.buf(*a.shape[:-1], Ca + Cb)
         pp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         k2 = self.p.esize // 2                      # the concat kernel moves 16-byte pieces of 2-byte elements: fp32 channels count twice
+        if b.shape[0] != a.shape[0]:                # a skip the CFG entries of a view share (shared-prefix plans): row i reads b's row i mod rows_b
+            assert a.shape[0] % b.shape[0] == 0 and a.shape[1:-1] == b.shape[1:-1], (tuple(a.shape), tuple(b.shape))
+            self.p.add_call(self.L.dwg_concat_channels_bcast, a.numel() // Ca, b.numel() // Cb, Ca * k2, Cb * k2, pp(a), pp(b), pp(y))
+            return y
         self.p.add_call(self.L.dwg_concat_channels, a.numel() // Ca, Ca * k2, Cb * k2, pp(a), pp(b), pp(y))
         return y
 
@@ -797,8 +840,11 @@ class Builder:
         return ent[0][..., o:o + 2 * c]
 
     def transformer(self, x, pre, text, heads):
+        """x [B,H,W,C], text [Bo,77,cross].  Bo = R B with R > 1 (the first transformer of a shared-prefix plan): everything up to the cross-attention's
+        queries runs on the B rows the CFG entries share, the cross-attention writes Bo rows and the residuals h and x are broadcast."""
         self.p.scope = pre
         B, H, W, C = x.shape
+        Bo = text.shape[0]
         n = self.groupnorm(x, pre + ".norm", 1e-6, False)
         h = self.conv(n, pre + ".proj_in", pad=0).view(B, H * W, C)
         t = pre + ".transformer_blocks.0"
@@ -815,7 +861,7 @@ class Builder:
         wg, bg = self.w.lin_geglu(t + ".ff.net.0.proj")
         g = self.linear(l3, wg, bias=bg, act="geglu_pair", tag="ff_in")       # GEGLU fused into the projection's epilogue
         h = self.linear(g, self.w.lin(t + ".ff.net.2"), bias=self.w.f32(t + ".ff.net.2.bias"), residual=h, tag="ff_out")
-        return self.conv(h.view(B, H, W, C), pre + ".proj_out", pad=0, residual=x)
+        return self.conv(h.view(Bo, H, W, C), pre + ".proj_out", pad=0, residual=x, r_batch_bcast=Bo != B)
 
 
 def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
@@ -885,10 +931,23 @@ class DenoiserPlan:
     Inputs (static buffers, overwritten before run()):  latents [B,h,w,8] (4 used), t_emb [B,320] x2, text [B,77,768],
     cond [V,8h,8w,8] (3 used; V = `views`, B = 2 V ordered [negative of view 0..V-1 | text of view 0..V-1]: the condition image of a
     view is identical for its CFG entries -- controlnet.py:60-72 repeats it -- so its embedding is computed once per view and
-    broadcast).  Output: eps [B,h,w,4] fp32.  `weights`: (UNet, ControlNet) `Weights` of another plan of the same dtype to share."""
+    broadcast).  Output: eps [B,h,w,4] fp32.  `weights`: (UNet, ControlNet) `Weights` of another plan of the same dtype to share.
 
-    def __init__(self, cfg: UNetConfig, unet_sd, cn_sd, device, batch=2, latent_hw=64, text_len=77, dtype="bf16", views=1, weights=None):
+    `shared_prefix`: the two CFG entries of a view get the SAME noisy latents, timestep and condition image (basic.py:570 repeats the
+    latents) and differ only in their text, which both networks first read in the cross-attention of their first transformer block.  With
+    the flag the plan takes the V noisy latents themselves ([V,h,w,8]) and runs everything before that point -- conv_in (+ hint), the
+    resnets in front of the first transformer, its GroupNorm / proj_in / self-attention / to_q, and the zero convolutions and skips of
+    those layers -- on V rows; the cross-attention runs each view's queries against both of its key / value sets and the stream is 2 V rows
+    from there on (the V-row residuals and the first skip are broadcast).  B must be 2 V; the 16-bit and f32x plans only."""
+
+    def __init__(self, cfg: UNetConfig, unet_sd, cn_sd, device, batch=2, latent_hw=64, text_len=77, dtype="bf16", views=1, weights=None,
+                 shared_prefix=False):
         self.cfg, self.device, self.B, self.hw, self.views = cfg, device, batch, latent_hw, int(views)
+        self.shared_prefix = bool(shared_prefix)
+        if self.shared_prefix and batch != 2 * self.views:
+            raise ValueError("a shared-prefix plan runs the CFG pair of each view: batch must be 2 * views, got batch %d for %d view(s)" % (batch, self.views))
+        if self.shared_prefix and dtype_name(dtype) == "f32":
+            raise NotImplementedError("shared_prefix: the exact-f32 plans run attention on dwg_gemm, whose two batch levels are image x head")
         self._temb_table = None
         self.temb_rows = 1001                 # timesteps the embedding table covers: 0 .. the scheduler's num_train_timesteps (guidance sets it)
         assert batch % self.views == 0, (batch, views)
@@ -905,8 +964,10 @@ class DenoiserPlan:
         self.weights = (wu, wc)     # kernel-layout weight tensors must outlive the plan that points at them
         bu, bc = Builder(p, wu, cfg.groups, "unet"), Builder(p, wc, cfg.groups, "cnet")
         pu, pc = Builder(self.pre, wu, cfg.groups, "unet"), Builder(self.pre, wc, cfg.groups, "cnet")
+        if self.shared_prefix:
+            bu.full_batch = bc.full_batch = batch
         B, hw = batch, latent_hw
-        self.latents = p.buf(B, hw, hw, _pad8(cfg.in_channels), zero=True)
+        self.latents = p.buf(self.views if self.shared_prefix else B, hw, hw, _pad8(cfg.in_channels), zero=True)
         self.text = p.buf(B, text_len, cfg.cross_dim)
         self.cond_scale = 2 ** (len(cfg.cond_channels) - 1)      # one stride-2 convolution per embedding level: 8 for SD-1.5
         self.cond = p.buf(self.views, hw * self.cond_scale, hw * self.cond_scale, _pad8(cfg.cond_in_channels), zero=True)
@@ -1013,8 +1074,11 @@ class DenoiserPlan:
         self._pre_ready, self._pre_event = True, ev
 
     def set_inputs(self, latents_nchw, t=None, text=None, cond_nchw=None):
-        """latents [B,4,h,w] fp32, t scalar / [V] (one per view, repeated over the CFG entries) / [B], text [B,77,768],
-        cond [V,3,8h,8w] in [0,1] (optional).  After a `prefetch()` only the latents are taken."""
+        """latents [B,4,h,w] fp32 ([V,4,h,w] for a shared-prefix plan: ONE per view, so that the CFG entries cannot be handed different ones),
+        t scalar / [V] (one per view, repeated over the CFG entries) / [B], text [B,77,768], cond [V,3,8h,8w] in [0,1] (optional).  After a
+        `prefetch()` only the latents are taken."""
+        if self.shared_prefix and latents_nchw.shape[0] != self.views:
+            raise ValueError("a shared-prefix plan takes one latent image per view (%d), got %d" % (self.views, latents_nchw.shape[0]))
         self.plan.store(self.latents, latents_nchw.permute(0, 2, 3, 1), self._lat_stage)
         if not self._pre_ready:
             self._store_prelude_inputs(t, text, cond_nchw)

@@ -81,6 +81,9 @@ int dwg_adam_step_groups_dev(int32_t count, const dwg_adam_group* groups, const 
 
 /* NHWC channel concat (torch.cat([h, skip], 1) of the UNet up blocks): out[r] = [a[r] | b[r]], bf16, Ca % 8 == Cb % 8 == 0. */
 int dwg_concat_channels(int64_t rows, int32_t Ca, int32_t Cb, const void* a, const void* b, void* out, dwg_stream_t stream);
+/* The same with a BROADCAST second operand: b has rows_b rows (rows % rows_b == 0) and out[r] = [a[r] | b[r % rows_b]] -- the decoder's last
+ * skip of a denoiser plan whose two classifier-free-guidance entries share it (rows are pixels: rows_b = views x H x W). */
+int dwg_concat_channels_bcast(int64_t rows, int64_t rows_b, int32_t Ca, int32_t Cb, const void* a, const void* b, void* out, dwg_stream_t stream);
 /* out = a + b on bf16 buffers (n % 8 == 0): gradient joins of the VAE-encoder backward. */
 int dwg_add_bf16(int64_t n, const void* a, const void* b, void* out, dwg_stream_t stream);
 /* out[b, 2i+py, 2j+px, :] = s<py><px>[b, i, j, :] -- NHWC bf16, C % 8 == 0.  Assembles the input gradient of a stride-2

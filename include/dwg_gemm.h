@@ -68,6 +68,10 @@ typedef struct dwg_gemm_desc {
     void* workspace;          /* optional split-K slab workspace (device, 16-byte aligned, else DWG_E_ARG), see dwg_gemm_workspace_bytes */
     size_t workspace_bytes;
     const char* name;         /* optional label for dwg_prof */
+    int32_t plan_m;           /* > M: choose the kernel family, tile and split-K factor as for a product of this many rows (0: of M).  A
+                                 caller that computes only some rows of a larger product -- the rows the classifier-free-guidance entries of
+                                 a denoiser plan share -- gets, row for row, the bits the whole product gives: the order of the sums over K
+                                 depends on those choices, not on how many rows are launched.  The workspace query counts plan_m rows. */
 } dwg_gemm_desc;
 
 int dwg_gemm(const dwg_gemm_desc* desc, dwg_stream_t stream);

@@ -76,6 +76,19 @@ size_t dwg_attention_split_workspace_bytes(int32_t dtype, int32_t B, int32_t H, 
 int dwg_attention_forward_ws(int32_t dtype, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq,
                              int64_t bq, const void* K, int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O,
                              int64_t ldo, int64_t bo, float scale, void* workspace, size_t workspace_bytes, dwg_stream_t stream);
+/* The fused attention over a TWO-LEVEL batch of R x Bq images, like dwg_gemm's batch1 x batch2: image (r, v) reads Q at r * oq + v * bq, K at
+ * r * ok + v * bk, V at r * ov + v * bv and writes O at r * oo + v * bo (elements, multiples of 8).  oq may be 0 -- the R entries of a view
+ * share its queries: the classifier-free-guidance pair of the denoiser, whose two entries differ only in their text, runs each view's
+ * queries against both of that view's key / value sets -- ok, ov and oo may not (DWG_E_ARG when R > 1).  Grid, key split and per-workgroup
+ * arithmetic are those of the entry points above over B = R Bq images (they ARE the R = 1 case): the results are bit-identical to theirs on
+ * Q materialised R times.  The workspace is sized by dwg_attention_split_workspace_bytes(dtype, R * Bq, ...). */
+int dwg_attention_forward_pairs_dt(int32_t dtype, int32_t R, int32_t Bq, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq,
+                                   int64_t bq, int64_t oq, const void* K, int64_t ldk, int64_t bk, int64_t ok, const void* V, int64_t ldv,
+                                   int64_t bv, int64_t ov, void* O, int64_t ldo, int64_t bo, int64_t oo, float scale, dwg_stream_t stream);
+int dwg_attention_forward_pairs_ws(int32_t dtype, int32_t R, int32_t Bq, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq,
+                                   int64_t bq, int64_t oq, const void* K, int64_t ldk, int64_t bk, int64_t ok, const void* V, int64_t ldv,
+                                   int64_t bv, int64_t ov, void* O, int64_t ldo, int64_t bo, int64_t oo, float scale, void* workspace,
+                                   size_t workspace_bytes, dwg_stream_t stream);
 /* P / dS have element type `dtype`; S / dP stay fp32 */
 int dwg_softmax_rows_forward_dt(int32_t dtype, int32_t rows, int32_t n, float scale, const float* S, int64_t lds, void* P,
                                 int64_t ldp, dwg_stream_t stream);
