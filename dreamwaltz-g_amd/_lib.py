@@ -101,6 +101,8 @@ SIGNATURES = {
     # include/dwg_nerf_render.h
     "dwg_nerf_render_infer": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, _vp, _vp, _vp, _u32, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _f32,
                                              _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "dwg_nerf_render_shaded": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, _vp, _vp, _vp, _u32, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _f32,
+                                              _u32, _u32, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _u32, _vp]),
     # include/dwg_pointcloud.h
     "dwg_pc_lattice_sigma": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "dwg_pc_select_workspace_bytes": (_sz, [ctypes.c_uint64]),

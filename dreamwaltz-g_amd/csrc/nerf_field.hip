@@ -17,6 +17,7 @@
 #include "../../include/dwg_nerf_render.h"
 #include "../../include/dwg_occupancy.h"
 #include "../../include/dwg_pointcloud.h"
+#include "fd_normal.h"
 #include "gridenc_common.h"
 #include "morton.h"
 #include "occupancy_common.h"
@@ -151,6 +152,15 @@ struct XOccupancy {                         // the jittered cell points of dwg_o
 struct XStaged {                            // the pending samples of the inference render, compacted into LDS in slot order
     const float* s;
     __device__ __forceinline__ float operator()(uint64_t p0, uint32_t i) const { return s[(uint32_t)p0 * 3u + i]; }
+};
+struct XStagedFd {                          // those samples (pass 0) or their shift pass - 1 of the finite-difference normal (fd_normal.h)
+    const float* s;
+    uint32_t pass;
+    float eps, bound;
+    __device__ __forceinline__ float operator()(uint64_t p0, uint32_t i) const {
+        const float v = s[(uint32_t)p0 * 3u + i];
+        return pass == 0u ? v : fd_shift(v, i % 3u, pass - 1u, eps, bound);
+    }
 };
 
 // x of the tile -> sx, the encoder's (x + bound) / (2 bound) -> sxn, the 64 x L lookups -> enc, then the layers; points at or past
@@ -332,6 +342,13 @@ struct RenderP {
     int32_t* counts;
 };
 
+struct ShadeP {                             // the shaded render (boundary B15): forward() of nerf_model.py:86-103 per sample
+    uint32_t shading;                       // 1 normal, 2 textureless, 3 lambertian
+    const float* light_d;                   // [3]; read for 2 and 3
+    float ratio, one_minus_ratio;           // ambient_ratio and the Python scalar 1 - ambient_ratio as torch hands it to the kernel
+    float eps, bound;                       // normal()'s epsilon; the clamp of the shifted points
+};
+
 // The statements of k_composite_rays (raymarch.hip) for one sample, in their order and without FP contraction, as that file compiles
 // them.  Returns true when the transmittance before the sample was below T_thresh (the sample is composited all the same).
 template <int NC>
@@ -349,13 +366,40 @@ __device__ __forceinline__ bool composite_sample(float sigma, const float (&rgb)
     return T < T_thresh;
 }
 
+// The colour of a sample from its density gradient g (fd_normal.h) and albedo: forward()'s statements for shading 'normal',
+// 'textureless' and 'lambertian', without FP contraction.  l = -light_d.
+template <int NC>
+__device__ __forceinline__ void shade_sample(const ShadeP& sh, float lx, float ly, float lz, float g0, float g1, float g2, const float (&alb)[NC],
+                                             float (&rgb)[NC]) {
+#pragma clang fp contract(off)
+    float n0, n1, n2;
+    fd_normalize(g0, g1, g2, n0, n1, n2);
+#pragma unroll
+    for (int k = 0; k < NC; ++k) rgb[k] = 0.f;
+    if (sh.shading == 1u) {
+        rgb[0] = (n0 + 1.f) / 2.f; rgb[1] = (n1 + 1.f) / 2.f; rgb[2] = (n2 + 1.f) / 2.f;
+        return;
+    }
+    const float dot = (n0 * lx + n1 * ly) + n2 * lz;
+    const float lam = sh.ratio + sh.one_minus_ratio * (dot < 0.f ? 0.f : dot);      // clamp(min=0): NaN stays NaN
+    if (sh.shading == 2u) { rgb[0] = lam; rgb[1] = lam; rgb[2] = lam; }
+    else {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) rgb[k] = alb[k] * lam;
+    }
+}
+
 // One ray per thread (NR_SLOTS slots).  A round: every thread marches its ray to the next sample (taking the workgroup's next ray from
 // the LDS cursor when its slot is free), the pending samples are compacted into `stage` in slot order, field_tile runs on every 64 of
 // them and each owner composites its sample from its row of the last layer's output.  Workgroup w of G owns the 64-ray blocks w, w + G,
 // ...: the cursor counts through them.  Which slot or round a ray lands in changes no arithmetic of the ray.
-template <typename T, int NC>
-__global__ __launch_bounds__(256) void k_nf_render(NfP p, MarchP m, RenderP q) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+//
+// SHADED (k_nf_render_shaded): field_tile runs seven times on every 64 pending samples, through XStagedFd: the samples, then their six
+// shifts.  The owner keeps the sample's density and albedo from pass 0, one density of each +- pair and the three components of the
+// gradient in named registers, and shades before it composites.  NC is the width of the image: with four channels the colour of
+// 'normal' and 'textureless' is the reference's zero pad in the fourth.
+template <typename T, int NC, bool SHADED>
+__device__ __forceinline__ void nf_render(const NfP& p, const MarchP& m, const RenderP& q, const ShadeP& sh, unsigned char* smem) {
     T* lds; float *bias, *sx, *sxn, *red;
     lds_carve(p, smem, lds, bias, sx, sxn, red);
     float* stage = red + NF_TILE;                                               // [NR_SLOTS][3]
@@ -366,6 +410,10 @@ __global__ __launch_bounds__(256) void k_nf_render(NfP p, MarchP m, RenderP q) {
     const float es = p.act == 2 ? expf(*p.sigma_scale) : 0.f;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const bool binarize = q.binarize != 0;
+    float lx = 0.f, ly = 0.f, lz = 0.f;                                         // -l
+    if constexpr (SHADED) {
+        if (sh.shading >= 2u) { lx = -sh.light_d[0]; ly = -sh.light_d[1]; lz = -sh.light_d[2]; }
+    }
     Ray ray = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float t = 0.f, far = 0.f, ws = 0.f, d = 0.f, col[NC];
 #pragma unroll
@@ -416,6 +464,44 @@ __global__ __launch_bounds__(256) void k_nf_render(NfP p, MarchP m, RenderP q) {
         if (pend) { stage[3 * pos] = cx; stage[3 * pos + 1] = cy; stage[3 * pos + 2] = cz; }
         __syncthreads();
         for (uint32_t base = 0; base < total; base += NF_TILE) {
+            if constexpr (SHADED) {
+                const bool mine = pend && pos - base < (uint32_t)NF_TILE;       // pos < base wraps past NF_TILE
+                const uint32_t r = pos - base;
+                float sigma = 0.f, s_pos = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f, alb[NC];
+#pragma unroll
+                for (int k = 0; k < NC; ++k) alb[k] = 0.f;
+                for (uint32_t pass = 0; pass < 7u; ++pass) {
+                    field_tile(p, XStagedFd{stage, pass, sh.eps, sh.bound}, (uint64_t)total, (uint64_t)base, lds, bias, sx, sxn);
+                    if (mine) {
+                        const T* o = lds + p.aoff[p.nl] + r * p.ast[p.nl];
+                        const float sg = nf_sigma(p, (float)o[0], sx + 3 * r, es);     // sx holds the shifted point: the prior is taken there
+                        if (pass == 0u) {
+                            sigma = sg;
+                            if (sh.shading == 3u) {
+#pragma unroll
+                                for (int k = 0; k < NC; ++k) {
+                                    float v = (float)o[1 + k];
+                                    if (p.sig) v = 1.f / (1.f + expf(-v));
+                                    alb[k] = (float)(T)v;
+                                }
+                            }
+                        } else if (pass & 1u) s_pos = sg;
+                        else {
+                            const float g = fd_gradient(s_pos, sg, sh.eps);
+                            if (pass == 2u) g0 = g; else if (pass == 4u) g1 = g; else g2 = g;
+                        }
+                    }
+                    __syncthreads();
+                }
+                if (mine) {
+                    float rgb[NC];
+                    shade_sample<NC>(sh, lx, ly, lz, g0, g1, g2, alb, rgb);
+                    const bool stop = composite_sample<NC>(sigma, rgb, t, dt, q.T_thresh, binarize, ws, d, col);
+                    ++cnt;
+                    if (stop || cnt >= q.max_steps) finish();
+                }
+                continue;
+            }
             field_tile(p, XStaged{stage}, (uint64_t)total, (uint64_t)base, lds, bias, sx, sxn);
             if (pend && pos - base < (uint32_t)NF_TILE) {                       // pos < base wraps past NF_TILE
                 const uint32_t r = pos - base;
@@ -435,6 +521,18 @@ __global__ __launch_bounds__(256) void k_nf_render(NfP p, MarchP m, RenderP q) {
             __syncthreads();
         }
     }
+}
+
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void k_nf_render(NfP p, MarchP m, RenderP q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    nf_render<T, NC, false>(p, m, q, ShadeP{}, smem);
+}
+
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void k_nf_render_shaded(NfP p, MarchP m, RenderP q, ShadeP sh) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    nf_render<T, NC, true>(p, m, q, sh, smem);
 }
 
 // One chunk [m0, m0 + n) of the backward.  partial: [gridDim.x][P] floats, overwritten when `first`, else added to.
@@ -665,6 +763,30 @@ int launch_render(const NfP& p, const MarchP& m, const RenderP& q, unsigned grid
     return DWG_OK;
 }
 
+template <typename T, int NC>
+int launch_render_shaded(const NfP& p, const MarchP& m, const RenderP& q, const ShadeP& sh, unsigned grid, size_t lds, hipStream_t st) {
+    static bool attr = false; lds_opt_in(&k_nf_render_shaded<T, NC>, attr);
+    DWG_LAUNCH("nf_render_shaded", (k_nf_render_shaded<T, NC>), dim3(grid), dim3(256), lds, st, p, m, q, sh);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+// the checks dwg_nerf_render_infer and dwg_nerf_render_shaded share; lds: the field's bytes in, the render's out
+int render_args(const dwg_nerf_field_desc* desc, NfP& p, size_t& lds, float bound, uint32_t max_steps, uint32_t C, uint32_t H) {
+    int rc = make_params(desc, p, lds);
+    if (rc) return rc;
+    if (!march_args_ok(bound, max_steps, C, H)) return DWG_E_ARG;
+    if (desc->raw || (desc->out_dim != 4 && desc->out_dim != 5)) return DWG_E_ARG;
+    lds += (NR_SLOTS * 3 + 16) * sizeof(float);
+    if (lds > 160 * 1024) return DWG_E_ARG;
+    return DWG_OK;
+}
+
+unsigned render_grid(uint32_t N, uint32_t max_workgroups) {
+    const uint32_t blocks = (uint32_t)(((uint64_t)N + 63u) / 64u), cap = max_workgroups ? max_workgroups : NR_DEFAULT_WG;
+    return blocks < cap ? blocks : cap;
+}
+
 }  // namespace
 
 extern "C" {
@@ -815,21 +937,39 @@ int dwg_nerf_render_infer(const dwg_nerf_field_desc* desc, const float* rays_o, 
                           uint32_t max_workgroups, dwg_stream_t stream) {
     NfP p;
     size_t lds = 0;
-    int rc = make_params(desc, p, lds);
+    int rc = render_args(desc, p, lds, bound, max_steps, C, H);
     if (rc) return rc;
-    if (!march_args_ok(bound, max_steps, C, H)) return DWG_E_ARG;
-    if (desc->raw || (desc->out_dim != 4 && desc->out_dim != 5)) return DWG_E_ARG;
-    lds += (NR_SLOTS * 3 + 16) * sizeof(float);
-    if (lds > 160 * 1024) return DWG_E_ARG;
     if (N == 0) return DWG_OK;
     if (!rays_o || !rays_d || !nears || !fars || !bitfield || !weights_sum || !depth || !image) return DWG_E_ARG;
     const MarchP m = make_march(bitfield, bound, contract, dt_gamma, max_steps, C, H);
     const RenderP q{rays_o, rays_d, nears, fars, N, max_steps, T_thresh, binarize, weights_sum, depth, image, counts};
-    const uint32_t blocks = (uint32_t)(((uint64_t)N + 63u) / 64u), cap = max_workgroups ? max_workgroups : NR_DEFAULT_WG;
-    const unsigned grid = blocks < cap ? blocks : cap;
+    const unsigned grid = render_grid(N, max_workgroups);
     hipStream_t st = (hipStream_t)stream;
     if (desc->precision) return desc->out_dim == 4 ? launch_render<_Float16, 3>(p, m, q, grid, lds, st) : launch_render<_Float16, 4>(p, m, q, grid, lds, st);
     return desc->out_dim == 4 ? launch_render<float, 3>(p, m, q, grid, lds, st) : launch_render<float, 4>(p, m, q, grid, lds, st);
+}
+
+int dwg_nerf_render_shaded(const dwg_nerf_field_desc* desc, const float* rays_o, const float* rays_d, const float* nears, const float* fars,
+                           uint32_t N, const uint8_t* bitfield, float bound, uint32_t contract, float dt_gamma, uint32_t max_steps, uint32_t C,
+                           uint32_t H, float T_thresh, uint32_t binarize, uint32_t shading, const float* light_d, float ambient_ratio,
+                           float epsilon, float* weights_sum, float* depth, float* image, int32_t* counts, uint32_t max_workgroups,
+                           dwg_stream_t stream) {
+    NfP p;
+    size_t lds = 0;
+    int rc = render_args(desc, p, lds, bound, max_steps, C, H);
+    if (rc) return rc;
+    if (shading < 1u || shading > 3u || (shading >= 2u && !light_d) || !(epsilon > 0.f)) return DWG_E_ARG;
+    if (shading == 3u && desc->out_dim == 5) return DWG_E_ARG;      // albedo [., 4] * lambertian plus the zero pad: five channels into four
+    if (N == 0) return DWG_OK;
+    if (!rays_o || !rays_d || !nears || !fars || !bitfield || !weights_sum || !depth || !image) return DWG_E_ARG;
+    const MarchP m = make_march(bitfield, bound, contract, dt_gamma, max_steps, C, H);
+    const RenderP q{rays_o, rays_d, nears, fars, N, max_steps, T_thresh, binarize, weights_sum, depth, image, counts};
+    // the field's own bound clamps the shifted points (normal() clamps to self.bound, which common_forward normalises by)
+    const ShadeP sh{shading, light_d, ambient_ratio, (float)(1.0 - (double)ambient_ratio), epsilon, desc->bound};
+    const unsigned grid = render_grid(N, max_workgroups);
+    hipStream_t st = (hipStream_t)stream;
+    if (desc->precision) return desc->out_dim == 4 ? launch_render_shaded<_Float16, 3>(p, m, q, sh, grid, lds, st) : launch_render_shaded<_Float16, 4>(p, m, q, sh, grid, lds, st);
+    return desc->out_dim == 4 ? launch_render_shaded<float, 3>(p, m, q, sh, grid, lds, st) : launch_render_shaded<float, 4>(p, m, q, sh, grid, lds, st);
 }
 
 }  // extern "C"

@@ -7,11 +7,10 @@
 // and the write pass gives each surviving lane the slot block base + (rounds and waves before it) + lanes below it in the ballot.
 // No atomic decides a slot.  The pointwise kernels are one lane per output element (or per point where a point's outputs depend on
 // each other); nothing here uses LDS beyond the scans' few words.
-#include <float.h>
-
 #include "dwg_common.h"
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_pointcloud.h"
+#include "fd_normal.h"
 #include "pointcloud_index.h"
 
 namespace {
@@ -144,15 +143,7 @@ __global__ __launch_bounds__(256) void k_pc_fd_points(uint64_t n3, const float* 
     if (e >= 6u * n3) return;
     const uint32_t s = (uint32_t)(e / n3);                      // 0 .. 5: +x, -x, +y, -y, +z, -z
     const uint64_t r = e - (uint64_t)s * n3;
-    const uint32_t k = (uint32_t)(r % 3u);
-    const float d = k == (s >> 1) ? ((s & 1u) ? -eps : eps) : 0.f;
-    const float v = points[r] + d;
-    out[e] = v < -bound ? -bound : (v > bound ? bound : v);     // torch.clamp: NaN stays NaN
-}
-
-__device__ __forceinline__ float pc_nan_to_num(float v) {
-    if (v != v) return 0.f;
-    return v > FLT_MAX ? FLT_MAX : (v < -FLT_MAX ? -FLT_MAX : v);
+    out[e] = fd_shift(points[r], (uint32_t)(r % 3u), s, eps, bound);
 }
 
 __global__ __launch_bounds__(256) void k_pc_finish(uint64_t n, uint32_t C, const float* __restrict__ albedo, const float* __restrict__ sig6,
@@ -171,11 +162,10 @@ __global__ __launch_bounds__(256) void k_pc_finish(uint64_t n, uint32_t C, const
         // products rounded one by one and summed in k order
         for (int j = 0; j < 3; j++) colors[3u * i + j] = ((a.x * m[0][j] + a.y * m[1][j]) + a.z * m[2][j]) + a.w * m[3][j];
     }
-    float v[3];
-    for (int a = 0; a < 3; a++) v[a] = (-0.5f * (sig6[(uint64_t)(2 * a) * n + i] - sig6[(uint64_t)(2 * a + 1) * n + i])) / eps;
-    const float d = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-    const float len = sqrtf(d < 1e-20f ? 1e-20f : d);           // torch.clamp(min): NaN stays NaN, and with it all three components
-    for (int a = 0; a < 3; a++) normals[3u * i + a] = pc_nan_to_num(v[a] / len);
+    const float g0 = fd_gradient(sig6[i], sig6[n + i], eps), g1 = fd_gradient(sig6[2u * n + i], sig6[3u * n + i], eps);
+    const float g2 = fd_gradient(sig6[4u * n + i], sig6[5u * n + i], eps);
+    float* nrm = normals + 3u * i;
+    fd_normalize(g0, g1, g2, nrm[0], nrm[1], nrm[2]);
 }
 
 __global__ __launch_bounds__(256) void k_pc_outside_boxes(uint64_t n, const float* __restrict__ points, uint32_t nb, const double* __restrict__ boxes,

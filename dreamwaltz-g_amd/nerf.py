@@ -7,7 +7,8 @@
   bind_nerf_network(ref)         rebinds common_forward and local_geometry_forward of a constructed reference _NeRFNetwork to
                                  nerf_field; the reference's own Parameters are read in place (optimizer, checkpoints untouched).
                                  With cuda_ray it also rebinds update_extra_state to the native occupancy update (occupancy.py, B13)
-                                 and run_cuda to the one-launch inference render (nerf_render.py, B14).
+                                 and run_cuda to the one-launch inference render (nerf_render.py, B14; with shaded_render=True
+                                 also for the shaded views, B15).
 Precision follows autocast: under torch.autocast(fp16) the kernels mirror the reference's fp16 rounding points (f16 MFMA, fp32
 accumulation), otherwise they compute in exact f32.  The arithmetic is csrc/nerf_field.hip; no CPU fallback.  Every buffer is checked
 (CUDA, contiguous, dtype, size) and a violation raises RuntimeError before any launch.
@@ -254,14 +255,16 @@ def _covered_call(x):
     return True
 
 
-def bind_nerf_network(ref):
+def bind_nerf_network(ref, shaded_render=False):
     """Rebind ref.common_forward / ref.local_geometry_forward to the fused kernels.  Returns None when bound, else the reason it was
     left unbound (also kept as ref._dwg_nerf_unbound).  Calls the kernels do not take (x requiring a gradient -- the autograd normal --,
-    a CPU x, bf16 autocast) go to the original methods."""
+    a CPU x, bf16 autocast) go to the original methods.  shaded_render: the installed run_cuda also takes the evaluation views with
+    shading 'normal', 'textureless' and 'lambertian' (nerf_render.covered_call, B15); off, they stay on the original method."""
     reason = unbound_reason(ref)
     if reason is not None:
         ref._dwg_nerf_unbound = reason
         return reason
+    ref._dwg_shaded_render = bool(shaded_render)
     if getattr(ref, "_dwg_nerf_bound", False):
         return None
     orig_common, orig_local = ref.common_forward, ref.local_geometry_forward
@@ -366,8 +369,8 @@ def _bind_update_extra_state(ref):
 
 def _bind_run_cuda(ref):
     """Install run_cuda on a bound network with cuda_ray: nerf_render.run_cuda, which renders an evaluation view (not training, shading
-    'albedo', no perturbation, CUDA fp32 rays, no autocast or fp16 autocast) in one launch and hands every other call to the original
-    method unchanged."""
+    'albedo' -- or a shaded view when ref._dwg_shaded_render --, no perturbation, CUDA fp32 rays, no autocast or fp16 autocast) in one
+    launch and hands every other call to the original method unchanged."""
     if "run_cuda" in ref.__dict__ or not getattr(ref, "cuda_ray", False) or not hasattr(type(ref), "run_cuda"):
         return
     from . import nerf_render
@@ -382,7 +385,7 @@ def _bind_run_cuda(ref):
 
 def unbind_nerf_network(ref):
     """Undo bind_nerf_network (the instance attributes go; the class methods show through again)."""
-    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "run_cuda", "_dwg_occupancy"):
+    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "run_cuda", "_dwg_occupancy", "_dwg_shaded_render"):
         if name in ref.__dict__:
             del ref.__dict__[name]
     ref._dwg_nerf_bound = False

@@ -15,8 +15,12 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              local_geometry_forward of that object to the fused field kernel (grid encoding -> sigma_net ->
                                              density / albedo); density, forward and normal reach it through them; with cuda_ray it also installs
                                              update_extra_state on the native occupancy update (B13, dreamwaltz_g_amd.occupancy) and
-                                             run_cuda on the one-launch inference render (B14, dreamwaltz_g_amd.nerf_render: an evaluation
-                                             view with shading 'albedo'; shading != 'albedo' in eval stays on the reference's loop).  The
+                                             run_cuda on the one-launch inference render (dreamwaltz_g_amd.nerf_render: an evaluation view
+                                             with shading 'albedo', B14, and -- bound here with shaded_render=True -- the shaded view the
+                                             trainer renders beside it, B15: 'normal' without autocast or under fp16 autocast, 'textureless'
+                                             and rgb 'lambertian' without autocast, the seven field evaluations per sample, the
+                                             finite-difference normal and the shading inside the one launch; latent 'lambertian' and the
+                                             lambert shadings under autocast stay on the reference's loop).  The
                                              network's own Parameters are read in place.  What the kernel does not cover (dual_mlp / dual_enc,
                                              density_prior smpl, a decoder_layer, a non-grid backbone) stays unbound with the reason in
                                              `_dwg_nerf_unbound`.  DWG_BIND_NERF=0: nothing is bound
@@ -215,7 +219,7 @@ def bind_nerf(ref):
         return ref
     _pkg()
     from dreamwaltz_g_amd.nerf import bind_nerf_network
-    reason = bind_nerf_network(ref)
+    reason = bind_nerf_network(ref, shaded_render=True)
     if reason is not None:
         print("[dwg_bind] NeRF field left on the reference path: %s" % reason, file=sys.stderr)
     return ref

@@ -3,6 +3,11 @@
 recipe), in f16 (the trainer evaluates under autocast) and f32, with the evaluation defaults max_steps 1024 / T_thresh 1e-4.
 
     python tools/bench_nerf_render.py [--sizes 512,256] [--reps 20] [--composition-reps 5] [--out profiles/b14_bench_nerf_render.txt]
+    python tools/bench_nerf_render.py --shading normal [...] [--out profiles/b15_bench_nerf_render.txt]
+
+--shading normal (boundary B15) times the shaded view the trainer renders beside every albedo view: the network bound with
+shaded_render=True against the composition of tests/nerf_shading_cases._NeRFNetwork.run_cuda (the reference's forward and normal over the
+bound field: seven field launches per loop iteration).  ambient_ratio and light_d do not enter 'normal' shading.
 
 The scene: a network with density_prior 'gaussian' and random parameters, its occupancy bitfield built by the native B13 update
 (update_extra_state of the bound network).  Such a field is FOG, not a trained surface: outside the central blob the density is near 1,
@@ -29,6 +34,7 @@ sys.path.insert(0, ROOT)
 import dwg_import  # noqa: E402,F401
 from dreamwaltz_g_amd import nerf, nerf_render, raymarch  # noqa: E402
 from tests import nerf_render_cases as rc  # noqa: E402
+from tests import nerf_shading_cases as sc  # noqa: E402
 from tests import raymarch_cases as rmc  # noqa: E402
 
 
@@ -55,7 +61,8 @@ def _count_syncs(fn):
             fn()
         finally:
             torch.cuda.set_sync_debug_mode("default")
-    return sum(1 for x in w if "synchroniz" in str(x.message))
+    # torch's one-time notice that the debug mode is a prototype also speaks of "synchronizing operations": not a synchronisation
+    return sum(1 for x in w if "synchroniz" in str(x.message) and "prototype feature" not in str(x.message))
 
 
 def main():
@@ -65,14 +72,16 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--composition-reps", type=int, default=5)
     ap.add_argument("--max-steps", type=int, default=1024)
+    ap.add_argument("--shading", default="albedo", choices=["albedo", "normal"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     H, bound = (int(v) for v in a.grid.split(":"))
     nets = []
     for _ in range(2):
-        net = rc.make_render_network(H, float(bound), gridtype='hash', interp='smoothstep').cuda().eval()
-        assert nerf.bind_nerf_network(net) is None
+        make = rc.make_render_network if a.shading == "albedo" else sc.make_shading_network
+        net = make(H, float(bound), gridtype='hash', interp='smoothstep').cuda().eval()
+        assert nerf.bind_nerf_network(net, shaded_render=a.shading != "albedo") is None
         nets.append(net)
     native, composed = nets
     with torch.autocast("cuda", dtype=torch.float16):
@@ -84,12 +93,12 @@ def main():
     rows, lines = [], []
     for size in (int(v) for v in a.sizes.split(",")):
         o, d = rmc.make_cameras(1, size, size, seed=0)
-        ro, rd = torch.from_numpy(o).cuda()[None], torch.from_numpy(d).cuda()[None]
+        ro, rd = torch.from_numpy(np.ascontiguousarray(o)).cuda()[None], torch.from_numpy(np.ascontiguousarray(d)).cuda()[None]
         nears, fars = raymarch.near_far_from_aabb(ro[0], rd[0], native.aabb_infer)
         for f16 in (True, False):
             def run(net):
                 with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16, enabled=f16):
-                    return net.run_cuda(ro, rd, light_d=ro[0, 0], max_steps=a.max_steps)
+                    return net.run_cuda(ro, rd, light_d=ro[0, 0], shading=a.shading, max_steps=a.max_steps)
             before = _median_ms(lambda: run(composed), a.composition_reps)
             t_native = _median_ms(lambda: run(native), a.reps)
             after = _median_ms(lambda: run(composed), a.composition_reps)
@@ -109,7 +118,7 @@ def main():
                          % (size, row["rays"], row["precision"], row["samples"], row["max_count"], t_native, row["native_host_syncs"], before, after,
                             row["composition_host_syncs"], min(before, after) / t_native, diff))
             print(lines[-1], flush=True)
-    head = "B14 inference render, %s, torch %s, grid_size %d bound %d (%.1f %% of the cells occupied), max_steps %d, reps %d / %d" % (
+    head = ("B14 inference render" if a.shading == "albedo" else "B15 inference render with shading '%s'" % a.shading) + ", %s, torch %s, grid_size %d bound %d (%.1f %% of the cells occupied), max_steps %d, reps %d / %d" % (
         torch.cuda.get_device_name(0), torch.__version__, H, bound, 100 * occupied, a.max_steps, a.reps, a.composition_reps)
     text = "\n".join([head] + lines + [json.dumps(rows)]) + "\n"
     if a.out:
