@@ -228,6 +228,10 @@ SIGNATURES = {
                                                ctypes.c_float, _i32, _vp, _vp]),
     "dwg_condition_workspace_bytes": (_sz, [_i32, _i32]),
     "dwg_condition_draw": (ctypes.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "dwg_condition_keypoints_people": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, ctypes.c_float, ctypes.c_float,
+                                                      ctypes.c_float, _i32, _i32, _vp, _vp, _vp]),
+    "dwg_condition_people_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dwg_condition_draw_people": (ctypes.c_int, [_i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     # include/dwg_depthmap.h
     "dwg_depthmap_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dwg_depthmap_cast": (ctypes.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),

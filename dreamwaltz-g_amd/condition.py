@@ -10,7 +10,10 @@ Same names, arguments and error behaviour as the reference seam; what differs, d
     `ConditionImage.to_pil()` gives the PIL image where one is wanted, `export_pose_chw` gives the float [1, 3, H, W] in [0, 1]
     that `ControlNetScoreDistillation.prepare_image` would make of it (controlnet.py:33-55 at equal size is the identity resize);
   * `export_depth(raw=True)` returns a `DepthMap` (fp32 [H, W] on the device; `np.asarray(depth_map)` gives the reference's array);
-  * nothing here leaves the device: no `.cpu()`, no host synchronisation.
+  * nothing here leaves the device: no `.cpu()`, no host synchronisation;
+  * several people (`--prompt.num_person`; the reference adds one mesh per person to ONE open3d scene and reads `geometry_ids`) are a
+    `PeopleScene` (`build_people_scene`): vertices [P,V,3] over one triangle topology.  Keypoints [P,K,3] / rows [P,128,4] give one image
+    for all of them, person 0 drawn first; `export_depth` / `export_normal_raw` cast against the concatenated mesh.
 There is no CPU fallback: CPU tensors raise."""
 import ctypes
 from typing import Optional
@@ -21,6 +24,7 @@ import torch
 from . import _lib
 
 N_KEYPOINTS = 128                 # body 18 + hands 2 x 21 + face 51 + 17 (smpl_condition.py:22)
+MAX_PEOPLE = 16                   # DWG_COND_MAX_PEOPLE
 DRAW_BODY, DRAW_HAND, DRAW_FACE, FLIP_LR = 1, 2, 4, 8
 
 
@@ -44,9 +48,45 @@ def build_ray_casting_scene(vertices, triangles) -> RayCastingScene:
         triangles = torch.as_tensor(np.asarray(triangles).astype(np.int32))
     if vertices.dim() == 3:
         if vertices.shape[0] != 1:
-            raise NotImplementedError("one person per condition image")
+            raise NotImplementedError("one mesh per RayCastingScene; several people are a PeopleScene (build_people_scene)")
         vertices = vertices[0]
     return RayCastingScene(vertices, triangles)
+
+
+class PeopleScene:
+    """utils/open3d.py:8-19 with one mesh per person: vertices [P,V,3] fp32 + the triangles [F,3] int32 all P meshes share, on the device.
+    `merged` is the same geometry as ONE mesh (vertices [P V,3], person p's triangles offset by p V), built on first use: what the
+    per-pixel casts (export_depth, export_normal_raw) run against."""
+
+    def __init__(self, vertices: torch.Tensor, triangles: torch.Tensor):
+        if vertices.dim() != 3 or vertices.shape[-1] != 3:
+            raise ValueError("build_people_scene takes vertices [P,V,3]; got %s" % (tuple(vertices.shape),))
+        if not 1 <= vertices.shape[0] <= MAX_PEOPLE:
+            raise ValueError("a condition image holds 1 to %d people; got %d" % (MAX_PEOPLE, vertices.shape[0]))
+        if not vertices.is_cuda:
+            raise RuntimeError("dreamwaltz_g_amd.condition runs on the GPU only (HIP kernels); got a CPU tensor")
+        self.vertices = vertices.detach().float().contiguous()
+        self.triangles = triangles.to(device=vertices.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+        self._merged = None
+
+    @property
+    def num_people(self) -> int:
+        return int(self.vertices.shape[0])
+
+    @property
+    def merged(self) -> RayCastingScene:
+        if self._merged is None:
+            P, V = self.vertices.shape[:2]
+            offsets = torch.arange(P, dtype=torch.int32, device=self.vertices.device) * V
+            self._merged = RayCastingScene(self.vertices.reshape(P * V, 3), (self.triangles[None] + offsets[:, None, None]).reshape(-1, 3))
+        return self._merged
+
+
+def build_people_scene(vertices, triangles) -> PeopleScene:
+    """build_ray_casting_scene for [P,V,3] vertices (utils/open3d.py:12-18: one add_triangles per person, same triangles)."""
+    if not torch.is_tensor(triangles):
+        triangles = torch.as_tensor(np.asarray(triangles).astype(np.int32))
+    return PeopleScene(vertices, triangles)
 
 
 def adjust_intrinsics_size(intrinsics: torch.Tensor, width: int, height: int) -> torch.Tensor:
@@ -75,7 +115,8 @@ class OcclusionCulling:
         else:
             raise NotImplementedError
         # One person per image: every ray that hits anything hits that person's own mesh, so ignoring body SELF occlusion
-        # (:132-135, the shipped default configs/__init__.py:445) means the body group is never culled.
+        # (:132-135, the shipped default configs/__init__.py:445) means the body group is never culled.  With several people
+        # (PeopleScene) the kernel keeps who was hit, and only a hit on the keypoint's own person is ignored.
         self.ignore_body_self_occlusion = ignore_body_self_occlusion
         self.thres_body, self.thres_face, self.thres_hand = 0.2, 0.02, 0.2          # __call__ defaults, :100-103
         self._groups = {}
@@ -142,12 +183,13 @@ class SMPL2Condition:
     # -- the two launches ------------------------------------------------------------------------------------------------
     def pose_rows(self, keypoints: torch.Tensor, ray_casting_scene: Optional[RayCastingScene], extrinsic: torch.Tensor,
                   intrinsics: torch.Tensor) -> torch.Tensor:
-        """export_pose up to the drawing call (smpl_condition.py:191-224): fp64 rows [K,4] = (x / W, y / H, dist, valid)."""
+        """export_pose up to the drawing call (smpl_condition.py:191-224): fp64 rows [K,4] = (x / W, y / H, dist, valid); [P,K,4] for
+        keypoints [P,K,3] of several people or a PeopleScene (people_rows)."""
         if not keypoints.is_cuda:
             raise RuntimeError("dreamwaltz_g_amd.condition runs on the GPU only (HIP kernels); got a CPU tensor")
+        if isinstance(ray_casting_scene, PeopleScene) or (keypoints.dim() == 3 and keypoints.shape[0] != 1):
+            return self.people_rows(keypoints, ray_casting_scene, extrinsic, intrinsics)[0]
         if keypoints.dim() == 3:
-            if keypoints.shape[0] != 1:
-                raise NotImplementedError("one person per condition image")
             keypoints = keypoints[0]
         dev = keypoints.device
         kp = keypoints.detach().float().contiguous()
@@ -168,22 +210,72 @@ class SMPL2Condition:
             p(rows), _stream(dev)), "dwg_condition_keypoints")
         return rows
 
+    def people_rows(self, keypoints: torch.Tensor, people_scene: Optional[PeopleScene], extrinsic: torch.Tensor,
+                    intrinsics: torch.Tensor, return_hit_person: bool = False):
+        """pose_rows for P people (smpl_condition.py:96-143 with N = P): keypoints [P,K,3] against all P meshes of the PeopleScene ->
+        (fp64 rows [P,K,4], int32 [P,K] person the nearest hit belongs to (-1 = none; open3d's geometry_ids) | None)."""
+        if keypoints.dim() == 2:
+            keypoints = keypoints[None]
+        if keypoints.dim() != 3 or keypoints.shape[-1] != 3:
+            raise ValueError("keypoints are [P,K,3]; got %s" % (tuple(keypoints.shape),))
+        P, K = int(keypoints.shape[0]), int(keypoints.shape[1])
+        if not 1 <= P <= MAX_PEOPLE:
+            raise ValueError("a condition image holds 1 to %d people; got %d" % (MAX_PEOPLE, P))
+        cull = self.occlusion_culling is not None
+        oc = self.occlusion_culling
+        if cull and people_scene is None:
+            raise ValueError("occlusion culling needs the body meshes (build_people_scene)")
+        if people_scene is not None:
+            if not isinstance(people_scene, PeopleScene):
+                raise ValueError("keypoints of %d people need a PeopleScene (build_people_scene), not one mesh" % P)
+            if people_scene.num_people != P:
+                raise ValueError("keypoints of %d people against the meshes of %d" % (P, people_scene.num_people))
+        if not keypoints.is_cuda:
+            raise RuntimeError("dreamwaltz_g_amd.condition runs on the GPU only (HIP kernels); got a CPU tensor")
+        dev = keypoints.device
+        kp = keypoints.detach().float().contiguous()
+        ext = extrinsic.detach().to(dev).float().reshape(4, 4).contiguous()
+        intr = intrinsics.detach().to(dev).float().reshape(3, 3).contiguous()
+        rows = torch.empty(P, K, 4, dtype=torch.float64, device=dev)
+        hit = torch.empty(P, K, dtype=torch.int32, device=dev) if return_hit_person else None
+        p = _lib.ptr
+        _lib.check(_lib.lib().dwg_condition_keypoints_people(
+            P, K, p(kp), p(ext), p(intr), int(people_scene.vertices.shape[1]) if cull else 0, p(people_scene.vertices) if cull else None,
+            int(people_scene.triangles.shape[0]) if cull else 0, p(people_scene.triangles) if cull else None,
+            p(oc.groups(K, dev)) if cull else None, oc.thres_body if cull else 0.0, oc.thres_hand if cull else 0.0,
+            oc.thres_face if cull else 0.0, 1 if (cull and oc.ignore_body_self_occlusion) else 0, 1 if cull else 0, p(rows), p(hit),
+            _stream(dev)), "dwg_condition_keypoints_people")
+        return rows, hit
+
     def draw(self, rows: torch.Tensor, height: int, width: int, out_u8: bool = True, out_chw: bool = False):
-        """adaptive_draw_poses (open_pose.py:279-333) from the rows -> (uint8 [H,W,3] | None, float [1,3,H,W] | None)."""
-        if rows.shape[0] != N_KEYPOINTS:
-            raise ValueError("the OpenPose layout has 128 keypoints (body 18, hands 2 x 21, face 68); got %d" % rows.shape[0])
+        """adaptive_draw_poses (open_pose.py:279-333) from the rows [128,4], or [P,128,4] for P people on one canvas (person 0 first)
+        -> (uint8 [H,W,3] | None, float [1,3,H,W] | None)."""
+        people = rows.dim() == 3
+        if rows.shape[-2] != N_KEYPOINTS:
+            raise ValueError("the OpenPose layout has 128 keypoints (body 18, hands 2 x 21, face 68); got %d" % rows.shape[-2])
+        if people and not 1 <= rows.shape[0] <= MAX_PEOPLE:
+            raise ValueError("a condition image holds 1 to %d people; got %d" % (MAX_PEOPLE, rows.shape[0]))
+        if not rows.is_cuda:
+            raise RuntimeError("dreamwaltz_g_amd.condition runs on the GPU only (HIP kernels); got a CPU tensor")
         dev = rows.device
         rows = rows.double().contiguous()
-        key = (str(dev), height, width)
+        L = _lib.lib()
+        P = int(rows.shape[0]) if people else None
+        key = (str(dev), height, width) if not people else (str(dev), height, width, P)
         if key not in self._ws:
-            self._ws[key] = torch.empty(max(int(_lib.lib().dwg_condition_workspace_bytes(height, width)), 16), dtype=torch.uint8, device=dev)
+            need = L.dwg_condition_people_workspace_bytes(P, height, width) if people else L.dwg_condition_workspace_bytes(height, width)
+            self._ws[key] = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
         flags = ((DRAW_BODY if self.draw_body else 0) | (DRAW_HAND if self.draw_hand else 0) | (DRAW_FACE if self.draw_face else 0)
                  | (FLIP_LR if self.openpose_left_right_flip else 0))
         u8 = torch.empty(height, width, 3, dtype=torch.uint8, device=dev) if out_u8 else None
         chw = torch.empty(1, 3, height, width, dtype=torch.float32, device=dev) if out_chw else None
         p = _lib.ptr
-        _lib.check(_lib.lib().dwg_condition_draw(height, width, p(rows), flags, p(u8) if out_u8 else None, p(chw) if out_chw else None,
-                                                 p(self._ws[key]), _stream(dev)), "dwg_condition_draw")
+        if people:
+            _lib.check(L.dwg_condition_draw_people(P, height, width, p(rows), flags, p(u8) if out_u8 else None, p(chw) if out_chw else None,
+                                                   p(self._ws[key]), _stream(dev)), "dwg_condition_draw_people")
+        else:
+            _lib.check(L.dwg_condition_draw(height, width, p(rows), flags, p(u8) if out_u8 else None, p(chw) if out_chw else None,
+                                            p(self._ws[key]), _stream(dev)), "dwg_condition_draw")
         return u8, chw
 
     # -- the reference's methods -----------------------------------------------------------------------------------------
@@ -203,6 +295,8 @@ class SMPL2Condition:
                    normals: bool = False, minmax: bool = False):
         """utils/open3d.py:21-45 cast_rays: one pinhole ray per pixel -> (t_hit fp32 [H,W], primitive normals fp32 [H,W,3] | None,
         workspace).  `minmax` leaves the extrema of 1 / t_hit in the workspace for `_depth_image(..., from_cast=True)`."""
+        if isinstance(ray_casting_scene, PeopleScene):                    # every person's triangles in one mesh: the nearest of them all
+            ray_casting_scene = ray_casting_scene.merged
         if not isinstance(ray_casting_scene, RayCastingScene):
             raise RuntimeError("dreamwaltz_g_amd.condition runs on the GPU only (HIP kernels); the scene is build_ray_casting_scene's")
         if not (torch.is_tensor(extrinsic) and torch.is_tensor(intrinsics)):
@@ -288,9 +382,11 @@ class SMPL2Condition:
         assert extrinsic.dim() == 2 and extrinsic.numel() == 16
         assert intrinsics.dim() == 2 and intrinsics.numel() == 9
         intrinsics = adjust_intrinsics_size(intrinsics, width=condition_width, height=condition_height)
+        vertices = smpl_outputs.vertices.detach()
+        build_scene = build_people_scene if (vertices.dim() == 3 and vertices.shape[0] > 1) else build_ray_casting_scene      # num_person > 1
         if condition_type == 'depth_raw':
-            return self.export_depth(build_ray_casting_scene(smpl_outputs.vertices.detach(), triangles), raw=True, intrinsics=intrinsics,
+            return self.export_depth(build_scene(vertices, triangles), raw=True, intrinsics=intrinsics,
                                      extrinsic=extrinsic, width=condition_width, height=condition_height)
-        scene = build_ray_casting_scene(smpl_outputs.vertices.detach(), triangles) if self.occlusion_culling is not None else None
+        scene = build_scene(vertices, triangles) if self.occlusion_culling is not None else None
         return self.export_pose(smpl_outputs.joints.detach(), scene, intrinsics=intrinsics, extrinsic=extrinsic, width=condition_width,
                                 height=condition_height)

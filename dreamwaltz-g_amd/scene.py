@@ -79,6 +79,15 @@ class Scene(nn.Module):
             gaussians.positions = gaussians.positions + t.unsqueeze(0)
         return gaussians
 
+    def _avatars_forward(self, smpl_observed_inputs: dict) -> GaussianOutput:
+        """scene.py:107-121: avatar i animated with slice i of the [A, ...] inputs (and its scale / translation), the outputs merged."""
+        parts = []
+        batch_size = smpl_observed_inputs['body_pose'].size(0)
+        assert batch_size <= len(self.avatars), f'Assert num_smplx_inputs: {batch_size} <= num_avatars: {len(self.avatars)}'
+        for i, avatar in enumerate(self.avatars):
+            parts.append(self.avatar_forward({k: v[i:i + 1, ...] for k, v in smpl_observed_inputs.items()}, avatar=avatar, avatar_index=i))
+        return merge_gaussians(*parts)
+
     def _video_indices(self, data, frame_indices):
         if frame_indices is not None:
             return frame_indices
@@ -98,20 +107,25 @@ class Scene(nn.Module):
         """Playback of F pose frames under one camera (`data`: the loader's dict) or each under its own (`data`: a list of F dicts, as the
         reference's evaluation loader yields them): `animate` per pose, then ONE rasterizer launch chain for all of them
         (renderer.render_frames).  Frame f equals `forward(data, poses[f], use_densifier=False, bg_mode=bg_mode)` bit for bit -- the
-        reference's evaluation loop renders such sequences one pose at a time under inference mode (trainer.py:1019-1150).  Single avatar,
-        no gradients.  `frozen_avatar`: the avatar's parameters do not change between the frames (a trained avatar playing a motion): the
+        reference's evaluation loop renders such sequences one pose at a time under inference mode (trainer.py:1019-1150).  No gradients.
+        With several avatars (`Scene(cfg, [avatar, ...])`) `poses[f]` carries the [A, ...] batch `forward` slices: avatar i is animated
+        with slice i and its `avatar_transl` / `avatar_scale`, and the A outputs of a frame are merged before the one launch chain.
+        `frozen_avatar`: the avatar's parameters do not change between the frames (a trained avatar playing a motion): the
         pose-independent part of `animate` -- canonical positions, grid encoding, colour / opacity network -- is computed once and kept until
         a parameter changes (avatar.DreamWaltzG.frozen_playback; same bits, 0.3 ms less per 300 k-Gaussian frame).  A video background
         takes one frame index per frame (`frame_indices`: ints or an int32 CUDA tensor; else each data dict's 'frame_index', or a
         single dict's list / tensor of F) and composites all F frames in one launch after the rasterizer chain.
         -> {'image' | 'image_fg' | 'image_bg' | 'depth' | 'alpha': [F, H, W, C]}."""
-        if self.avatars is not None:
-            raise NotImplementedError("forward_frames renders one avatar per frame")
         frames = []
-        self.avatar.frozen_playback = bool(frozen_avatar)
+        avatars = [self.avatar] if self.avatars is None else list(self.avatars)
+        for avatar in avatars:
+            avatar.frozen_playback = bool(frozen_avatar)
         try:
             for pose in poses:
-                g = self.avatar_forward(smpl_observed_inputs=pose)
+                if self.avatars is None:
+                    g = self.avatar_forward(smpl_observed_inputs=pose)
+                else:
+                    g = self._avatars_forward(pose)
                 if self.use_zero_scales:
                     g.scales = g.scales * 0.1
                 if self.use_constant_colors:
@@ -122,7 +136,8 @@ class Scene(nn.Module):
                     g = downsample_gaussians(g, self.fixed_n_gaussians)
                 frames.append(g)
         finally:
-            self.avatar.frozen_playback = False
+            for avatar in avatars:
+                avatar.frozen_playback = False
         outputs = self.renderer.render_frames(data=data, frames=frames)
         if bg_mode in self.pure_colors:
             outputs['image_bg'] = self.pure_colors.get_background_like(bg_mode, outputs['image'])
@@ -193,12 +208,7 @@ class Scene(nn.Module):
         if self.avatars is None:
             gaussians = self.avatar_forward(smpl_observed_inputs=smpl_observed_inputs)
         else:
-            parts = []
-            batch_size = smpl_observed_inputs['body_pose'].size(0)
-            assert batch_size <= len(self.avatars), f'Assert num_smplx_inputs: {batch_size} <= num_avatars: {len(self.avatars)}'
-            for i, avatar in enumerate(self.avatars):
-                parts.append(self.avatar_forward({k: v[i:i + 1, ...] for k, v in smpl_observed_inputs.items()}, avatar=avatar, avatar_index=i))
-            gaussians = merge_gaussians(*parts)
+            gaussians = self._avatars_forward(smpl_observed_inputs)
         if self.use_zero_scales:
             gaussians.scales = gaussians.scales * 0.1
         if self.use_constant_colors:

@@ -44,6 +44,29 @@ size_t dwg_condition_workspace_bytes(int32_t H, int32_t W);
 int dwg_condition_draw(int32_t H, int32_t W, const double* rows, int32_t flags, uint8_t* out_u8, float* out_chw, void* workspace,
                        dwg_stream_t stream);
 
+/* ---- several people on one canvas (--prompt.num_person; smpl_condition.py:96-143 with N > 1, open_pose.py:282-333, utils/open3d.py:8-19
+ * with one mesh per person) ------------------------------------------------------------------------------------------------------- */
+#define DWG_COND_MAX_PEOPLE 16
+
+/* export_pose up to the drawing call for P people who share one triangle topology: keypoints [P,K,3], vertices [P,V,3], triangles [F,3].
+ * One ray per (person, keypoint) against the triangles of ALL P meshes, with the arithmetic of dwg_condition_keypoints; the nearest hit
+ * keeps the person it belongs to (open3d's geometry_ids; on equal t the lower person index), written to hit_person [P,K] (-1 = miss)
+ * when that pointer is given.  occluded = (t_far - t_hit) > thres[group], and for the body group with ignore_body_self_occlusion
+ * additionally hit_person != the keypoint's own person (:132-135).  The thresholds are finite; the flag says who may hide whom.
+ * rows [P,K,4] fp64 as above.  DWG_E_ARG (before any launch): P < 1, P > DWG_COND_MAX_PEOPLE, a missing pointer, culling without a mesh. */
+int dwg_condition_keypoints_people(int32_t P, int32_t K, const float* keypoints, const float* extrinsic, const float* intrinsics,
+                                   int32_t V, const float* vertices, int32_t F, const int32_t* triangles, const uint8_t* groups,
+                                   float thres_body, float thres_hand, float thres_face, int32_t ignore_body_self_occlusion,
+                                   int32_t use_occlusion_culling, double* rows, int32_t* hit_person, dwg_stream_t stream);
+
+/* bytes of scratch dwg_condition_draw_people needs (limb spans of every person); 0 for a P or a size it does not take */
+size_t dwg_condition_people_workspace_bytes(int32_t P, int32_t H, int32_t W);
+
+/* adaptive_draw_poses for P people from rows [P,128,4]: person 0 is drawn first, each later person over the earlier ones, within a
+ * person the order of dwg_condition_draw.  Size rule, flags, outputs and size limits as dwg_condition_draw. */
+int dwg_condition_draw_people(int32_t P, int32_t H, int32_t W, const double* rows, int32_t flags, uint8_t* out_u8, float* out_chw,
+                              void* workspace, dwg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
