@@ -239,6 +239,11 @@ SIGNATURES = {
     "dwg_pretrain_loss_workspace_bytes": (_sz, [_i64]),
     "dwg_pretrain_loss_forward": (ctypes.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dwg_pretrain_loss_backward": (ctypes.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # include/dwg_image_loss.h
+    "dwg_image_loss_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "dwg_image_loss_forward": (ctypes.c_int, [_i32] * 5 + [_f32] + [_vp, _i64, _i64, _i64, _i64] * 2 + [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "dwg_image_loss_backward": (ctypes.c_int, [_i32] * 5 + [ctypes.c_double] * 2 + [_vp, _i64, _i64, _i64, _i64] * 2
+                                + [_vp, _vp, _i32, _vp, _vp]),
     # include/dwg_graph.h
     "dwg_graph_begin_capture": (ctypes.c_int, [_vp]),
     "dwg_graph_end_capture": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),

@@ -320,6 +320,34 @@ class SDSTrainer:
             self.check_replicas()
         return out
 
+    def nerf2gs_step(self, data, nerf_guidance):
+        """The loop body of the reference's Trainer.pretrain_nerf2gs (trainer.py:1304-1332, boundary B17): one step that fits the avatar's
+        render to `nerf_guidance.render(data=data, shading='albedo')['image_fg']` under the L1 + D-SSIM image loss -- spatial scale,
+        forward (image_loss.nerf2gs_forward), zero_grad + update_learning_rate, backward, the densifier hook, the optimizers.  The
+        reference's loop is single-view and single-GPU; so is this.  -> (loss, render_outputs, nerf_outputs)."""
+        from . import image_loss
+        if self.world != 1 or self.total_views != 1:
+            raise NotImplementedError("the nerf2gs step is the reference's single-view, single-GPU loop (ranks: %d, views per step: %d)"
+                                      % (self.world, self.total_views))
+        self._check_caches()
+        self.nerf_guidance = nerf_guidance
+        self.train_step_index += 1
+        spatial_scale = self.get_spatial_scale(data)
+        renderer = getattr(self.model, "renderer", None)
+        while True:
+            self._begin_step(spatial_scale)
+            loss, render_outputs, nerf_outputs = image_loss.nerf2gs_forward(self, data)
+            self._backward(loss)
+            if renderer is None or not renderer.consume_overflow():
+                break
+            self.redone_frames += 1                 # a truncated frame contributed a zero gradient: render it again (see _view)
+        if self.densifiers is not None:
+            self.model.densify(densifiers=self.densifiers, render_outputs=render_outputs, spatial_scale=spatial_scale,
+                               train_step=self.train_step_index)
+        for optimizer in self.optimizers.values():
+            optimizer.step()
+        return loss, render_outputs, nerf_outputs
+
     def _reduce_and_step(self):
         """The exchange step of a multi-rank SDS step (nothing in the reference to mirror: SURVEY 2.2 finds no torch.distributed).
         The flat gradient buffer is reduced SLICE BY SLICE, one asynchronous all-reduce per named optimizer, smallest slice first -- the grid

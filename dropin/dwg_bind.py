@@ -35,6 +35,14 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              launch; the map stays on the device when the loader hands a condition.DepthMap (INTEGRATION
                                              B9), an np.ndarray is uploaded.  visual_outputs is built only when time_to_snapshot.  CPU
                                              renders go to the original method.  DWG_BIND_PRETRAIN=0: nothing is bound
+  B17 core.trainer.Trainer.init_losses (trainer.py:633-645) and Trainer.pretrain_nerf2gs_forward (trainer.py:1370-1386), the nerf2gs
+                                             loop (`--log.nerf2gs`) -> dreamwaltz_g_amd.image_loss: init_losses runs the original; where
+                                             that fails because core/gaussian/gaussian_loss.py imports the absent pytorch3d, it runs once
+                                             more with cfg.log.nerf2gs off (restored afterwards); with cfg.log.nerf2gs set, losses['image']
+                                             is the native ImageReconstructionLoss (L1 + D-SSIM, one forward and one backward launch
+                                             chain).  pretrain_nerf2gs_forward renders once; a device render goes to
+                                             image_loss.nerf2gs_forward, which reads both [B, H, W, C] renders in place; a CPU render goes
+                                             to the original method.  DWG_BIND_NERF2GS=0: nothing is bound
   B3  core.system.avatar.build_gaussian_avatar (avatar.py:1642-1714)  -> the reference builds ITS avatar (point cloud, nearest triangles,
                                              inverse LBS, LBS weights ...), then `DreamWaltzG.from_reference(ref)` adopts every Parameter
                                              and buffer by name; non-DreamWaltzG gs_types are returned untouched (reference path)
@@ -70,6 +78,7 @@ Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's fie
              DWG_BIND_POINTCLOUD = 0                  leave the NeRF-to-Gaussian point-cloud export (B12) on the reference path
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
              DWG_BIND_PRETRAIN = 0                    leave Trainer.pretrain_forward (B9) on the reference path (numpy on the host)
+             DWG_BIND_NERF2GS = 0                     leave Trainer.init_losses / pretrain_nerf2gs_forward (B17) on the reference path (pytorch3d)
              DWG_BIND_DTYPE = f32x | f32 | f16 | bf16  storage type of the denoiser / VAE plans.  Unset: the precision the reference loaded its
                                                      pipeline in -- torch.float32 (its default, core/guidance/basic.py:233) -> f32x (fp32-grade
                                                      split precision on the 16-bit MFMA pipe), torch.float16 (`--guide.dtype fp16`,
@@ -327,6 +336,7 @@ def _sigma_covered(trainer, data):
 def _patch_trainer_module(mod):
     _patch_trainer_sigma(mod)
     _patch_trainer_pretrain(mod)
+    _patch_trainer_nerf2gs(mod)
 
 
 def _patch_trainer_sigma(mod):
@@ -385,6 +395,56 @@ def _patch_trainer_pretrain(mod):
     setattr(pretrain_forward, _PATCHED, True)
     pretrain_forward.__wrapped__ = orig
     cls.pretrain_forward = pretrain_forward
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# B17: the nerf2gs loop's image loss
+# --------------------------------------------------------------------------------------------------------------------------------------
+def _patch_trainer_nerf2gs(mod):
+    if os.environ.get("DWG_BIND_NERF2GS", "1") == "0":
+        return
+    cls = mod.Trainer
+    orig_losses, orig_forward = cls.init_losses, cls.pretrain_nerf2gs_forward
+    if getattr(orig_losses, _PATCHED, False):
+        return
+    import functools
+
+    @functools.wraps(orig_losses)
+    def init_losses(self):
+        log = self.cfg.log
+        try:
+            losses = orig_losses(self)
+        except ModuleNotFoundError as e:
+            # core/gaussian/gaussian_loss.py imports pytorch3d at module level (for a regularizer nothing calls); without it the
+            # reference cannot build losses['image'].  Everything else of init_losses is built with the switch off
+            if not (e.name or "").startswith("pytorch3d") or not log.nerf2gs:
+                raise
+            saved = log.nerf2gs
+            log.nerf2gs = False
+            try:
+                losses = orig_losses(self)
+            finally:
+                log.nerf2gs = saved
+        if log.nerf2gs:
+            _pkg()
+            from dreamwaltz_g_amd.image_loss import ImageReconstructionLoss
+            losses['image'] = ImageReconstructionLoss()
+        return losses
+
+    @functools.wraps(orig_forward)
+    def pretrain_nerf2gs_forward(self, data):
+        once = _RenderedOnce(self, self.render(data=data))
+        if not getattr(once._render_outputs.get('image_fg'), 'is_cuda', False):
+            return orig_forward(once, data)                        # a CPU render: the reference's own statements fit it
+        _pkg()
+        from dreamwaltz_g_amd.image_loss import nerf2gs_forward as native
+        return native(once, data)
+
+    for f, orig in ((init_losses, orig_losses), (pretrain_nerf2gs_forward, orig_forward)):
+        setattr(f, _PATCHED, True)
+        f.__wrapped__ = orig
+    cls.init_losses = init_losses
+    cls.pretrain_nerf2gs_forward = pretrain_nerf2gs_forward
 
 
 # --------------------------------------------------------------------------------------------------------------------------------------
@@ -604,5 +664,6 @@ def uninstall():
         cls = getattr(mod, "Trainer", None)
         if cls is not None and getattr(cls.__dict__.get("calc_sigma_loss"), _PATCHED, False):
             cls.calc_sigma_loss = cls.calc_sigma_loss.__wrapped__
-        if cls is not None and getattr(cls.__dict__.get("pretrain_forward"), _PATCHED, False):
-            cls.pretrain_forward = cls.pretrain_forward.__wrapped__
+        for attr in ("pretrain_forward", "init_losses", "pretrain_nerf2gs_forward"):
+            if cls is not None and getattr(cls.__dict__.get(attr), _PATCHED, False):
+                setattr(cls, attr, getattr(cls, attr).__wrapped__)
