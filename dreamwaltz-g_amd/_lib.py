@@ -146,6 +146,12 @@ SIGNATURES = {
     "dwg_raymarch_march_rays_train": (ctypes.c_int, [_vp, _vp, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32,
                                                      _vp, _vp, _vp, _vp, _sz, _vp]),
     "dwg_raymarch_composite_rays_train_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "dwg_raymarch_composite_rays_train_forward_live": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _vp, _vp, _vp,
+                                                                      _vp]),
+    # include/dwg_nerf_train.h
+    "dwg_nerf_train_workspace_bytes": (_sz, [_u32]),
+    "dwg_nerf_train_compact_offsets": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _sz, _vp]),
+    "dwg_nerf_train_gather_live": (ctypes.c_int, [_vp, _vp, _u32, _u32, _u32] + [_vp] * 8 + [_u32, _u32, _vp]),
     "dwg_raymarch_composite_rays_train_backward": (ctypes.c_int, [_vp] * 11 + [_u32, _u32, _u32, _f32, _u32, _vp, _vp, _vp]),
     "dwg_raymarch_march_rays": (ctypes.c_int, [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp,
                                                _vp, _vp, _vp]),

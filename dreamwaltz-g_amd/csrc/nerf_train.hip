@@ -1,0 +1,168 @@
+// nerf_train.hip -- the training render of the NeRF stage for gfx950 (boundary B18, include/dwg_nerf_train.h): offsets of the samples
+// the training composite used, and the gather that keeps only those for the backward.
+//
+// composite_rays_train (the reference's core/nerf/raymarching/rgb/src/raymarching.cu:541-569) stops a ray at the first sample after which
+// T < T_thresh; its backward (:652-694) writes no gradient past it, and the field backward over those rows adds zeros.  raymarch.hip's
+// k_composite_fwd_live reports live[n], the count of leading samples ray n composited.  Here:
+//   - k_nt_block_sums / k_nt_scan_sums / k_nt_scan_down: the deterministic three-launch exclusive scan of raymarch.hip's count pass over
+//     live[], written as (offset, live) pairs -- the `rays` layout the composite backward reads.
+//   - k_nt_gather: one wave per ray (kRaysPerWave consecutive rays per wave, as the composite) walks the ray's live rows and copies the
+//     words of every per-sample array from the ray's range in the full buffers to its range in the live ones.  Consecutive lanes take
+//     consecutive words of a contiguous range: coalesced on both sides.
+// Integer adds and bit-for-bit copies only: no float arithmetic, no atomics.
+#include "dwg_common.h"
+#include "dwg_prof_internal.h"
+#include "../../include/dwg_nerf_train.h"
+#include "scan_common.h"
+
+namespace {
+
+constexpr int kScanThreads = 256;
+constexpr int kScanItems = 4;                       // 1024 rays per scan block
+constexpr int kScanBlock = kScanThreads * kScanItems;
+constexpr int kRaysPerWave = 4;
+
+__device__ __forceinline__ uint32_t live_of(const int32_t* __restrict__ live, uint32_t n, uint32_t N) {
+    if (n >= N) return 0u;
+    const int32_t v = live[n];
+    return v > 0 ? (uint32_t)v : 0u;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_nt_block_sums(const int32_t* __restrict__ live, uint32_t N, uint32_t* __restrict__ sums) {
+    __shared__ uint32_t lds[kScanThreads / 64 + 1];
+    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) s += live_of(live, base + k, N);
+    uint32_t total;
+    block_excl_scan_u32<kScanThreads>(s, lds, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// one workgroup: block sums -> exclusive block offsets; total[0] = the sum
+__global__ __launch_bounds__(1024) void k_nt_scan_sums(uint32_t* __restrict__ sums, uint32_t nb, int32_t* __restrict__ total_out) {
+    __shared__ uint32_t lds[1024 / 64 + 1];
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nb; b0 += 1024) {
+        const uint32_t i = b0 + threadIdx.x;
+        const uint32_t v = i < nb ? sums[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_excl_scan_u32<1024>(v, lds, &total);
+        if (i < nb) sums[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) total_out[0] = (int32_t)carry;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_nt_scan_down(const int32_t* __restrict__ live, uint32_t N, const uint32_t* __restrict__ sums,
+                                                               int32_t* __restrict__ rays_live) {
+    __shared__ uint32_t lds[kScanThreads / 64 + 1];
+    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
+    uint32_t c[kScanItems], s = 0;
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) {
+        c[k] = live_of(live, base + k, N);
+        s += c[k];
+    }
+    uint32_t total;
+    uint32_t off = sums[blockIdx.x] + block_excl_scan_u32<kScanThreads>(s, lds, &total);
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) {
+        if (base + k < N) *reinterpret_cast<int2*>(rays_live + 2 * (size_t)(base + k)) = make_int2((int32_t)off, (int32_t)c[k]);
+        off += c[k];
+    }
+}
+
+// rows [so, so + cnt) of src -> rows [dof, dof + cnt) of dst, `w` elements per row, as one contiguous range of elements
+template <typename T>
+__device__ __forceinline__ void copy_rows(const T* __restrict__ src, T* __restrict__ dst, size_t so, size_t dof, uint32_t cnt, uint32_t w,
+                                          int lane) {
+    const T* s = src + so * w;
+    T* d = dst + dof * w;
+    const size_t n = (size_t)cnt * w;
+    for (size_t i = (size_t)lane; i < n; i += 64) d[i] = s[i];
+}
+
+struct GatherP {
+    const uint32_t* xyzs; uint32_t* xyzs_live;
+    const uint32_t* ts; uint32_t* ts_live;
+    const uint32_t* sigmas; uint32_t* sigmas_live;
+    const void* rgbs; void* rgbs_live;
+    uint32_t channels, rgbs_f16;
+};
+
+__global__ __launch_bounds__(256) void k_nt_gather(GatherP p, const int32_t* __restrict__ rays, const int32_t* __restrict__ rays_live, uint32_t N,
+                                                   uint32_t M, uint32_t M_live) {
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = dwg_lane();
+    for (uint32_t r = 0; r < kRaysPerWave; ++r) {
+        const uint32_t n = wave * kRaysPerWave + r;
+        if (n >= N) return;
+        const int2 src = *reinterpret_cast<const int2*>(rays + 2 * (size_t)n);
+        const int2 dst = *reinterpret_cast<const int2*>(rays_live + 2 * (size_t)n);
+        const uint32_t so = (uint32_t)src.x, sc = (uint32_t)src.y, dof = (uint32_t)dst.x, cnt = (uint32_t)dst.y;
+        if (cnt == 0 || cnt > sc || so > M || sc > M - so || dof > M_live || cnt > M_live - dof) continue;
+        if (p.xyzs) copy_rows<uint32_t>(p.xyzs, p.xyzs_live, so, dof, cnt, 3, lane);
+        if (p.ts) copy_rows<uint32_t>(p.ts, p.ts_live, so, dof, cnt, 2, lane);
+        if (p.sigmas) copy_rows<uint32_t>(p.sigmas, p.sigmas_live, so, dof, cnt, 1, lane);
+        if (p.rgbs) {
+            if (p.rgbs_f16 && p.channels == 4)                  // 8-byte rows: whole words, as the fp32 arrays
+                copy_rows<uint32_t>((const uint32_t*)p.rgbs, (uint32_t*)p.rgbs_live, so, dof, cnt, 2, lane);
+            else if (p.rgbs_f16)                                // 6-byte rows start on any half-word
+                copy_rows<uint16_t>((const uint16_t*)p.rgbs, (uint16_t*)p.rgbs_live, so, dof, cnt, 3, lane);
+            else
+                copy_rows<uint32_t>((const uint32_t*)p.rgbs, (uint32_t*)p.rgbs_live, so, dof, cnt, p.channels, lane);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dwg_nerf_train_workspace_bytes(uint32_t N) {
+    return (size_t)((N + kScanBlock - 1) / kScanBlock) * sizeof(uint32_t);
+}
+
+int dwg_nerf_train_compact_offsets(const int32_t* live, uint32_t N, int32_t* rays_live, int32_t* total, void* workspace,
+                                   size_t workspace_bytes, dwg_stream_t stream) {
+    if (N == 0) return DWG_OK;
+    if (!live || !rays_live || !total || ((uintptr_t)rays_live & 7)) return DWG_E_ARG;
+    if (!workspace || ((uintptr_t)workspace & 3)) return DWG_E_ARG;
+    if (workspace_bytes < dwg_nerf_train_workspace_bytes(N)) return DWG_E_CAPACITY;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nb = (N + kScanBlock - 1) / kScanBlock;
+    uint32_t* sums = (uint32_t*)workspace;
+    DWG_LAUNCH("nt_block_sums", k_nt_block_sums, dim3(nb), dim3(kScanThreads), 0, st, live, N, sums);
+    DWG_LAUNCH("nt_scan_sums", k_nt_scan_sums, dim3(1), dim3(1024), 0, st, sums, nb, total);
+    DWG_LAUNCH("nt_scan_down", k_nt_scan_down, dim3(nb), dim3(kScanThreads), 0, st, live, N, sums, rays_live);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_nerf_train_gather_live(const int32_t* rays, const int32_t* rays_live, uint32_t N, uint32_t M, uint32_t M_live, const float* xyzs,
+                               float* xyzs_live, const float* ts, float* ts_live, const float* sigmas, float* sigmas_live, const void* rgbs,
+                               void* rgbs_live, uint32_t channels, uint32_t rgbs_f16, dwg_stream_t stream) {
+    if (channels != 3 && channels != 4) return DWG_E_ARG;
+    if (rgbs_f16 > 1) return DWG_E_ARG;
+    if (!xyzs != !xyzs_live || !ts != !ts_live || !sigmas != !sigmas_live || !rgbs != !rgbs_live) return DWG_E_ARG;
+    if (M_live > M) return DWG_E_ARG;
+    if (N == 0 || M == 0 || M_live == 0) return DWG_OK;
+    if (!rays || !rays_live || ((uintptr_t)rays & 7) || ((uintptr_t)rays_live & 7)) return DWG_E_ARG;
+    if (((uintptr_t)xyzs | (uintptr_t)xyzs_live | (uintptr_t)ts | (uintptr_t)ts_live | (uintptr_t)sigmas | (uintptr_t)sigmas_live) & 3)
+        return DWG_E_ARG;
+    if (((uintptr_t)rgbs | (uintptr_t)rgbs_live) & (rgbs_f16 && channels == 3 ? 1 : 3)) return DWG_E_ARG;
+    if (!xyzs && !ts && !sigmas && !rgbs) return DWG_OK;
+    GatherP p;
+    p.xyzs = (const uint32_t*)xyzs; p.xyzs_live = (uint32_t*)xyzs_live;
+    p.ts = (const uint32_t*)ts; p.ts_live = (uint32_t*)ts_live;
+    p.sigmas = (const uint32_t*)sigmas; p.sigmas_live = (uint32_t*)sigmas_live;
+    p.rgbs = rgbs; p.rgbs_live = rgbs_live;
+    p.channels = channels; p.rgbs_f16 = rgbs_f16;
+    const uint32_t waves = (N + kRaysPerWave - 1) / kRaysPerWave;
+    DWG_LAUNCH("nt_gather", k_nt_gather, dim3((waves + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, rays, rays_live, N, M, M_live);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+}  // extern "C"

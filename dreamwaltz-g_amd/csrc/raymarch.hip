@@ -9,6 +9,7 @@
 //     (coalesced loads of its contiguous range), the transmittance is a wave prefix product and the running sums are wave prefix sums;
 //     the ray stops after the first lane whose transmittance drops below T_thresh (ballot).  Forward and backward run the same scan code,
 //     so the backward's running sums reproduce the forward's totals bit for bit, as the reference's sequential loops do.
+//     The `_live` forward (boundary B18, dwg_nerf_train.h) is the same pass that also reports where each ray stopped.
 // FP contraction is off in this file: the float32 restatement (tests/raymarch_cases.py) rounds every operation separately, and a
 // one-ulp change of t moves a sample across a voxel boundary.  No float atomics anywhere.
 #include <float.h>
@@ -18,6 +19,7 @@
 #include "../../include/dwg_raymarch.h"
 #include "morton.h"
 #include "raymarch_common.h"
+#include "scan_common.h"
 
 #pragma clang fp contract(off)
 
@@ -144,35 +146,7 @@ __global__ void k_march_write(MarchP p, const float* __restrict__ rays_o, const 
     }
 }
 
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-    const int lane = dwg_lane();
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// exclusive scan over the block (NT threads); *total = block sum.  lds: NT/64 + 1 words.
-template <int NT>
-__device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const int lane = dwg_lane(), w = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan_u32(v);
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (int i = 0; i < NT / 64; ++i) { const uint32_t c = lds[i]; lds[i] = s; s += c; }
-        lds[NT / 64] = s;
-    }
-    __syncthreads();
-    const uint32_t res = lds[w] + incl - v;
-    *total = lds[NT / 64];
-    __syncthreads();
-    return res;
-}
-
+// wave_incl_scan_u32 / block_excl_scan_u32: scan_common.h
 __global__ __launch_bounds__(kScanThreads) void k_scan_block_sums(const int32_t* __restrict__ rays, uint32_t N, uint32_t* __restrict__ sums) {
     __shared__ uint32_t lds[kScanThreads / 64 + 1];
     const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
@@ -310,17 +284,21 @@ __device__ __forceinline__ bool ray_ok(const int32_t* rays, uint32_t n, uint32_t
     return cnt != 0 && off <= M && cnt <= M - off;
 }
 
-template <int NC>
-__global__ __launch_bounds__(256) void k_composite_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
-                                                       const float* __restrict__ ts, const int32_t* __restrict__ rays, uint32_t M, uint32_t N,
-                                                       float T_thresh, uint32_t binarize, float* __restrict__ weights,
-                                                       float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image) {
+// The forward pass of a wave's rays.  LIVE: also live[n] = the number of leading samples of ray n that were composited (base + f + 1 in
+// the chunk where the stop fires, cnt for a ray that never stops, 0 for a ray ray_ok rejects), and `weights` may be NULL.  Without LIVE
+// this is k_composite_fwd as it always was.
+template <int NC, bool LIVE>
+__device__ __forceinline__ void composite_fwd_rays(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                   const float* __restrict__ ts, const int32_t* __restrict__ rays, uint32_t M, uint32_t N,
+                                                   float T_thresh, uint32_t binarize, float* __restrict__ weights,
+                                                   float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image,
+                                                   int32_t* __restrict__ live) {
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = dwg_lane();
     for (uint32_t r = 0; r < kRaysPerWave; ++r) {
         const uint32_t n = wave * kRaysPerWave + r;
         if (n >= N) return;
-        uint32_t off, cnt;
+        uint32_t off, cnt, used = 0;
         Carry<NC> c;
         c.T = 1.f; c.ws = 0.f; c.d = 0.f;
 #pragma unroll
@@ -329,7 +307,12 @@ __global__ __launch_bounds__(256) void k_composite_fwd(const float* __restrict__
             for (uint32_t base = 0; base < cnt; base += 64) {
                 Lane<NC> L;
                 const bool stop = composite_chunk<NC>(sigmas, rgbs, ts, off, cnt, base, T_thresh, binarize != 0, c, L);
-                if (L.keep) weights[(size_t)off + base + lane] = L.w;
+                if (LIVE) {
+                    if (L.keep && weights) weights[(size_t)off + base + lane] = L.w;
+                    used = base + (uint32_t)__popcll(__ballot(L.keep));     // the kept lanes are 0..f, or every lane inside the ray
+                } else {
+                    if (L.keep) weights[(size_t)off + base + lane] = L.w;
+                }
                 if (stop) break;
             }
         }
@@ -338,8 +321,26 @@ __global__ __launch_bounds__(256) void k_composite_fwd(const float* __restrict__
             depth[n] = c.d;
 #pragma unroll
             for (int k = 0; k < NC; ++k) image[(size_t)NC * n + k] = c.acc[k];
+            if (LIVE) live[n] = (int32_t)used;
         }
     }
+}
+
+template <int NC>
+__global__ __launch_bounds__(256) void k_composite_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                       const float* __restrict__ ts, const int32_t* __restrict__ rays, uint32_t M, uint32_t N,
+                                                       float T_thresh, uint32_t binarize, float* __restrict__ weights,
+                                                       float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image) {
+    composite_fwd_rays<NC, false>(sigmas, rgbs, ts, rays, M, N, T_thresh, binarize, weights, weights_sum, depth, image, nullptr);
+}
+
+template <int NC>
+__global__ __launch_bounds__(256) void k_composite_fwd_live(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                            const float* __restrict__ ts, const int32_t* __restrict__ rays, uint32_t M,
+                                                            uint32_t N, float T_thresh, uint32_t binarize, float* __restrict__ weights,
+                                                            float* __restrict__ weights_sum, float* __restrict__ depth,
+                                                            float* __restrict__ image, int32_t* __restrict__ live) {
+    composite_fwd_rays<NC, true>(sigmas, rgbs, ts, rays, M, N, T_thresh, binarize, weights, weights_sum, depth, image, live);
 }
 
 template <int NC>
@@ -559,6 +560,26 @@ int dwg_raymarch_composite_rays_train_forward(const float* sigmas, const float* 
     else
         DWG_LAUNCH("rm_composite_fwd", k_composite_fwd<4>, g, dim3(256), 0, (hipStream_t)stream, sigmas, rgbs, ts, rays, M, N, T_thresh,
                    binarize, weights, weights_sum, depth, image);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_raymarch_composite_rays_train_forward_live(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M,
+                                                   uint32_t N, uint32_t channels, float T_thresh, uint32_t binarize, float* weights,
+                                                   float* weights_sum, float* depth, float* image, int32_t* live, dwg_stream_t stream) {
+    if (channels != 3 && channels != 4) return DWG_E_ARG;
+    if (N == 0) return DWG_OK;
+    if (!rays || !weights_sum || !depth || !image || !live) return DWG_E_ARG;
+    if (M != 0 && (!sigmas || !rgbs || !ts)) return DWG_E_ARG;
+    if (((uintptr_t)ts & 7) || (channels == 4 && ((uintptr_t)rgbs & 15))) return DWG_E_ARG;
+    const uint32_t waves = (N + kRaysPerWave - 1) / kRaysPerWave;
+    const dim3 g((waves + 3) / 4);
+    if (channels == 3)
+        DWG_LAUNCH("rm_composite_fwd_live", k_composite_fwd_live<3>, g, dim3(256), 0, (hipStream_t)stream, sigmas, rgbs, ts, rays, M, N,
+                   T_thresh, binarize, weights, weights_sum, depth, image, live);
+    else
+        DWG_LAUNCH("rm_composite_fwd_live", k_composite_fwd_live<4>, g, dim3(256), 0, (hipStream_t)stream, sigmas, rgbs, ts, rays, M, N,
+                   T_thresh, binarize, weights, weights_sum, depth, image, live);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

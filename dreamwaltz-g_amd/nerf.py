@@ -8,7 +8,7 @@
                                  nerf_field; the reference's own Parameters are read in place (optimizer, checkpoints untouched).
                                  With cuda_ray it also rebinds update_extra_state to the native occupancy update (occupancy.py, B13)
                                  and run_cuda to the one-launch inference render (nerf_render.py, B14; with shaded_render=True
-                                 also for the shaded views, B15).
+                                 also for the shaded views, B15; with train_render=True also the training view, B18).
 Precision follows autocast: under torch.autocast(fp16) the kernels mirror the reference's fp16 rounding points (f16 MFMA, fp32
 accumulation), otherwise they compute in exact f32.  The arithmetic is csrc/nerf_field.hip; no CPU fallback.  Every buffer is checked
 (CUDA, contiguous, dtype, size) and a violation raises RuntimeError before any launch.
@@ -255,16 +255,19 @@ def _covered_call(x):
     return True
 
 
-def bind_nerf_network(ref, shaded_render=False):
+def bind_nerf_network(ref, shaded_render=False, train_render=False):
     """Rebind ref.common_forward / ref.local_geometry_forward to the fused kernels.  Returns None when bound, else the reason it was
     left unbound (also kept as ref._dwg_nerf_unbound).  Calls the kernels do not take (x requiring a gradient -- the autograd normal --,
     a CPU x, bf16 autocast) go to the original methods.  shaded_render: the installed run_cuda also takes the evaluation views with
-    shading 'normal', 'textureless' and 'lambertian' (nerf_render.covered_call, B15); off, they stay on the original method."""
+    shading 'normal', 'textureless' and 'lambertian' (nerf_render.covered_call, B15); off, they stay on the original method.
+    train_render: the installed run_cuda also takes the training view with shading 'albedo' (nerf_render.render_rays_train, B18: the
+    backward runs over the samples the composite used); off, training calls stay on the original method."""
     reason = unbound_reason(ref)
     if reason is not None:
         ref._dwg_nerf_unbound = reason
         return reason
     ref._dwg_shaded_render = bool(shaded_render)
+    ref._dwg_train_render = bool(train_render)
     if getattr(ref, "_dwg_nerf_bound", False):
         return None
     orig_common, orig_local = ref.common_forward, ref.local_geometry_forward
@@ -370,7 +373,8 @@ def _bind_update_extra_state(ref):
 def _bind_run_cuda(ref):
     """Install run_cuda on a bound network with cuda_ray: nerf_render.run_cuda, which renders an evaluation view (not training, shading
     'albedo' -- or a shaded view when ref._dwg_shaded_render --, no perturbation, CUDA fp32 rays, no autocast or fp16 autocast) in one
-    launch and hands every other call to the original method unchanged."""
+    launch, takes the training view with shading 'albedo' through nerf_render.render_rays_train when ref._dwg_train_render, and hands
+    every other call to the original method unchanged."""
     if "run_cuda" in ref.__dict__ or not getattr(ref, "cuda_ray", False) or not hasattr(type(ref), "run_cuda"):
         return
     from . import nerf_render
@@ -385,7 +389,8 @@ def _bind_run_cuda(ref):
 
 def unbind_nerf_network(ref):
     """Undo bind_nerf_network (the instance attributes go; the class methods show through again)."""
-    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "run_cuda", "_dwg_occupancy", "_dwg_shaded_render"):
+    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "run_cuda", "_dwg_occupancy", "_dwg_shaded_render",
+                 "_dwg_train_render"):
         if name in ref.__dict__:
             del ref.__dict__[name]
     ref._dwg_nerf_bound = False

@@ -7,21 +7,27 @@ zeroed buffers and one host wait per iteration.
   render_rays(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_size, encoder, sigma_net, sigma_scale, bound, ...)
                                  (weights_sum [N], depth [N], image [N, out_dim - 1][, counts [N]]) through dwg_nerf_render_infer
                                  or, with shading=..., dwg_nerf_render_shaded (include/dwg_nerf_render.h)
-  run_cuda(ref, orig, ...)       the statements of run_cuda around it, for a bound reference network (nerf.bind_nerf_network installs it)
+  render_rays_train(...)         the training render (boundary B18): march_rays_train -> field -> composite_rays_train as one autograd
+                                 function whose backward runs over the samples the composite used (include/dwg_nerf_train.h)
+  run_cuda(ref, orig, ...)       the statements of run_cuda around them, for a bound reference network (nerf.bind_nerf_network installs it)
 
 A ray's samples, and everything composited from them, are the loop's: the marching rule is the shared csrc/raymarch_common.h, the field
 is the fused kernel's field_tile, the composite is composite_rays' statements in their order.  The one difference: a ray stops after
 exactly max_steps composited samples, where the loop's budget (n_step per iteration) lets a ray still alive at the end take between
 max_steps and max_steps + 7; rays that end at far or by T_thresh are unaffected.  Precision follows autocast like nerf.nerf_field.
 No CPU fallback, no host synchronisation (after the encoder's offsets have been read once); every buffer is checked (CUDA, dtype, shape,
-contiguity) and a violation raises RuntimeError before any launch.  Nothing here records autograd state."""
+contiguity) and a violation raises RuntimeError before any launch.  render_rays records no autograd state; render_rays_train is the one
+autograd function here (its host reads: the march's M and 4 bytes of M_live)."""
 import ctypes
 
 import torch
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import nerf
 from . import pointcloud
+from . import raymarch
 
 _st = nerf._st
 _check = pointcloud._dev_check
@@ -99,6 +105,224 @@ def render_rays(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_siz
     return (weights_sum, depth, image, counts) if return_counts else (weights_sum, depth, image)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------------
+# training render (boundary B18)
+# ------------------------------------------------------------------------------------------------------------------------------------
+class _RenderRaysTrain(Function):
+    """march -> field -> composite in the forward; of the per-sample arrays only the rows the composite used are kept, and the backward
+    (composite backward -> field backward) runs over those.  `st`: the call's settings, and where the non-differentiable extras go."""
+
+    @staticmethod
+    def forward(ctx, st, rays_o, rays_d, nears, fars, bits, noises, counter, embeddings, sigma_scale, *wb):
+        spec, L, dev = st.spec, _lib.lib(), rays_o.device
+        N, ch = rays_o.shape[0], spec.out_dim - 1
+        # 1. the march of raymarch.march_rays_train: count pass, one host read of M, write pass
+        rays = torch.empty(N, 2, dtype=torch.int32, device=dev)
+        march = (rays_o, rays_d, bits, st.bound, st.contract, st.dt_gamma, st.max_steps, N, st.C, st.H, nears, fars)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        raymarch.march_rays_train_into(*march, None, None, None, rays, count, noises)
+        M = int(count.item())
+        if counter is not None:
+            counter[:1].add_(count)                                         # what the march adds to the caller's counter
+        xyzs = torch.zeros(M, 3, dtype=torch.float32, device=dev)
+        ts = torch.zeros(M, 2, dtype=torch.float32, device=dev)
+        if M:
+            dirs = torch.zeros(M, 3, dtype=torch.float32, device=dev)       # the write pass fills it; 'albedo' never reads it
+            raymarch.march_rays_train_into(*march, xyzs, dirs, ts, rays, count, noises)
+            del dirs
+        # 2. the field
+        sigmas = torch.empty(M, dtype=torch.float32, device=dev)
+        albedo = torch.empty(M, ch, dtype=torch.float16 if spec.precision else torch.float32, device=dev)
+        if M:
+            d = spec.desc(embeddings, sigma_scale, wb)
+            _lib.check(L.dwg_nerf_field_forward(ctypes.byref(d), _lib.ptr(xyzs), M, _lib.ptr(sigmas), _lib.ptr(albedo), _st(rays_o)),
+                       "dwg_nerf_field_forward")
+        rgbs = albedo.float() if spec.precision else albedo                 # the composite reads fp32, as composite_rays_train casts
+        # 3. the composite, which also reports where each ray stopped
+        weights = torch.zeros(M, dtype=torch.float32, device=dev) if st.return_weights else None
+        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        image = torch.empty(N, ch, dtype=torch.float32, device=dev)
+        live = torch.empty(N, dtype=torch.int32, device=dev)
+        _lib.check(L.dwg_raymarch_composite_rays_train_forward_live(
+            _lib.ptr(sigmas), _lib.ptr(rgbs), _lib.ptr(ts), _lib.ptr(rays), M, N, ch, ctypes.c_float(st.T_thresh), int(st.binarize),
+            _lib.ptr(weights), _lib.ptr(weights_sum), _lib.ptr(depth), _lib.ptr(image), _lib.ptr(live), _st(rays_o)),
+            "dwg_raymarch_composite_rays_train_forward_live")
+        del rgbs
+        st.M, st.weights, st.sigmas = M, weights, sigmas if st.return_sigmas else None
+        st.live = live if st.return_stats else None
+        if not (st.keep or st.return_stats):
+            st.M_live = None
+            return weights_sum, depth, image
+        # 4. offsets of the live samples; the one host read this render adds to the march's
+        rays_live = torch.empty(N, 2, dtype=torch.int32, device=dev)
+        total = torch.zeros(1, dtype=torch.int32, device=dev)
+        nbytes = int(L.dwg_nerf_train_workspace_bytes(N))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dwg_nerf_train_compact_offsets(_lib.ptr(live), N, _lib.ptr(rays_live), _lib.ptr(total), _lib.ptr(ws), nbytes, _st(rays_o)),
+                   "dwg_nerf_train_compact_offsets")
+        M_live = int(total.item()) if N and M else 0
+        st.M_live = M_live
+        if not st.keep:
+            return weights_sum, depth, image
+        # 5. the gather: only the live rows stay for the backward (nothing culled: the live rows are the rows, rays_live is rays)
+        if M_live == M:
+            xyzs_l, ts_l, sigmas_l, albedo_l = xyzs, ts, sigmas, albedo
+        else:
+            xyzs_l = torch.empty(M_live, 3, dtype=torch.float32, device=dev)
+            ts_l = torch.empty(M_live, 2, dtype=torch.float32, device=dev)
+            sigmas_l = torch.empty(M_live, dtype=torch.float32, device=dev)
+            albedo_l = torch.empty(M_live, ch, dtype=albedo.dtype, device=dev)
+        if 0 < M_live < M:
+            _lib.check(L.dwg_nerf_train_gather_live(
+                _lib.ptr(rays), _lib.ptr(rays_live), N, M, M_live, _lib.ptr(xyzs), _lib.ptr(xyzs_l), _lib.ptr(ts), _lib.ptr(ts_l),
+                _lib.ptr(sigmas), _lib.ptr(sigmas_l), _lib.ptr(albedo), _lib.ptr(albedo_l), ch, int(spec.precision), _st(rays_o)),
+                "dwg_nerf_train_gather_live")
+        ctx.st = st
+        ctx.save_for_backward(xyzs_l, ts_l, sigmas_l, albedo_l, rays_live, weights_sum, depth, image, embeddings, sigma_scale, *wb)
+        if st.debug is not None:
+            st.debug.update(rays=rays, rays_live=rays_live)
+        return weights_sum, depth, image
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_weights_sum, grad_depth, grad_image):
+        xyzs, ts, sigmas, albedo, rays_live, weights_sum, depth, image, embeddings, sigma_scale, *wb = ctx.saved_tensors
+        st, need = ctx.st, ctx.needs_input_grad
+        spec, L = st.spec, _lib.lib()
+        M, N, ch = xyzs.shape[0], rays_live.shape[0], spec.out_dim - 1
+        n_in = 10 + len(wb)
+        # the table gradient is added into, the others are overwritten (accumulate = 0), as in _NerfField.backward
+        g_emb = torch.zeros_like(embeddings) if need[8] else None
+        g_ss = torch.empty_like(sigma_scale) if (need[9] and spec.act == nerf.ACTIVATIONS['scaling']) else None
+        g_wb = [torch.empty_like(t) if need[10 + i] else None for i, t in enumerate(wb)]
+        out = (None,) * 8 + (g_emb, g_ss if need[9] else None, *g_wb)
+        assert len(out) == n_in
+        if g_emb is None and g_ss is None and all(t is None for t in g_wb):
+            return out
+        if M == 0:                                                          # no live sample: the kernels launch nothing
+            for t in [g_ss] + g_wb:
+                if t is not None:
+                    t.zero_()
+            return out
+
+        def g(t, like):
+            return torch.zeros_like(like) if t is None else t.float().contiguous()
+        # 1. the composite backward over the live rows; its temporaries go before the field backward allocates its workspace
+        rgbs = albedo.float()
+        grad_weights = torch.zeros(M, dtype=torch.float32, device=xyzs.device)
+        grad_sigmas = torch.zeros(M, dtype=torch.float32, device=xyzs.device)
+        grad_rgbs = torch.zeros(M, ch, dtype=torch.float32, device=xyzs.device)
+        raymarch.composite_rays_train_backward_into(
+            grad_weights, g(grad_weights_sum, weights_sum), g(grad_depth, depth), g(grad_image, image), sigmas, rgbs, ts, rays_live,
+            weights_sum, depth, image, M, N, st.T_thresh, st.binarize, grad_sigmas, grad_rgbs, ch)
+        del rgbs, grad_weights
+        if st.debug is not None:
+            st.debug.update(grad_sigmas_live=grad_sigmas, grad_rgbs_live=grad_rgbs)
+        dalbedo = grad_rgbs.to(albedo.dtype)
+        del grad_rgbs
+        # 2. the field backward over the live rows
+        gr = _lib.NerfFieldGradsC()
+        gr.embeddings = None if g_emb is None else g_emb.data_ptr()
+        for l in range(spec.num_layers):
+            gr.weight[l] = None if g_wb[2 * l] is None else g_wb[2 * l].data_ptr()
+            gr.bias[l] = None if g_wb[2 * l + 1] is None else g_wb[2 * l + 1].data_ptr()
+        gr.sigma_scale = None if g_ss is None else g_ss.data_ptr()
+        gr.accumulate = 0
+        d = spec.desc(embeddings, sigma_scale, wb)
+        nbytes = int(L.dwg_nerf_field_backward_workspace_bytes(ctypes.byref(d), M))
+        ws = torch.empty(max(nbytes, 1), device=xyzs.device, dtype=torch.uint8)
+        _lib.check(L.dwg_nerf_field_backward(ctypes.byref(d), _lib.ptr(xyzs), M, _lib.ptr(grad_sigmas), _lib.ptr(dalbedo), ctypes.byref(gr),
+                                             _lib.ptr(ws), nbytes, _st(xyzs)), "dwg_nerf_field_backward")
+        return out
+
+
+class _TrainSettings:
+    pass
+
+
+def render_rays_train(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_size, encoder, sigma_net, sigma_scale, bound, *,
+                      density_activation, density_prior, albedo_sigmoid, perturb=True, noises=None, dt_gamma=0, max_steps=1024,
+                      T_thresh=1e-4, binarize=False, contract=False, precision=None, counter=None, return_weights=False, return_sigmas=False,
+                      return_stats=False, _debug=None):
+    """The training render (boundary B18): what the training branch of run_cuda computes for shading 'albedo'
+    (core/nerf/nerf_renderer.py:334-349) -- raymarch.march_rays_train -> nerf.nerf_field -> raymarch.composite_rays_train -- as one
+    autograd function that keeps, for the backward, only the samples the composite used.  A ray stops at the first sample after which
+    T < T_thresh; the samples behind it get no weight and no gradient, so the composite backward and the field backward run over the
+    M_live <= M live rows.
+
+      -> weights_sum [N], depth [N], image [N, out_dim - 1]        fp32, bit-equal to the composition's; differentiable with respect to
+         [, weights [M]] [, sigmas [M]]                             encoder.embeddings, sigma_net's parameters and sigma_scale (rays are
+         [, {'M': int, 'M_live': int, 'live': int32 [N]}]           not differentiated).  The optional returns are not differentiable.
+
+    rays_o / rays_d [N, 3], nears / fars [N] fp32 on the device, none requiring grad.  perturb / noises [N]: as march_rays_train (noises
+    overrides the torch.rand(N) draw).  counter: an int32 device tensor whose first element the march adds M to (default: a private
+    zero).  precision: None follows autocast, 0 f32, 1 f16.  Host reads: the march's read of M, and 4 bytes of M_live; the backward reads
+    nothing.  Under no_grad / inference_mode, or when no parameter requires grad, nothing is gathered or saved.  The parameter gradients
+    are the composition's up to the order of the fp32 sums over samples (with T_thresh = 0, where no sample is culled, bit-equal)."""
+    st = _TrainSettings()
+    wb = []
+    try:
+        spec, emb_d, _, _ = pointcloud.field_spec(encoder, sigma_net, sigma_scale, bound, density_activation, density_prior, albedo_sigmoid, precision)
+    except ValueError as e:
+        raise RuntimeError(str(e)) from None
+    for lin in sigma_net.net:
+        wb += [lin.weight, lin.bias]
+    _check("rays_o", rays_o, torch.float32, (None, 3))
+    N = rays_o.shape[0]
+    _check("rays_d", rays_d, torch.float32, (N, 3))
+    _check("nears", nears, torch.float32, (N,))
+    _check("fars", fars, torch.float32, (N,))
+    for name, t in (("rays_o", rays_o), ("rays_d", rays_d), ("nears", nears), ("fars", fars)):
+        if t.requires_grad:
+            raise RuntimeError("render_rays_train does not differentiate the rays: %s requires grad" % name)
+    C, H = int(cascade), int(grid_size)
+    if C != cascade or H != grid_size or not (1 <= C <= 8 and 2 <= H <= 1024 and C * H ** 3 < 1 << 32) or H & (H - 1):
+        raise RuntimeError("bad occupancy grid shape: cascade %r, grid_size %r (a power of two: a cell's Morton index must stay below "
+                           "grid_size^3)" % (cascade, grid_size))
+    _check("density_bitfield", density_bitfield, torch.uint8, (C * H ** 3 // 8,))
+    if int(max_steps) != max_steps or not 1 <= max_steps < 1 << 31:
+        raise RuntimeError("max_steps must be an integer >= 1, got %r" % (max_steps,))
+    if N >= 1 << 31:
+        raise RuntimeError("render_rays_train takes fewer than 2^31 rays")
+    dev = rays_o.device
+    others = []
+    if noises is not None:
+        _check("noises", noises, torch.float32, (N,))
+        others.append(("noises", noises))
+    if counter is not None:
+        _check("counter", counter, torch.int32, (None,))
+        if counter.numel() < 1:
+            raise RuntimeError("counter must hold at least one element")
+        others.append(("counter", counter))
+    for name, t in [("rays_d", rays_d), ("nears", nears), ("fars", fars), ("density_bitfield", density_bitfield), ("embeddings", emb_d)] + others:
+        if t.device != dev:
+            raise RuntimeError("%s is on %s, rays_o on %s" % (name, t.device, dev))
+    st.spec, st.bound, st.C, st.H = spec, float(bound), C, H
+    st.contract, st.dt_gamma, st.max_steps = bool(contract), float(dt_gamma), int(max_steps)
+    st.T_thresh, st.binarize = float(T_thresh), bool(binarize)
+    st.return_weights, st.return_sigmas, st.return_stats = bool(return_weights), bool(return_sigmas), bool(return_stats)
+    st.debug = _debug
+    ss = sigma_scale.reshape(1)
+    # the saved state follows the CALLER's grad mode: inside Function.forward gradients are always off, and needs_input_grad does not
+    # know about inference_mode
+    st.keep = torch.is_grad_enabled() and any(t.requires_grad for t in [encoder.embeddings, ss] + wb)
+    with torch.cuda.device(dev):
+        if noises is None:
+            noises = torch.rand(N, device=dev) if perturb else torch.zeros(N, device=dev)
+        weights_sum, depth, image = _RenderRaysTrain.apply(st, rays_o, rays_d, nears, fars, density_bitfield, noises, counter,
+                                                           encoder.embeddings, ss, *wb)
+    out = [weights_sum, depth, image]
+    if return_weights:
+        out.append(st.weights)
+    if return_sigmas:
+        out.append(st.sigmas)
+    if return_stats:
+        out.append({'M': st.M, 'M_live': st.M_live, 'live': st.live})
+    st.weights = st.sigmas = st.live = None
+    return tuple(out)
+
+
 def covered_call(ref, rays_o, rays_d, shading, perturb, light_d=None):
     """The native render takes this run_cuda call: evaluation mode, no perturbation, CUDA fp32 rays, the bitfield and the parameters on
     the device, and no autocast dtype but fp16.  shading 'albedo' always; with the network bound with shaded_render, also 'normal' (the
@@ -117,6 +341,11 @@ def covered_call(ref, rays_o, rays_d, shading, perturb, light_d=None):
         if light_d is not None and not (isinstance(light_d, torch.Tensor) and light_d.dtype == torch.float32 and tuple(light_d.shape) == (3,)
                                         and isinstance(rays_o, torch.Tensor) and light_d.device == rays_o.device):
             return False
+    return _covered_state(ref, rays_o, rays_d)
+
+
+def _covered_state(ref, rays_o, rays_d):
+    """covered_call's conditions on the rays, the bitfield, the parameters and autocast (shared with covered_train_call)."""
     for t in (rays_o, rays_d):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
             return False
@@ -136,17 +365,33 @@ def covered_call(ref, rays_o, rays_d, shading, perturb, light_d=None):
     return True
 
 
+def covered_train_call(ref, rays_o, rays_d, shading):
+    """The native training render takes this run_cuda call: the network bound with train_render, in training mode, shading 'albedo',
+    rays that need no gradient, and covered_call's conditions on the rays, the bitfield, the parameters and autocast."""
+    if not ref.training or shading != 'albedo' or not getattr(ref, "_dwg_train_render", False) or not getattr(ref, "cuda_ray", False):
+        return False
+    if not _covered_state(ref, rays_o, rays_d) or rays_o.requires_grad or rays_d.requires_grad:
+        return False
+    sc = getattr(ref, "step_counter", None)
+    return isinstance(sc, torch.Tensor) and sc.is_cuda and sc.dtype == torch.int32 and sc.dim() == 2 and sc.shape[0] >= 16
+
+
 def _safe_normalize(x, eps=1e-20):
     return x / torch.sqrt(torch.clamp(torch.sum(x * x, -1, keepdim=True), min=eps))
 
 
 def run_cuda(ref, orig, rays_o, rays_d, light_d=None, ambient_ratio=1.0, shading='albedo', perturb=False, dt_gamma=0, max_steps=1024,
              T_thresh=1e-4, **kwargs):
-    """run_cuda of a bound network.  Calls the native render does not take (training, perturb, CPU, bf16 autocast; a shading other than
-    'albedo' unless the network was bound with shaded_render, see covered_call) go to `orig` unchanged.  The native branch keeps the original's statements around the loop: near_far_from_aabb with aabb_infer, the light_d
-    draw (it consumes the device generator as the original does), the reshapes and mask = nears < fars.  results['xyzs'], ['sigmas'] and
-    ['rgbs'] -- in the original the last loop iteration's leftovers, read by nothing outside training -- are None."""
-    if not covered_call(ref, rays_o, rays_d, shading, perturb, light_d) or not isinstance(ambient_ratio, (int, float)):
+    """run_cuda of a bound network.  Calls the native renders do not take (perturb in evaluation, CPU, bf16 autocast; a shading other
+    than 'albedo' unless the network was bound with shaded_render, see covered_call; a training call unless it was bound with
+    train_render, see covered_train_call) go to `orig` unchanged.  The native branches keep the original's statements around the render:
+    near_far_from_aabb with aabb_infer (aabb_train in training), the light_d draw (it consumes the device generator as the original
+    does), in training the step counter's statements, the reshapes and mask = nears < fars.  Evaluation: results['xyzs'], ['sigmas'] and
+    ['rgbs'] -- in the original the last loop iteration's leftovers, read by nothing outside training -- are None.  Training
+    (render_rays_train, B18): results['weights'] and ['sigmas'] are the full [M] arrays, detached; ['xyzs'] and ['rgbs'] are None; the
+    march adds its sample count into the step counter's row."""
+    train = covered_train_call(ref, rays_o, rays_d, shading)
+    if not train and (not covered_call(ref, rays_o, rays_d, shading, perturb, light_d) or not isinstance(ambient_ratio, (int, float))):
         return orig(rays_o, rays_d, light_d=light_d, ambient_ratio=ambient_ratio, shading=shading, perturb=perturb, dt_gamma=dt_gamma,
                     max_steps=max_steps, T_thresh=T_thresh, **kwargs)
     prefix = rays_o.shape[:-1]
@@ -155,7 +400,7 @@ def run_cuda(ref, orig, rays_o, rays_d, light_d=None, ambient_ratio=1.0, shading
     device = rays_o.device
 
     # pre-calculate near far
-    nears, fars = ref.raymarching.near_far_from_aabb(rays_o, rays_d, ref.aabb_infer)
+    nears, fars = ref.raymarching.near_far_from_aabb(rays_o, rays_d, ref.aabb_train if train else ref.aabb_infer)
 
     # random sample light_d if not provided
     if light_d is None:
@@ -163,18 +408,31 @@ def run_cuda(ref, orig, rays_o, rays_d, light_d=None, ambient_ratio=1.0, shading
         light_d = _safe_normalize(light_d)
 
     latent = bool(getattr(ref, "latent_mode", False))
-    weights_sum, depth, image = render_rays(
-        rays_o, rays_d, nears.float().contiguous(), fars.float().contiguous(), ref.density_bitfield, ref.cascade, ref.grid_size, ref.encoder,
-        ref.sigma_net, ref.sigma_scale, ref.bound, density_activation=ref.opt.density_activation, density_prior=ref.density_prior_type,
-        albedo_sigmoid=not latent, dt_gamma=dt_gamma, max_steps=max_steps, T_thresh=T_thresh, shading=shading,
-        light_d=light_d.contiguous() if shading != 'albedo' else None, ambient_ratio=ambient_ratio)
-
+    field = (ref.density_bitfield, ref.cascade, ref.grid_size, ref.encoder, ref.sigma_net, ref.sigma_scale, ref.bound)
     results = {}
+    xyzs, sigmas = None, None
+    if train:
+        # setup counter
+        counter = ref.step_counter[ref.local_step % 16]
+        counter.zero_()  # set to 0
+        ref.local_step += 1
+
+        weights_sum, depth, image, weights, sigmas = render_rays_train(
+            rays_o, rays_d, nears.float().contiguous(), fars.float().contiguous(), *field, density_activation=ref.opt.density_activation,
+            density_prior=ref.density_prior_type, albedo_sigmoid=not latent, perturb=perturb, dt_gamma=dt_gamma, max_steps=max_steps,
+            T_thresh=T_thresh, counter=counter, return_weights=True, return_sigmas=True)
+        results['weights'] = weights
+    else:
+        weights_sum, depth, image = render_rays(
+            rays_o, rays_d, nears.float().contiguous(), fars.float().contiguous(), *field, density_activation=ref.opt.density_activation,
+            density_prior=ref.density_prior_type, albedo_sigmoid=not latent, dt_gamma=dt_gamma, max_steps=max_steps, T_thresh=T_thresh,
+            shading=shading, light_d=light_d.contiguous() if shading != 'albedo' else None, ambient_ratio=ambient_ratio)
+
     results['image'] = image.reshape(*prefix, image.shape[-1])
     results['depth'] = depth.reshape(*prefix)
     results['weights_sum'] = weights_sum.reshape(*prefix)
     results['mask'] = (nears < fars).reshape(*prefix)
-    results['xyzs'] = None
-    results['sigmas'] = None
+    results['xyzs'] = xyzs
+    results['sigmas'] = sigmas
     results['rgbs'] = None
     return results

@@ -20,7 +20,9 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              trainer renders beside it, B15: 'normal' without autocast or under fp16 autocast, 'textureless'
                                              and rgb 'lambertian' without autocast, the seven field evaluations per sample, the
                                              finite-difference normal and the shading inside the one launch; latent 'lambertian' and the
-                                             lambert shadings under autocast stay on the reference's loop).  The
+                                             lambert shadings under autocast stay on the reference's loop; with DWG_BIND_NERF_TRAIN=1
+                                             also the training view with shading 'albedo', B18: march, field and composite as one autograd
+                                             function whose backward runs over the samples the composite used).  The
                                              network's own Parameters are read in place.  What the kernel does not cover (dual_mlp / dual_enc,
                                              density_prior smpl, a decoder_layer, a non-grid backbone) stays unbound with the reason in
                                              `_dwg_nerf_unbound`.  DWG_BIND_NERF=0: nothing is bound
@@ -74,6 +76,8 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              calc_gradients, tp_scheduler, pipe, decode_latents, isinstance checks) is the reference's own.
 
 Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's field network (B7) on the reference path
+             DWG_BIND_NERF_TRAIN = 1                  also bind the NeRF stage's training render (B18, nerf_render.render_rays_train); unset or
+                                                     any other value: training calls of run_cuda stay on the reference's statements
              DWG_BIND_INIT = 0                        leave the avatar constructor's geometry (B11) on the reference path (igl + pytorch3d)
              DWG_BIND_POINTCLOUD = 0                  leave the NeRF-to-Gaussian point-cloud export (B12) on the reference path
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
@@ -228,7 +232,10 @@ def bind_nerf(ref):
         return ref
     _pkg()
     from dreamwaltz_g_amd.nerf import bind_nerf_network
-    reason = bind_nerf_network(ref, shaded_render=True)
+    if os.environ.get("DWG_BIND_NERF_TRAIN", "0") == "1":
+        reason = bind_nerf_network(ref, shaded_render=True, train_render=True)
+    else:
+        reason = bind_nerf_network(ref, shaded_render=True)
     if reason is not None:
         print("[dwg_bind] NeRF field left on the reference path: %s" % reason, file=sys.stderr)
     return ref

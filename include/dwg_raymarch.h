@@ -56,6 +56,16 @@ int dwg_raymarch_composite_rays_train_forward(const float* sigmas /*[M]*/, const
                                               const int32_t* rays /*[N,2]*/, uint32_t M, uint32_t N, uint32_t channels, float T_thresh,
                                               uint32_t binarize, float* weights, float* weights_sum, float* depth, float* image,
                                               dwg_stream_t stream);
+/* The same pass, which also reports where each ray stopped (boundary B18, dwg_nerf_train.h).  weights (when given), weights_sum, depth
+ * and image are those of dwg_raymarch_composite_rays_train_forward, bit for bit; weights may be NULL.  live[n] is the number of leading
+ * samples of ray n that were composited: up to and including the sample where T first drops below T_thresh, rays[n,1] for a ray that
+ * never stops, 0 for an empty ray and for one whose range exceeds M.  Rows at or beyond live[n] get no weight and, in the backward, no
+ * gradient. */
+int dwg_raymarch_composite_rays_train_forward_live(const float* sigmas /*[M]*/, const float* rgbs /*[M,channels]*/,
+                                                   const float* ts /*[M,2]*/, const int32_t* rays /*[N,2]*/, uint32_t M, uint32_t N,
+                                                   uint32_t channels, float T_thresh, uint32_t binarize, float* weights /*[M] or NULL*/,
+                                                   float* weights_sum, float* depth, float* image, int32_t* live /*[N]*/,
+                                                   dwg_stream_t stream);
 /* the reference's gradient formula (raymarching.cu:652-694); grad_sigmas / grad_rgbs are written up to the same sample as the
  * forward pass (the caller pre-zeroes them) */
 int dwg_raymarch_composite_rays_train_backward(const float* grad_weights /*[M]*/, const float* grad_weights_sum /*[N]*/,
