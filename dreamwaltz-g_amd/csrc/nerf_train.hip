@@ -3,8 +3,8 @@
 //
 // composite_rays_train (the reference's core/nerf/raymarching/rgb/src/raymarching.cu:541-569) stops a ray at the first sample after which
 // T < T_thresh; its backward (:652-694) writes no gradient past it, and the field backward over those rows adds zeros.  raymarch.hip's
-// k_composite_fwd_live reports live[n], the count of leading samples ray n composited.  Here:
-//   - k_nt_block_sums / k_nt_scan_sums / k_nt_scan_down: the deterministic three-launch exclusive scan of raymarch.hip's count pass over
+// k_composite_fwd<NC, LIVE> reports live[n], the count of leading samples ray n composited.  Here:
+//   - scan_counts (scan_common.h, the deterministic three-launch exclusive scan that raymarch.hip's training march uses too) over
 //     live[], written as (offset, live) pairs -- the `rays` layout the composite backward reads.
 //   - k_nt_gather: one wave per ray (kRaysPerWave consecutive rays per wave, as the composite) walks the ray's live rows and copies the
 //     words of every per-sample array from the ray's range in the full buffers to its range in the live ones.  Consecutive lanes take
@@ -17,61 +17,22 @@
 
 namespace {
 
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 4;                       // 1024 rays per scan block
-constexpr int kScanBlock = kScanThreads * kScanItems;
 constexpr int kRaysPerWave = 4;
 
-__device__ __forceinline__ uint32_t live_of(const int32_t* __restrict__ live, uint32_t n, uint32_t N) {
-    if (n >= N) return 0u;
-    const int32_t v = live[n];
-    return v > 0 ? (uint32_t)v : 0u;
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_nt_block_sums(const int32_t* __restrict__ live, uint32_t N, uint32_t* __restrict__ sums) {
-    __shared__ uint32_t lds[kScanThreads / 64 + 1];
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) s += live_of(live, base + k, N);
-    uint32_t total;
-    block_excl_scan_u32<kScanThreads>(s, lds, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one workgroup: block sums -> exclusive block offsets; total[0] = the sum
-__global__ __launch_bounds__(1024) void k_nt_scan_sums(uint32_t* __restrict__ sums, uint32_t nb, int32_t* __restrict__ total_out) {
-    __shared__ uint32_t lds[1024 / 64 + 1];
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nb; b0 += 1024) {
-        const uint32_t i = b0 + threadIdx.x;
-        const uint32_t v = i < nb ? sums[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_excl_scan_u32<1024>(v, lds, &total);
-        if (i < nb) sums[i] = carry + ex;
-        carry += total;
+// the scan of the live counts (scan_common.h): the count of ray n is max(live[n], 0), the pair (offset, count) goes to rays_live[n]
+struct LiveCount {
+    const int32_t* live;
+    __device__ __forceinline__ uint32_t operator()(uint32_t n) const {
+        const int32_t v = live[n];
+        return v > 0 ? (uint32_t)v : 0u;
     }
-    if (threadIdx.x == 0) total_out[0] = (int32_t)carry;
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_nt_scan_down(const int32_t* __restrict__ live, uint32_t N, const uint32_t* __restrict__ sums,
-                                                               int32_t* __restrict__ rays_live) {
-    __shared__ uint32_t lds[kScanThreads / 64 + 1];
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
-    uint32_t c[kScanItems], s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        c[k] = live_of(live, base + k, N);
-        s += c[k];
+};
+struct LivePair {
+    int32_t* rays_live;
+    __device__ __forceinline__ void operator()(uint32_t n, uint32_t off, uint32_t cnt) const {
+        *reinterpret_cast<int2*>(rays_live + 2 * (size_t)n) = make_int2((int32_t)off, (int32_t)cnt);
     }
-    uint32_t total;
-    uint32_t off = sums[blockIdx.x] + block_excl_scan_u32<kScanThreads>(s, lds, &total);
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        if (base + k < N) *reinterpret_cast<int2*>(rays_live + 2 * (size_t)(base + k)) = make_int2((int32_t)off, (int32_t)c[k]);
-        off += c[k];
-    }
-}
+};
 
 // rows [so, so + cnt) of src -> rows [dof, dof + cnt) of dst, `w` elements per row, as one contiguous range of elements
 template <typename T>
@@ -120,9 +81,7 @@ __global__ __launch_bounds__(256) void k_nt_gather(GatherP p, const int32_t* __r
 
 extern "C" {
 
-size_t dwg_nerf_train_workspace_bytes(uint32_t N) {
-    return (size_t)((N + kScanBlock - 1) / kScanBlock) * sizeof(uint32_t);
-}
+size_t dwg_nerf_train_workspace_bytes(uint32_t N) { return scan_workspace_bytes(N); }
 
 int dwg_nerf_train_compact_offsets(const int32_t* live, uint32_t N, int32_t* rays_live, int32_t* total, void* workspace,
                                    size_t workspace_bytes, dwg_stream_t stream) {
@@ -130,12 +89,8 @@ int dwg_nerf_train_compact_offsets(const int32_t* live, uint32_t N, int32_t* ray
     if (!live || !rays_live || !total || ((uintptr_t)rays_live & 7)) return DWG_E_ARG;
     if (!workspace || ((uintptr_t)workspace & 3)) return DWG_E_ARG;
     if (workspace_bytes < dwg_nerf_train_workspace_bytes(N)) return DWG_E_CAPACITY;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t nb = (N + kScanBlock - 1) / kScanBlock;
-    uint32_t* sums = (uint32_t*)workspace;
-    DWG_LAUNCH("nt_block_sums", k_nt_block_sums, dim3(nb), dim3(kScanThreads), 0, st, live, N, sums);
-    DWG_LAUNCH("nt_scan_sums", k_nt_scan_sums, dim3(1), dim3(1024), 0, st, sums, nb, total);
-    DWG_LAUNCH("nt_scan_down", k_nt_scan_down, dim3(nb), dim3(kScanThreads), 0, st, live, N, sums, rays_live);
+    scan_counts({"nt_block_sums", "nt_scan_sums", "nt_scan_down"}, LiveCount{live}, LivePair{rays_live}, N, (uint32_t*)workspace,
+                (uint32_t*)total, false, (hipStream_t)stream);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

@@ -4,7 +4,7 @@
 //   k_occ_ema       grid-strided over float4s; every lane keeps (count, fp64 sum, min, max, NaN seen) of the valid cells it updated, a
 //                   wave folds its lanes with shuffles, thread 0 folds the four waves in order -> one partial per workgroup
 //   k_occ_finalize  one workgroup: thread t folds partials t, t + 256, ... in order, then the same wave / workgroup fold -> stats [8]
-//   k_occ_packbits  k_packbits of raymarch.hip with the threshold read from stats
+//   packbits        dwg_raymarch_packbits_dev of raymarch.hip: its k_packbits with the threshold read from stats
 // The assignment of cells to lanes depends on C and H alone and every fold has a fixed order, so the statistics are bit-reproducible.
 // No atomics.
 #include <math.h>
@@ -91,16 +91,6 @@ __global__ __launch_bounds__(256) void k_occ_finalize(const OccPartial* __restri
     stats[6] = __uint_as_float((uint32_t)v.count); stats[7] = __uint_as_float((uint32_t)(v.count >> 32));
 }
 
-__global__ void k_occ_packbits(const float4* __restrict__ grid, uint32_t N, const float* __restrict__ thresh_p, uint8_t* __restrict__ bitfield) {
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    const float thresh = *thresh_p;
-    const float4 a = grid[2 * n], b = grid[2 * n + 1];
-    const uint32_t bits = (a.x > thresh ? 1u : 0u) | (a.y > thresh ? 2u : 0u) | (a.z > thresh ? 4u : 0u) | (a.w > thresh ? 8u : 0u) |
-                          (b.x > thresh ? 16u : 0u) | (b.y > thresh ? 32u : 0u) | (b.z > thresh ? 64u : 0u) | (b.w > thresh ? 128u : 0u);
-    bitfield[n] = (uint8_t)bits;
-}
-
 __global__ void k_occ_points(OccLattice l, uint64_t n3, float* __restrict__ out) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n3) return;
@@ -130,14 +120,6 @@ size_t dwg_occ_update_workspace_bytes(uint32_t C, uint32_t H) {
     uint32_t lg = 0;
     if (!occ_limits(C, H, lg)) return 0;
     return (size_t)occ_groups((uint32_t)(((uint64_t)C << (3u * lg)) / 4u)) * sizeof(OccPartial);
-}
-
-int dwg_raymarch_packbits_dev(const float* grid, uint32_t N, const float* density_thresh, uint8_t* bitfield, dwg_stream_t stream) {
-    if (N == 0) return DWG_OK;
-    if (!grid || !density_thresh || !bitfield || ((uintptr_t)grid & 15)) return DWG_E_ARG;
-    DWG_LAUNCH("occ_packbits", k_occ_packbits, dim3((N + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, (const float4*)grid, N, density_thresh, bitfield);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
 }
 
 int dwg_occ_update(float* density_grid, const float* tmp_grid, uint32_t C, uint32_t H, float decay, float density_thresh, uint8_t* bitfield,

@@ -3,8 +3,9 @@
 // finite-difference normal, colours and normals of the survivors, and the bounding-box keep mask.
 //
 // The selection is deterministic by construction: a block takes SEL_BLOCK consecutive entries as SEL_ITERS rounds of 256 (round-major,
-// so ascending in memory), every wave counts a round's survivors with ballot + popcount, the block counts are scanned by one workgroup,
-// and the write pass gives each surviving lane the slot block base + (rounds and waves before it) + lanes below it in the ballot.
+// so ascending in memory), every wave counts a round's survivors with ballot + popcount, the block counts are scanned by one workgroup
+// (k_scan_sums of scan_common.h, shared with raymarch.hip and nerf_train.hip), and the write pass gives each surviving lane the slot
+// block base + (rounds and waves before it) + lanes below it in the ballot.
 // No atomic decides a slot.  The pointwise kernels are one lane per output element (or per point where a point's outputs depend on
 // each other); nothing here uses LDS beyond the scans' few words.
 #include "dwg_common.h"
@@ -12,6 +13,7 @@
 #include "../../include/dwg_pointcloud.h"
 #include "fd_normal.h"
 #include "pointcloud_index.h"
+#include "scan_common.h"
 
 namespace {
 
@@ -63,40 +65,6 @@ __global__ __launch_bounds__(SEL_THREADS) void k_sel_block_sums(P pred, uint64_t
         for (int k = 0; k < SEL_ITERS * SEL_WAVES; k++) s += cnt[k];
         sums[blockIdx.x] = s;
     }
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, 64);
-        if (lane >= (uint32_t)d) v += u;
-    }
-    return v;
-}
-
-// one workgroup: block sums -> exclusive block bases; count[0] = the total
-__global__ __launch_bounds__(1024) void k_sel_scan_sums(uint32_t* __restrict__ sums, uint32_t nb, uint32_t* __restrict__ count) {
-    __shared__ uint32_t lds[1024 / 64 + 1];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nb; b0 += 1024u) {
-        const uint32_t i = b0 + threadIdx.x;
-        const uint32_t v = i < nb ? sums[i] : 0u;
-        const uint32_t incl = wave_incl_scan_u32(v);
-        if (lane == 63u) lds[wave] = incl;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t s = 0;
-            for (int k = 0; k < 1024 / 64; k++) { const uint32_t c = lds[k]; lds[k] = s; s += c; }
-            lds[1024 / 64] = s;
-        }
-        __syncthreads();
-        if (i < nb) sums[i] = carry + lds[wave] + incl - v;
-        carry += lds[1024 / 64];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) count[0] = carry;
 }
 
 template <typename P>
@@ -191,7 +159,7 @@ int select(const P& pred, uint64_t M, uint32_t* idx_out, uint64_t capacity, uint
     uint32_t* sums = reinterpret_cast<uint32_t*>(workspace);
     hipStream_t st = (hipStream_t)stream;
     DWG_LAUNCH("pc_select_block_sums", k_sel_block_sums<P>, dim3(nb), dim3(SEL_THREADS), 0, st, pred, M, sums);
-    DWG_LAUNCH("pc_select_scan_sums", k_sel_scan_sums, dim3(1), dim3(1024), 0, st, sums, nb, count_out);
+    DWG_LAUNCH("pc_select_scan_sums", k_scan_sums, dim3(1), dim3(kScanSumsThreads), 0, st, sums, nb, count_out, 0u);
     DWG_LAUNCH("pc_select_write", k_sel_write<P>, dim3(nb), dim3(SEL_THREADS), 0, st, pred, M, (const uint32_t*)sums, idx_out, capacity);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;

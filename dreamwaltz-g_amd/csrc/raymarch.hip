@@ -1,15 +1,17 @@
 // raymarch.hip -- occupancy-grid ray marcher and compositing of the NeRF stage for gfx950 (boundary B6).
 //
-// Native restatement of the reference's CUDA extension (/root/reference/core/nerf/raymarching/rgb/src/raymarching.cu: utils :92-326,
+// Native restatement of the reference's CUDA extension (core/nerf/raymarching/rgb/src/raymarching.cu: utils :92-326,
 // march_rays_train :338-475, composite_rays_train :501-695, march_rays :714-829, composite_rays :843-925; the latent variant differs only
 // in the colour width and has no `binarize`).  Two departures, both invisible to the callers:
-//   - march_rays_train: count pass (one lane per ray) -> three-launch exclusive scan of the counts -> write pass.  The offsets are
-//     ray-major and the output is bit-reproducible (the reference takes them with atomicAdd).
+//   - march_rays_train: count pass (one lane per ray) -> three-launch exclusive scan of the counts (scan_common.h, which
+//     nerf_train.hip and pointcloud.hip use too) -> write pass.  The offsets are ray-major and the output is bit-reproducible (the
+//     reference takes them with atomicAdd).
 //   - composite_rays_train: one WAVE per ray instead of one lane per ray.  The 64 lanes take 64 consecutive samples of the ray at a time
 //     (coalesced loads of its contiguous range), the transmittance is a wave prefix product and the running sums are wave prefix sums;
 //     the ray stops after the first lane whose transmittance drops below T_thresh (ballot).  Forward and backward run the same scan code,
 //     so the backward's running sums reproduce the forward's totals bit for bit, as the reference's sequential loops do.
-//     The `_live` forward (boundary B18, dwg_nerf_train.h) is the same pass that also reports where each ray stopped.
+//     The `_live` forward (boundary B18, dwg_nerf_train.h) is the same kernel, which then also reports where each ray stopped.
+// k_packbits serves dwg_raymarch_packbits and dwg_raymarch_packbits_dev, the last stage of occupancy.hip's dwg_occ_update.
 // FP contraction is off in this file: the float32 restatement (tests/raymarch_cases.py) rounds every operation separately, and a
 // one-ulp change of t moves a sample across a voxel boundary.  No float atomics anywhere.
 #include <float.h>
@@ -26,9 +28,6 @@
 namespace {
 
 constexpr float kRPi = 0.3183098861837907f;
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 4;                       // 1024 rays per scan block
-constexpr int kScanBlock = kScanThreads * kScanItems;
 constexpr int kRaysPerWave = 4;                     // composite: consecutive rays owned by one wave
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -88,9 +87,15 @@ __global__ void k_morton3d_invert(const int32_t* __restrict__ indices, uint32_t 
     coords[3 * n + 2] = (int32_t)morton3d_invert(ind >> 2);
 }
 
-__global__ void k_packbits(const float4* __restrict__ grid, uint32_t N, float thresh, uint8_t* __restrict__ bitfield) {
+// T = float: the threshold itself (dwg_raymarch_packbits); T = const float*: where it lies in device memory (dwg_raymarch_packbits_dev)
+__device__ __forceinline__ float thresh_of(float t) { return t; }
+__device__ __forceinline__ float thresh_of(const float* t) { return *t; }
+
+template <typename T>
+__global__ void k_packbits(const float4* __restrict__ grid, uint32_t N, T thresh_arg, uint8_t* __restrict__ bitfield) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
+    const float thresh = thresh_of(thresh_arg);
     const float4 a = grid[2 * n], b = grid[2 * n + 1];
     const uint32_t bits = (a.x > thresh ? 1u : 0u) | (a.y > thresh ? 2u : 0u) | (a.z > thresh ? 4u : 0u) | (a.w > thresh ? 8u : 0u) |
                           (b.x > thresh ? 16u : 0u) | (b.y > thresh ? 32u : 0u) | (b.z > thresh ? 64u : 0u) | (b.w > thresh ? 128u : 0u);
@@ -146,51 +151,15 @@ __global__ void k_march_write(MarchP p, const float* __restrict__ rays_o, const 
     }
 }
 
-// wave_incl_scan_u32 / block_excl_scan_u32: scan_common.h
-__global__ __launch_bounds__(kScanThreads) void k_scan_block_sums(const int32_t* __restrict__ rays, uint32_t N, uint32_t* __restrict__ sums) {
-    __shared__ uint32_t lds[kScanThreads / 64 + 1];
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k)
-        if (base + k < N) s += (uint32_t)rays[2 * (base + k) + 1];
-    uint32_t total;
-    block_excl_scan_u32<kScanThreads>(s, lds, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one workgroup: block sums -> exclusive block offsets (+ counter_in); counter[0] = counter_in + total
-__global__ __launch_bounds__(1024) void k_scan_sums(uint32_t* __restrict__ sums, uint32_t nb, int32_t* __restrict__ counter) {
-    __shared__ uint32_t lds[1024 / 64 + 1];
-    uint32_t carry = (uint32_t)counter[0];
-    for (uint32_t b0 = 0; b0 < nb; b0 += 1024) {
-        const uint32_t i = b0 + threadIdx.x;
-        const uint32_t v = i < nb ? sums[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_excl_scan_u32<1024>(v, lds, &total);
-        if (i < nb) sums[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) counter[0] = (int32_t)carry;
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_scan_down(int32_t* __restrict__ rays, uint32_t N, const uint32_t* __restrict__ sums) {
-    __shared__ uint32_t lds[kScanThreads / 64 + 1];
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
-    uint32_t c[kScanItems], s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        c[k] = base + k < N ? (uint32_t)rays[2 * (base + k) + 1] : 0u;
-        s += c[k];
-    }
-    uint32_t total;
-    uint32_t off = sums[blockIdx.x] + block_excl_scan_u32<kScanThreads>(s, lds, &total);
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        if (base + k < N) rays[2 * (base + k)] = (int32_t)off;
-        off += c[k];
-    }
-}
+// the scan of the counts (scan_common.h): the count of ray n is rays[n][1], its offset goes to rays[n][0]
+struct RayCount {
+    const int32_t* rays;
+    __device__ __forceinline__ uint32_t operator()(uint32_t n) const { return (uint32_t)rays[2 * n + 1]; }
+};
+struct RayOffset {
+    int32_t* rays;
+    __device__ __forceinline__ void operator()(uint32_t n, uint32_t off, uint32_t) const { rays[2 * n] = (int32_t)off; }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // training composite: one wave per ray, 64 samples per iteration
@@ -284,15 +253,15 @@ __device__ __forceinline__ bool ray_ok(const int32_t* rays, uint32_t n, uint32_t
     return cnt != 0 && off <= M && cnt <= M - off;
 }
 
-// The forward pass of a wave's rays.  LIVE: also live[n] = the number of leading samples of ray n that were composited (base + f + 1 in
-// the chunk where the stop fires, cnt for a ray that never stops, 0 for a ray ray_ok rejects), and `weights` may be NULL.  Without LIVE
-// this is k_composite_fwd as it always was.
+// The forward pass.  LIVE (dwg_raymarch_composite_rays_train_forward_live): also live[n] = the number of leading samples of ray n that were
+// composited (base + f + 1 in the chunk where the stop fires, cnt for a ray that never stops, 0 for a ray ray_ok rejects), and `weights`
+// may be NULL.  Without LIVE `live` is not touched.
 template <int NC, bool LIVE>
-__device__ __forceinline__ void composite_fwd_rays(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
-                                                   const float* __restrict__ ts, const int32_t* __restrict__ rays, uint32_t M, uint32_t N,
-                                                   float T_thresh, uint32_t binarize, float* __restrict__ weights,
-                                                   float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image,
-                                                   int32_t* __restrict__ live) {
+__global__ __launch_bounds__(256) void k_composite_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                       const float* __restrict__ ts, const int32_t* __restrict__ rays, uint32_t M, uint32_t N,
+                                                       float T_thresh, uint32_t binarize, float* __restrict__ weights,
+                                                       float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image,
+                                                       int32_t* __restrict__ live) {
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = dwg_lane();
     for (uint32_t r = 0; r < kRaysPerWave; ++r) {
@@ -324,23 +293,6 @@ __device__ __forceinline__ void composite_fwd_rays(const float* __restrict__ sig
             if (LIVE) live[n] = (int32_t)used;
         }
     }
-}
-
-template <int NC>
-__global__ __launch_bounds__(256) void k_composite_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
-                                                       const float* __restrict__ ts, const int32_t* __restrict__ rays, uint32_t M, uint32_t N,
-                                                       float T_thresh, uint32_t binarize, float* __restrict__ weights,
-                                                       float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image) {
-    composite_fwd_rays<NC, false>(sigmas, rgbs, ts, rays, M, N, T_thresh, binarize, weights, weights_sum, depth, image, nullptr);
-}
-
-template <int NC>
-__global__ __launch_bounds__(256) void k_composite_fwd_live(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
-                                                            const float* __restrict__ ts, const int32_t* __restrict__ rays, uint32_t M,
-                                                            uint32_t N, float T_thresh, uint32_t binarize, float* __restrict__ weights,
-                                                            float* __restrict__ weights_sum, float* __restrict__ depth,
-                                                            float* __restrict__ image, int32_t* __restrict__ live) {
-    composite_fwd_rays<NC, true>(sigmas, rgbs, ts, rays, M, N, T_thresh, binarize, weights, weights_sum, depth, image, live);
 }
 
 template <int NC>
@@ -454,6 +406,25 @@ __global__ void k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thre
 
 inline dim3 grid1d(uint32_t n, uint32_t bs) { return dim3((n + bs - 1) / bs); }
 
+// The checks and the channel dispatch of the two training-composite forwards.  The plain one wants `weights` when there are samples;
+// LIVE wants `live` and takes weights == NULL.
+template <bool LIVE>
+int composite_fwd(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N, uint32_t channels,
+                  float T_thresh, uint32_t binarize, float* weights, float* weights_sum, float* depth, float* image, int32_t* live,
+                  dwg_stream_t stream) {
+    if (channels != 3 && channels != 4) return DWG_E_ARG;
+    if (N == 0) return DWG_OK;
+    if (!rays || !weights_sum || !depth || !image || (LIVE && !live)) return DWG_E_ARG;
+    if (M != 0 && (!sigmas || !rgbs || !ts || (!LIVE && !weights))) return DWG_E_ARG;
+    if (((uintptr_t)ts & 7) || (channels == 4 && ((uintptr_t)rgbs & 15))) return DWG_E_ARG;
+    const uint32_t waves = (N + kRaysPerWave - 1) / kRaysPerWave;
+    const auto kernel = channels == 3 ? k_composite_fwd<3, LIVE> : k_composite_fwd<4, LIVE>;
+    DWG_LAUNCH_W(LIVE ? "rm_composite_fwd_live" : "rm_composite_fwd", "k_composite_fwd", 0.0, kernel, dim3((waves + 3) / 4), dim3(256), 0,
+                 (hipStream_t)stream, sigmas, rgbs, ts, rays, M, N, T_thresh, binarize, weights, weights_sum, depth, image, live);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -494,7 +465,17 @@ int dwg_raymarch_morton3d_invert(const int32_t* indices, uint32_t N, int32_t* co
 int dwg_raymarch_packbits(const float* grid, uint32_t N, float density_thresh, uint8_t* bitfield, dwg_stream_t stream) {
     if (N == 0) return DWG_OK;
     if (!grid || !bitfield || ((uintptr_t)grid & 15)) return DWG_E_ARG;
-    DWG_LAUNCH("rm_packbits", k_packbits, grid1d(N, 256), dim3(256), 0, (hipStream_t)stream, (const float4*)grid, N, density_thresh, bitfield);
+    DWG_LAUNCH("rm_packbits", k_packbits<float>, grid1d(N, 256), dim3(256), 0, (hipStream_t)stream, (const float4*)grid, N, density_thresh,
+               bitfield);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_raymarch_packbits_dev(const float* grid, uint32_t N, const float* density_thresh, uint8_t* bitfield, dwg_stream_t stream) {
+    if (N == 0) return DWG_OK;
+    if (!grid || !density_thresh || !bitfield || ((uintptr_t)grid & 15)) return DWG_E_ARG;
+    DWG_LAUNCH("occ_packbits", k_packbits<const float*>, grid1d(N, 256), dim3(256), 0, (hipStream_t)stream, (const float4*)grid, N,
+               density_thresh, bitfield);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }
@@ -507,9 +488,7 @@ int dwg_raymarch_flatten_rays(const int32_t* rays, uint32_t N, uint32_t M, int32
     return DWG_OK;
 }
 
-size_t dwg_raymarch_train_workspace_bytes(uint32_t N) {
-    return (size_t)((N + kScanBlock - 1) / kScanBlock) * sizeof(uint32_t);
-}
+size_t dwg_raymarch_train_workspace_bytes(uint32_t N) { return scan_workspace_bytes(N); }
 
 int dwg_raymarch_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, uint32_t contract,
                                   float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, const float* nears,
@@ -524,13 +503,10 @@ int dwg_raymarch_march_rays_train(const float* rays_o, const float* rays_d, cons
         if (!rays_o || !rays_d || !grid || !nears || !fars || !rays || !noises) return DWG_E_ARG;
         if (!workspace || workspace_bytes < dwg_raymarch_train_workspace_bytes(N)) return DWG_E_CAPACITY;
         const MarchP p = make_march(grid, bound, contract, dt_gamma, max_steps, C, H);
-        const uint32_t nb = (N + kScanBlock - 1) / kScanBlock;
-        uint32_t* sums = (uint32_t*)workspace;
         DWG_LAUNCH("rm_march_count", k_march_count, grid1d(N, 128), dim3(128), 0, st, p, rays_o, rays_d, nears, fars, noises, N, max_steps,
                    rays);
-        DWG_LAUNCH("rm_scan_block_sums", k_scan_block_sums, dim3(nb), dim3(kScanThreads), 0, st, rays, N, sums);
-        DWG_LAUNCH("rm_scan_sums", k_scan_sums, dim3(1), dim3(1024), 0, st, sums, nb, counter);
-        DWG_LAUNCH("rm_scan_down", k_scan_down, dim3(nb), dim3(kScanThreads), 0, st, rays, N, sums);
+        scan_counts({"rm_scan_block_sums", "rm_scan_sums", "rm_scan_down"}, RayCount{rays}, RayOffset{rays}, N, (uint32_t*)workspace,
+                    (uint32_t*)counter, true, st);                  // the offsets start from counter[0], which receives the total
         DWG_RETURN_IF_LAUNCH_FAILED();
         return DWG_OK;
     }
@@ -547,41 +523,13 @@ int dwg_raymarch_march_rays_train(const float* rays_o, const float* rays_d, cons
 int dwg_raymarch_composite_rays_train_forward(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M,
                                               uint32_t N, uint32_t channels, float T_thresh, uint32_t binarize, float* weights,
                                               float* weights_sum, float* depth, float* image, dwg_stream_t stream) {
-    if (channels != 3 && channels != 4) return DWG_E_ARG;
-    if (N == 0) return DWG_OK;
-    if (!rays || !weights_sum || !depth || !image) return DWG_E_ARG;
-    if (M != 0 && (!sigmas || !rgbs || !ts || !weights)) return DWG_E_ARG;
-    if (((uintptr_t)ts & 7) || (channels == 4 && ((uintptr_t)rgbs & 15))) return DWG_E_ARG;
-    const uint32_t waves = (N + kRaysPerWave - 1) / kRaysPerWave;
-    const dim3 g((waves + 3) / 4);
-    if (channels == 3)
-        DWG_LAUNCH("rm_composite_fwd", k_composite_fwd<3>, g, dim3(256), 0, (hipStream_t)stream, sigmas, rgbs, ts, rays, M, N, T_thresh,
-                   binarize, weights, weights_sum, depth, image);
-    else
-        DWG_LAUNCH("rm_composite_fwd", k_composite_fwd<4>, g, dim3(256), 0, (hipStream_t)stream, sigmas, rgbs, ts, rays, M, N, T_thresh,
-                   binarize, weights, weights_sum, depth, image);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
+    return composite_fwd<false>(sigmas, rgbs, ts, rays, M, N, channels, T_thresh, binarize, weights, weights_sum, depth, image, nullptr, stream);
 }
 
 int dwg_raymarch_composite_rays_train_forward_live(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M,
                                                    uint32_t N, uint32_t channels, float T_thresh, uint32_t binarize, float* weights,
                                                    float* weights_sum, float* depth, float* image, int32_t* live, dwg_stream_t stream) {
-    if (channels != 3 && channels != 4) return DWG_E_ARG;
-    if (N == 0) return DWG_OK;
-    if (!rays || !weights_sum || !depth || !image || !live) return DWG_E_ARG;
-    if (M != 0 && (!sigmas || !rgbs || !ts)) return DWG_E_ARG;
-    if (((uintptr_t)ts & 7) || (channels == 4 && ((uintptr_t)rgbs & 15))) return DWG_E_ARG;
-    const uint32_t waves = (N + kRaysPerWave - 1) / kRaysPerWave;
-    const dim3 g((waves + 3) / 4);
-    if (channels == 3)
-        DWG_LAUNCH("rm_composite_fwd_live", k_composite_fwd_live<3>, g, dim3(256), 0, (hipStream_t)stream, sigmas, rgbs, ts, rays, M, N,
-                   T_thresh, binarize, weights, weights_sum, depth, image, live);
-    else
-        DWG_LAUNCH("rm_composite_fwd_live", k_composite_fwd_live<4>, g, dim3(256), 0, (hipStream_t)stream, sigmas, rgbs, ts, rays, M, N,
-                   T_thresh, binarize, weights, weights_sum, depth, image, live);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
+    return composite_fwd<true>(sigmas, rgbs, ts, rays, M, N, channels, T_thresh, binarize, weights, weights_sum, depth, image, live, stream);
 }
 
 int dwg_raymarch_composite_rays_train_backward(const float* grad_weights, const float* grad_weights_sum, const float* grad_depth,

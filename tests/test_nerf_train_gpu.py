@@ -1,6 +1,7 @@
 """GPU tests of the training render (boundary B18, dreamwaltz_g_amd.nerf_render.render_rays_train; csrc/raymarch.hip
-k_composite_fwd_live, csrc/nerf_train.hip) against THE COMPOSITION it replaces, with the same noises:
+k_composite_fwd<NC, true>, csrc/nerf_train.hip) against THE COMPOSITION it replaces, with the same noises:
 raymarch.march_rays_train -> nerf.nerf_field -> raymarch.composite_rays_train."""
+import ctypes
 import functools
 
 import numpy as np
@@ -359,6 +360,30 @@ def test_argument_errors_raise_before_any_launch():
     bad(0, c.rays_o, counter=torch.zeros(1, device="cuda"))      # not int32
     bad(0, c.rays_o, max_steps=0)
     bad(0, c.rays_o, density_prior='smpl')
+
+
+@pytest.mark.parametrize("N", [1, 255, 1023, 1024, 1025, 4097, 1024 * 1024 + 5])
+def test_compact_offsets_against_cumsum(N):
+    """dwg_nerf_train_compact_offsets on its own: the pairs are (exclusive cumsum, max(live, 0)) and total is overwritten with the sum.
+    Sizes around the scan block of 1024 rays; the last one has more than 1024 blocks, so the scan of the block sums takes a second
+    trip and carries the first trip's total across.  Integers: exact.  The sum is at most 70 N < 7.4e7."""
+    from dreamwaltz_g_amd import _lib
+    L = _lib.lib()
+    live = torch.randint(-3, 71, (N,), generator=torch.Generator().manual_seed(N), dtype=torch.int32).cuda()
+    rays_live = torch.full((N, 2), -1, dtype=torch.int32, device="cuda")
+    total = torch.tensor([12345], dtype=torch.int32, device="cuda")
+    nbytes = int(L.dwg_nerf_train_workspace_bytes(N))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(L.dwg_nerf_train_compact_offsets(_lib.ptr(live), N, _lib.ptr(rays_live), _lib.ptr(total), _lib.ptr(ws), nbytes, stream),
+               "dwg_nerf_train_compact_offsets")
+    want = live.clamp(min=0)
+    if N > 1:
+        assert int((live < 0).sum()) > 0 and int((live > 0).sum()) > 0
+    assert torch.equal(rays_live[:, 1], want)
+    csum = torch.cumsum(want.long(), 0)
+    assert torch.equal(rays_live[:, 0], (csum - want.long()).to(torch.int32))
+    assert total.tolist() == [int(csum[-1])]
 
 
 def _bound_net(c, **kw):

@@ -1,5 +1,6 @@
 """GPU parity of the NeRF-stage ray marcher (boundary B6) against the CPU restatement in tests/raymarch_cases.py, driven through the
 drop-in backend modules exactly as the reference's raymarching.py drives its pybind backend.  Reads nothing of the reference."""
+import functools
 import os
 import sys
 
@@ -110,6 +111,73 @@ def test_march_rays_train_matches_restatement(perturb, dt_gamma, contract):
     for a, b in ((xyzs, rx), (dirs, rd), (ts, rt)):
         assert np.abs(a.cpu().numpy() - b).max() <= 1e-6
     assert (cnt > 0).mean() > 0.1 and (contract or (cnt == 0).any())      # under contraction the outer cells catch every ray
+
+
+SCAN_N = [1, 255, 1023, 1024, 1025, 4097, 1024 * 1024 + 5]
+SCAN_REF = 256                                                   # rays the restatement marches
+
+
+@functools.lru_cache(maxsize=None)
+def _scan_scene():
+    """Rays from the centre of a full grid (C = 1, H = 32, every bit set) with max_steps = 8: every step is a sample, so a ray's count is
+    its length over dt capped at 8, and the pass is short.  Every odd ray ends before it starts and has no sample.  Ray n depends on n
+    alone, so every N takes the first N rays.  -> device tensors, and the restatement's counts of the first SCAN_REF rays."""
+    n = max(SCAN_N)
+    rng = np.random.RandomState(18)
+    d = rng.randn(n, 3).astype(np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    o = np.zeros((n, 3), np.float32)
+    nears = np.full(n, 0.05, np.float32)
+    fars = (nears + 1.5 * rng.rand(n)).astype(np.float32)
+    fars[1::2] = 0.01
+    noises = np.zeros(n, np.float32)
+    bits = np.full(32 ** 3 // 8, 255, np.uint8)
+    k = SCAN_REF
+    ref = rc.march_train(o[:k], d[:k], bits, BOUND, False, 0.0, 8, 1, 32, nears[:k], fars[:k], noises[:k])[0]
+    return tuple(_cuda(a) for a in (o, d, bits, nears, fars, noises)) + (torch.from_numpy(ref).cuda(),)
+
+
+@pytest.mark.parametrize("N", SCAN_N)
+def test_march_count_pass_offsets_and_counter(N):
+    """The count pass of march_rays_train_into on its own: rays[:,0] = counter + exclusive cumsum of rays[:,1], counter += the sum.
+    Sizes around the scan block of 1024 rays; the last one has more than 1024 blocks, so the scan of the block sums takes a second
+    trip and carries the first trip's total across.  Integers: exact.  The input is not degenerate: the restatement's counts of the
+    first rays (which the device's equal) hold zeros and non-zeros."""
+    from dreamwaltz_g_amd import raymarch
+    o, d, bits, nears, fars, noises, ref = _scan_scene()
+    assert int((ref == 0).sum()) > 0 and int((ref > 0).sum()) > 0 and int(ref.max()) <= 8
+    rays = torch.full((N, 2), -1, dtype=torch.int32, device="cuda")
+    counter = torch.tensor([7], dtype=torch.int32, device="cuda")
+    raymarch.march_rays_train_into(o[:N], d[:N], bits, BOUND, False, 0.0, 8, N, 1, 32, nears[:N], fars[:N], None, None, None, rays, counter,
+                                   noises[:N])
+    cnt = rays[:, 1].long()
+    k = min(N, SCAN_REF)
+    assert torch.equal(rays[:k, 1], ref[:k])
+    assert int(cnt[1::2].count_nonzero()) == 0 and int(cnt.min()) >= 0
+    if N > 1:
+        assert int((cnt == 0).sum()) > 0 and int((cnt > 0).sum()) > 0
+    csum = torch.cumsum(cnt, 0)
+    assert torch.equal(rays[:, 0], (7 + csum - cnt).to(torch.int32))
+    assert counter.tolist() == [7 + int(csum[-1])]
+
+
+@pytest.mark.parametrize("n", [1, 257])
+def test_packbits_by_value_and_from_device_memory(n):
+    """dwg_raymarch_packbits (threshold by value) and dwg_raymarch_packbits_dev (threshold in device memory) on one grid with values
+    below, at and above the threshold, a NaN and both infinities: the same bytes, the restatement's.  The comparison is a strict >, and
+    a NaN threshold sets no bit."""
+    from dreamwaltz_g_amd import occupancy, raymarch
+    thresh = np.float32(0.37)
+    grid = np.random.RandomState(n).rand(8 * n).astype(np.float32)
+    grid[:8] = [thresh, np.nan, np.inf, 0.1, -np.inf, 0.9, np.nextafter(thresh, np.float32(1)), np.nextafter(thresh, np.float32(0))]
+    grid[8::5] = thresh
+    want = rc.packbits(grid, thresh)
+    assert want[0] == 0b01100100
+    g = _cuda(grid)
+    for t, w in ((thresh, want), (np.float32(np.nan), np.zeros(n, np.uint8))):
+        by_value = raymarch.packbits(g, float(t), torch.full((n,), 0xAA, dtype=torch.uint8, device="cuda"))
+        from_dev = occupancy.packbits_dev(g, _cuda(np.array([t], np.float32)), torch.full((n,), 0x55, dtype=torch.uint8, device="cuda"))
+        assert np.array_equal(by_value.cpu().numpy(), w) and np.array_equal(from_dev.cpu().numpy(), w)
 
 
 def _composite_case(channels, seed=0):
