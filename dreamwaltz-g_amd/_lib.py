@@ -98,6 +98,9 @@ SIGNATURES = {
     "dwg_nerf_field_backward_workspace_bytes": (_sz, [ctypes.POINTER(NerfFieldDescC), ctypes.c_uint64]),
     "dwg_nerf_field_backward": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _vp, _vp,
                                                ctypes.POINTER(NerfFieldGradsC), _vp, _sz, _vp]),
+    "dwg_nerf_field_forward_fd": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _f32, _vp, _vp, _vp, _vp]),
+    "dwg_nerf_field_backward_fd": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, ctypes.c_uint64, _f32, _vp, _vp, _vp,
+                                                  ctypes.POINTER(NerfFieldGradsC), _vp, _sz, _vp]),
     # include/dwg_nerf_render.h
     "dwg_nerf_render_infer": (ctypes.c_int, [ctypes.POINTER(NerfFieldDescC), _vp, _vp, _vp, _vp, _u32, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _f32,
                                              _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
@@ -152,6 +155,9 @@ SIGNATURES = {
     "dwg_nerf_train_workspace_bytes": (_sz, [_u32]),
     "dwg_nerf_train_compact_offsets": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _sz, _vp]),
     "dwg_nerf_train_gather_live": (ctypes.c_int, [_vp, _vp, _u32, _u32, _u32] + [_vp] * 8 + [_u32, _u32, _vp]),
+    "dwg_nerf_train_gather_live_rows": (ctypes.c_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "dwg_nerf_train_shade_forward": (ctypes.c_int, [_u32, _vp, _vp, _u32, _vp, _f32, _f32, _u32, _u32, _vp, _vp]),
+    "dwg_nerf_train_shade_backward": (ctypes.c_int, [_u32, _vp, _vp, _u32, _vp, _f32, _f32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "dwg_raymarch_composite_rays_train_backward": (ctypes.c_int, [_vp] * 11 + [_u32, _u32, _u32, _f32, _u32, _vp, _vp, _vp]),
     "dwg_raymarch_march_rays": (ctypes.c_int, [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp,
                                                _vp, _vp, _vp]),

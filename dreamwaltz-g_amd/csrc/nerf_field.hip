@@ -149,6 +149,15 @@ struct XOccupancy {                         // the jittered cell points of dwg_o
     }
 };
 
+struct XPointsFd {                          // x [M, 3] in memory (pass 0) or its shift pass - 1 of the finite-difference normal, made in registers
+    const float* __restrict__ x;
+    uint32_t pass;
+    float eps, bound;
+    __device__ __forceinline__ float operator()(uint64_t p0, uint32_t i) const {
+        const float v = x[p0 * 3 + i];
+        return pass == 0u ? v : fd_shift(v, i % 3u, pass - 1u, eps, bound);
+    }
+};
 struct XStaged {                            // the pending samples of the inference render, compacted into LDS in slot order
     const float* s;
     __device__ __forceinline__ float operator()(uint64_t p0, uint32_t i) const { return s[(uint32_t)p0 * 3u + i]; }
@@ -264,6 +273,42 @@ __global__ __launch_bounds__(256) void k_nf_fwd(NfP p, const float* __restrict__
     }
 }
 
+// The field at x and the density at its six shifts (dwg_nerf_field_forward_fd): k_nf_fwd's tile loop with seven passes of field_tile per
+// tile through XPointsFd.  Pass 0 stores what k_nf_fwd stores; pass s stores the density of shift s - 1, with the prior taken at the
+// shifted point (sx holds it), into sigma_fd [M, 6].  The shifted points exist in registers and LDS only.
+template <typename T>
+__global__ __launch_bounds__(256) void k_nf_fwd_fd(NfP p, const float* __restrict__ x, uint64_t M, uint64_t ntiles, float eps, float* __restrict__ sigma,
+                                                   T* __restrict__ albedo, float* __restrict__ sigma_fd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* lds; float *bias, *sx, *sxn, *red;
+    lds_carve(p, smem, lds, bias, sx, sxn, red);
+    load_weights(p, lds, bias);
+    const float es = p.act == 2 ? expf(*p.sigma_scale) : 0.f;
+    const uint32_t W = p.W;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t p0 = tile * NF_TILE;
+        for (uint32_t pass = 0; pass < 7u; ++pass) {
+            field_tile(p, XPointsFd{x, pass, eps, p.bound}, M, p0, lds, bias, sx, sxn);
+            const uint32_t t = threadIdx.x;
+            if (t < NF_TILE && p0 + t < M) {
+                const uint64_t pt = p0 + t;
+                const T* o = lds + p.aoff[p.nl] + t * p.ast[p.nl];
+                const float sg = nf_sigma(p, (float)o[0], sx + 3 * t, es);
+                if (pass == 0u) {
+                    sigma[pt] = sg;
+                    T* a = albedo + pt * (W - 1u);
+                    for (uint32_t c = 1; c < W; c++) {
+                        float v = (float)o[c];
+                        if (p.sig) v = 1.f / (1.f + expf(-v));
+                        a[c - 1] = (T)v;
+                    }
+                } else sigma_fd[pt * 6u + (pass - 1u)] = sg;
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // Density only, at the points of a lattice (dwg_pc_lattice_sigma): k_nf_fwd with the tile's x staged from the axis tables and without the
 // albedo.  minmax [DWG_PC_MINMAX_PAIRS][2]: this workgroup's (min, max) of the densities it wrote (NaN skipped), and (+inf, -inf) in the
 // pairs no workgroup owns (gridDim.x <= DWG_PC_MINMAX_PAIRS).
@@ -367,7 +412,8 @@ __device__ __forceinline__ bool composite_sample(float sigma, const float (&rgb)
 }
 
 // The colour of a sample from its density gradient g (fd_normal.h) and albedo: forward()'s statements for shading 'normal',
-// 'textureless' and 'lambertian', without FP contraction.  l = -light_d.
+// 'textureless' and 'lambertian', without FP contraction.  l = -light_d.  (shade_math.h's shade_color holds the same statements for the
+// training kernels and the host build; this copy stays as the inference kernels were compiled with it.)
 template <int NC>
 __device__ __forceinline__ void shade_sample(const ShadeP& sh, float lx, float ly, float lz, float g0, float g1, float g2, const float (&alb)[NC],
                                              float (&rgb)[NC]) {
@@ -535,9 +581,12 @@ __global__ __launch_bounds__(256) void k_nf_render_shaded(NfP p, MarchP m, Rende
     nf_render<T, NC, true>(p, m, q, sh, smem);
 }
 
-// One chunk [m0, m0 + n) of the backward.  partial: [gridDim.x][P] floats, overwritten when `first`, else added to.
-template <typename T>
-__global__ __launch_bounds__(256) void k_nf_bwd(NfP p, const float* __restrict__ x, uint64_t m0, uint64_t n, const float* __restrict__ dsigma,
+// One chunk [m0, m0 + n) of the backward.  partial: [gridDim.x][P] floats, overwritten when `first`, else added to.  XS: where the
+// points come from (XPoints, or XPointsFd for a pass of dwg_nerf_field_backward_fd); the density gradient of point pt is
+// dsigma[pt * ds_stride].  ALB false: the albedo has no gradient (the shifted points of the normal), the columns 1.. of d(last layer
+// output) are zero without a buffer of zeros being read.
+template <typename T, typename XS, bool ALB>
+__global__ __launch_bounds__(256) void k_nf_bwd(NfP p, XS x, uint64_t m0, uint64_t n, const float* __restrict__ dsigma, uint32_t ds_stride,
                                                 const T* __restrict__ dalbedo, float* __restrict__ d_enc, float* __restrict__ xn_out,
                                                 float* __restrict__ partial, int first, int want_w) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -563,7 +612,7 @@ __global__ __launch_bounds__(256) void k_nf_bwd(NfP p, const float* __restrict__
     float acc_b = 0.f, acc_s = 0.f;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t p0 = m0 + tile * NF_TILE;
-        field_tile(p, XPoints{x}, mend, p0, lds, bias, sx, sxn);
+        field_tile(p, x, mend, p0, lds, bias, sx, sxn);
         // d(last layer output), rounded to the operand type where autograd hands the reference an fp16 gradient
         if (threadIdx.x < NF_TILE) {
             const uint32_t t = threadIdx.x;
@@ -575,7 +624,7 @@ __global__ __launch_bounds__(256) void k_nf_bwd(NfP p, const float* __restrict__
             for (int c = 0; c < 16; c++) d[c] = 0.f;
             if (valid) {
                 if (xn_out) { for (int k = 0; k < 3; k++) xn_out[(pt - m0) * 3 + k] = sxn[3 * t + k]; }
-                const float g = dsigma[pt];
+                const float g = dsigma[pt * ds_stride];
                 const float h0 = (float)o[0];
                 if (p.raw) d[0] = g;
                 else {
@@ -584,13 +633,15 @@ __global__ __launch_bounds__(256) void k_nf_bwd(NfP p, const float* __restrict__
                     else if (p.act == 1) d[0] = nf_softplus_bwd(g, xv);
                     else { const float dy = nf_softplus_bwd(g, xv * es - 1.f); d[0] = dy * es; acc_s += dy * xv; }
                 }
-                const T* da = dalbedo + pt * (W - 1u);
+                if constexpr (ALB) {
+                    const T* da = dalbedo + pt * (W - 1u);
 #pragma unroll
-                for (int c = 1; c < 16; c++) {
-                    if ((uint32_t)c < W) {
-                        float gv = (float)da[c - 1];
-                        if (p.sig) { const float a = (float)(T)(1.f / (1.f + expf(-(float)o[c]))); gv = gv * (1.f - a) * a; }
-                        d[c] = gv;
+                    for (int c = 1; c < 16; c++) {
+                        if ((uint32_t)c < W) {
+                            float gv = (float)da[c - 1];
+                            if (p.sig) { const float a = (float)(T)(1.f / (1.f + expf(-(float)o[c]))); gv = gv * (1.f - a) * a; }
+                            d[c] = gv;
+                        }
                     }
                 }
             }
@@ -755,6 +806,15 @@ void lds_opt_in(K* kernel, bool& done) {
 uint64_t nf_chunk(uint64_t M) { return M < NF_CHUNK ? M : NF_CHUNK; }
 uint32_t nf_bwd_groups(uint64_t M) { const uint64_t t = (M + NF_TILE - 1) / NF_TILE; return (uint32_t)(t < NF_BWD_WG ? t : NF_BWD_WG); }
 
+// one launch of k_nf_bwd over the chunk [m0, m0 + n)
+template <typename T, typename XS, bool ALB>
+void launch_bwd(const NfP& p, const XS& x, uint64_t m0, uint64_t n, const float* dsigma, uint32_t ds_stride, const void* dalbedo, float* d_enc,
+                float* xn, float* partial, int first, int want_w, uint32_t G, size_t lds, hipStream_t st) {
+    static bool attr = false; lds_opt_in(&k_nf_bwd<T, XS, ALB>, attr);
+    DWG_LAUNCH("nerf_field_bwd", (k_nf_bwd<T, XS, ALB>), dim3(G), dim3(256), lds, st, p, x, m0, n, dsigma, ds_stride, (const T*)dalbedo, d_enc, xn,
+               partial, first, want_w);
+}
+
 template <typename T, int NC>
 int launch_render(const NfP& p, const MarchP& m, const RenderP& q, unsigned grid, size_t lds, hipStream_t st) {
     static bool attr = false; lds_opt_in(&k_nf_render<T, NC>, attr);
@@ -854,15 +914,12 @@ int dwg_nerf_field_backward(const dwg_nerf_field_desc* desc, const float* x, uin
     hipStream_t st = (hipStream_t)stream;
     for (uint64_t m0 = 0; m0 < M; m0 += ch) {
         const uint64_t n = M - m0 < ch ? M - m0 : ch;
-        if (desc->precision) {
-            static bool attr = false; lds_opt_in(&k_nf_bwd<_Float16>, attr);
-            DWG_LAUNCH("nerf_field_bwd", k_nf_bwd<_Float16>, dim3(G), dim3(256), lds, st, p, x, m0, n, dsigma, (const _Float16*)dalbedo,
-                       want_t ? d_enc : nullptr, want_t ? xn : nullptr, partial, m0 == 0 ? 1 : 0, want_w ? 1 : 0);
-        } else {
-            static bool attr = false; lds_opt_in(&k_nf_bwd<float>, attr);
-            DWG_LAUNCH("nerf_field_bwd", k_nf_bwd<float>, dim3(G), dim3(256), lds, st, p, x, m0, n, dsigma, (const float*)dalbedo,
-                       want_t ? d_enc : nullptr, want_t ? xn : nullptr, partial, m0 == 0 ? 1 : 0, want_w ? 1 : 0);
-        }
+        if (desc->precision)
+            launch_bwd<_Float16, XPoints, true>(p, XPoints{x}, m0, n, dsigma, 1u, dalbedo, want_t ? d_enc : nullptr, want_t ? xn : nullptr, partial,
+                                                m0 == 0 ? 1 : 0, want_w ? 1 : 0, G, lds, st);
+        else
+            launch_bwd<float, XPoints, true>(p, XPoints{x}, m0, n, dsigma, 1u, dalbedo, want_t ? d_enc : nullptr, want_t ? xn : nullptr, partial,
+                                             m0 == 0 ? 1 : 0, want_w ? 1 : 0, G, lds, st);
         DWG_RETURN_IF_LAUNCH_FAILED();
         if (want_t) {
             rc = dwg_grid_encode_backward_slabs(d_enc, xn, desc->embeddings, desc->offsets, grads->embeddings, (uint32_t)n, 3u, 2u,
@@ -870,6 +927,100 @@ int dwg_nerf_field_backward(const dwg_nerf_field_desc* desc, const float* x, uin
                                                 desc->gridtype, desc->align_corners ? 1u : 0u, desc->interp, 1u, desc->host_offsets,
                                                 slab_ws, slab_bytes, /*accumulate*/ 1, stream);
             if (rc) return rc;
+        }
+    }
+    if (want_w) {
+        DWG_LAUNCH("nerf_field_wgrad_reduce", k_nf_reduce, dim3((p.P + 255u) / 256u), dim3(256), 0, st, p, G, (const float*)partial, *grads);
+        DWG_RETURN_IF_LAUNCH_FAILED();
+    }
+    return DWG_OK;
+}
+
+int dwg_nerf_field_forward_fd(const dwg_nerf_field_desc* desc, const float* x, uint64_t M, float epsilon, float* sigma, void* albedo,
+                              float* sigma_fd, dwg_stream_t stream) {
+    NfP p;
+    size_t lds = 0;
+    int rc = make_params(desc, p, lds);
+    if (rc) return rc;
+    if (desc->raw || !(epsilon > 0.f)) return DWG_E_ARG;
+    if (M == 0) return DWG_OK;
+    if (!x || !sigma || !albedo || !sigma_fd) return DWG_E_ARG;
+    const uint64_t ntiles = (M + NF_TILE - 1) / NF_TILE;
+    const unsigned grid = (unsigned)(ntiles < 4096 ? ntiles : 4096);
+    hipStream_t st = (hipStream_t)stream;
+    if (desc->precision) {
+        static bool attr = false; lds_opt_in(&k_nf_fwd_fd<_Float16>, attr);
+        DWG_LAUNCH("nerf_field_fwd_fd", k_nf_fwd_fd<_Float16>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, epsilon, sigma, (_Float16*)albedo, sigma_fd);
+    } else {
+        static bool attr = false; lds_opt_in(&k_nf_fwd_fd<float>, attr);
+        DWG_LAUNCH("nerf_field_fwd_fd", k_nf_fwd_fd<float>, dim3(grid), dim3(256), lds, st, p, x, M, ntiles, epsilon, sigma, (float*)albedo, sigma_fd);
+    }
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_nerf_field_backward_fd(const dwg_nerf_field_desc* desc, const float* x, uint64_t M, float epsilon, const float* dsigma, const void* dalbedo,
+                               const float* dsigma_fd, const dwg_nerf_field_grads* grads, void* workspace, size_t workspace_bytes,
+                               dwg_stream_t stream) {
+    NfP p;
+    size_t lds = 0;
+    int rc = make_params(desc, p, lds);
+    if (rc) return rc;
+    if (!grads || desc->raw || !(epsilon > 0.f)) return DWG_E_ARG;
+    if (M == 0) return DWG_OK;
+    if (!x || !dsigma || !dsigma_fd) return DWG_E_ARG;
+    bool want_w = grads->sigma_scale != nullptr;
+    for (uint32_t l = 0; l < p.nl; l++) want_w = want_w || grads->weight[l] || grads->bias[l];
+    const bool want_t = grads->embeddings != nullptr;
+    if (grads->sigma_scale && p.act != 2) return DWG_E_ARG;
+    if (want_t) {
+        if (!desc->host_offsets) return DWG_E_ARG;
+        if ((uint64_t)desc->host_offsets[desc->num_levels] > 16384ull * 4096ull) return DWG_E_ARG;      // the slab pass's table limit
+    }
+    if (!want_w && !want_t) return DWG_OK;
+    if (!workspace || ((uintptr_t)workspace & 255u)) return DWG_E_ARG;
+    if (workspace_bytes < dwg_nerf_field_backward_workspace_bytes(desc, M)) return DWG_E_CAPACITY;
+    const uint64_t ch = nf_chunk(M);
+    const uint32_t G = nf_bwd_groups(M);
+    unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
+    float* partial = reinterpret_cast<float*>(w); w += dwg_align_up((size_t)G * p.P * sizeof(float), 256);
+    float* d_enc = reinterpret_cast<float*>(w); w += dwg_align_up((size_t)ch * p.K[0] * sizeof(float), 256);
+    float* xn = reinterpret_cast<float*>(w); w += dwg_align_up((size_t)ch * 3 * sizeof(float), 256);
+    void* slab_ws = w;
+    const size_t slab_bytes = want_t ? workspace_bytes - (size_t)(w - reinterpret_cast<unsigned char*>(workspace)) : 0;
+    float* de = want_t ? d_enc : nullptr;
+    float* xo = want_t ? xn : nullptr;
+    const int ww = want_w ? 1 : 0;
+    hipStream_t st = (hipStream_t)stream;
+    // The six shifted point sets first, chunk by chunk and in their +- pairs, then the points themselves: the two gradients of a pair
+    // have opposite signs and, through 0.5 / (eps |g|), can be many orders larger than the point's own, so they meet in the partials
+    // before anything smaller is added (on a constant density they cancel there exactly).  `first`: the very first launch.
+    int first = 1;
+    for (uint32_t round = 0; round < 2u; ++round) {
+        for (uint64_t m0 = 0; m0 < M; m0 += ch) {
+            const uint64_t n = M - m0 < ch ? M - m0 : ch;
+            for (uint32_t pass = round ? 0u : 1u; pass < (round ? 1u : 7u); ++pass) {
+                // pass 0: the points, with the density's own gradient and the albedo's when there is one; pass s: shift s - 1, column s - 1 of dsigma_fd
+                const XPointsFd xs{x, pass, epsilon, p.bound};
+                const float* ds = pass ? dsigma_fd + (pass - 1u) : dsigma;
+                const uint32_t stride = pass ? 6u : 1u;
+                if (desc->precision) {
+                    if (pass == 0u && dalbedo) launch_bwd<_Float16, XPointsFd, true>(p, xs, m0, n, ds, stride, dalbedo, de, xo, partial, first, ww, G, lds, st);
+                    else launch_bwd<_Float16, XPointsFd, false>(p, xs, m0, n, ds, stride, nullptr, de, xo, partial, first, ww, G, lds, st);
+                } else {
+                    if (pass == 0u && dalbedo) launch_bwd<float, XPointsFd, true>(p, xs, m0, n, ds, stride, dalbedo, de, xo, partial, first, ww, G, lds, st);
+                    else launch_bwd<float, XPointsFd, false>(p, xs, m0, n, ds, stride, nullptr, de, xo, partial, first, ww, G, lds, st);
+                }
+                DWG_RETURN_IF_LAUNCH_FAILED();
+                first = 0;
+                if (want_t) {
+                    rc = dwg_grid_encode_backward_slabs(d_enc, xn, desc->embeddings, desc->offsets, grads->embeddings, (uint32_t)n, 3u, 2u,
+                                                        desc->num_levels, desc->log2_per_level_scale, desc->base_resolution, nullptr, nullptr,
+                                                        desc->gridtype, desc->align_corners ? 1u : 0u, desc->interp, 1u, desc->host_offsets,
+                                                        slab_ws, slab_bytes, /*accumulate*/ 1, stream);
+                    if (rc) return rc;
+                }
+            }
         }
     }
     if (want_w) {

@@ -261,13 +261,16 @@ def bind_nerf_network(ref, shaded_render=False, train_render=False):
     a CPU x, bf16 autocast) go to the original methods.  shaded_render: the installed run_cuda also takes the evaluation views with
     shading 'normal', 'textureless' and 'lambertian' (nerf_render.covered_call, B15); off, they stay on the original method.
     train_render: the installed run_cuda also takes the training view with shading 'albedo' (nerf_render.render_rays_train, B18: the
-    backward runs over the samples the composite used); off, training calls stay on the original method."""
+    backward runs over the samples the composite used); off, training calls stay on the original method.  train_render='shaded': also
+    the training views with shading 'normal', 'textureless' and 'lambertian' (B19, nerf_render.covered_train_call); with True they stay
+    on the original method."""
     reason = unbound_reason(ref)
     if reason is not None:
         ref._dwg_nerf_unbound = reason
         return reason
     ref._dwg_shaded_render = bool(shaded_render)
     ref._dwg_train_render = bool(train_render)
+    ref._dwg_train_shaded = isinstance(train_render, str) and train_render == 'shaded'
     if getattr(ref, "_dwg_nerf_bound", False):
         return None
     orig_common, orig_local = ref.common_forward, ref.local_geometry_forward
@@ -373,8 +376,8 @@ def _bind_update_extra_state(ref):
 def _bind_run_cuda(ref):
     """Install run_cuda on a bound network with cuda_ray: nerf_render.run_cuda, which renders an evaluation view (not training, shading
     'albedo' -- or a shaded view when ref._dwg_shaded_render --, no perturbation, CUDA fp32 rays, no autocast or fp16 autocast) in one
-    launch, takes the training view with shading 'albedo' through nerf_render.render_rays_train when ref._dwg_train_render, and hands
-    every other call to the original method unchanged."""
+    launch, takes the training view with shading 'albedo' through nerf_render.render_rays_train when ref._dwg_train_render (the shaded
+    training views too when ref._dwg_train_shaded), and hands every other call to the original method unchanged."""
     if "run_cuda" in ref.__dict__ or not getattr(ref, "cuda_ray", False) or not hasattr(type(ref), "run_cuda"):
         return
     from . import nerf_render
@@ -390,7 +393,7 @@ def _bind_run_cuda(ref):
 def unbind_nerf_network(ref):
     """Undo bind_nerf_network (the instance attributes go; the class methods show through again)."""
     for name in ("common_forward", "local_geometry_forward", "update_extra_state", "run_cuda", "_dwg_occupancy", "_dwg_shaded_render",
-                 "_dwg_train_render"):
+                 "_dwg_train_render", "_dwg_train_shaded"):
         if name in ref.__dict__:
             del ref.__dict__[name]
     ref._dwg_nerf_bound = False

@@ -8,7 +8,8 @@ zeroed buffers and one host wait per iteration.
                                  (weights_sum [N], depth [N], image [N, out_dim - 1][, counts [N]]) through dwg_nerf_render_infer
                                  or, with shading=..., dwg_nerf_render_shaded (include/dwg_nerf_render.h)
   render_rays_train(...)         the training render (boundary B18): march_rays_train -> field -> composite_rays_train as one autograd
-                                 function whose backward runs over the samples the composite used (include/dwg_nerf_train.h)
+                                 function whose backward runs over the samples the composite used (include/dwg_nerf_train.h); with
+                                 shading=... the shaded one (B19): the backward also goes through the shading and the normal
   run_cuda(ref, orig, ...)       the statements of run_cuda around them, for a bound reference network (nerf.bind_nerf_network installs it)
 
 A ray's samples, and everything composited from them, are the loop's: the marching rule is the shared csrc/raymarch_common.h, the field
@@ -108,9 +109,18 @@ def render_rays(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_siz
 # ------------------------------------------------------------------------------------------------------------------------------------
 # training render (boundary B18)
 # ------------------------------------------------------------------------------------------------------------------------------------
+def _shade_train(L, st, sigma_fd, albedo, M, ch, rgbs, stream):
+    """dwg_nerf_train_shade_forward of the call's shading over M rows into rgbs [M, ch] fp32."""
+    _lib.check(L.dwg_nerf_train_shade_forward(
+        st.shading, _lib.ptr(sigma_fd), _lib.ptr(albedo) if st.shading == 3 else None, int(albedo.dtype == torch.float16), _lib.ptr(st.light_d),
+        ctypes.c_float(st.ratio), ctypes.c_float(st.eps), M, ch, _lib.ptr(rgbs), stream), "dwg_nerf_train_shade_forward")
+
+
 class _RenderRaysTrain(Function):
     """march -> field -> composite in the forward; of the per-sample arrays only the rows the composite used are kept, and the backward
-    (composite backward -> field backward) runs over those.  `st`: the call's settings, and where the non-differentiable extras go."""
+    (composite backward -> field backward) runs over those.  `st`: the call's settings, and where the non-differentiable extras go.
+    With st.shading (B19): the field also returns the densities at the six shifted points, the colours are shaded from them
+    (csrc/shade_math.h), and the backward goes composite -> shade -> the seven-point-set field backward, all over the live rows."""
 
     @staticmethod
     def forward(ctx, st, rays_o, rays_d, nears, fars, bits, noises, counter, embeddings, sigma_scale, *wb):
@@ -133,11 +143,20 @@ class _RenderRaysTrain(Function):
         # 2. the field
         sigmas = torch.empty(M, dtype=torch.float32, device=dev)
         albedo = torch.empty(M, ch, dtype=torch.float16 if spec.precision else torch.float32, device=dev)
-        if M:
+        sigma_fd = torch.empty(M, 6, dtype=torch.float32, device=dev) if st.shading else None
+        if M and st.shading:
+            d = spec.desc(embeddings, sigma_scale, wb)
+            _lib.check(L.dwg_nerf_field_forward_fd(ctypes.byref(d), _lib.ptr(xyzs), M, ctypes.c_float(st.eps), _lib.ptr(sigmas), _lib.ptr(albedo),
+                                                   _lib.ptr(sigma_fd), _st(rays_o)), "dwg_nerf_field_forward_fd")
+        elif M:
             d = spec.desc(embeddings, sigma_scale, wb)
             _lib.check(L.dwg_nerf_field_forward(ctypes.byref(d), _lib.ptr(xyzs), M, _lib.ptr(sigmas), _lib.ptr(albedo), _st(rays_o)),
                        "dwg_nerf_field_forward")
-        rgbs = albedo.float() if spec.precision else albedo                 # the composite reads fp32, as composite_rays_train casts
+        if st.shading:
+            rgbs = torch.empty(M, ch, dtype=torch.float32, device=dev)
+            _shade_train(L, st, sigma_fd, albedo, M, ch, rgbs, _st(rays_o))
+        else:
+            rgbs = albedo.float() if spec.precision else albedo             # the composite reads fp32, as composite_rays_train casts
         # 3. the composite, which also reports where each ray stopped
         weights = torch.zeros(M, dtype=torch.float32, device=dev) if st.return_weights else None
         weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
@@ -166,22 +185,35 @@ class _RenderRaysTrain(Function):
         if not st.keep:
             return weights_sum, depth, image
         # 5. the gather: only the live rows stay for the backward (nothing culled: the live rows are the rows, rays_live is rays)
+        if st.shading != 3 and st.shading:
+            albedo = albedo[:0]                                             # only 'lambertian' reads the albedo again
         if M_live == M:
-            xyzs_l, ts_l, sigmas_l, albedo_l = xyzs, ts, sigmas, albedo
+            xyzs_l, ts_l, sigmas_l, albedo_l, sigma_fd_l = xyzs, ts, sigmas, albedo, sigma_fd
         else:
             xyzs_l = torch.empty(M_live, 3, dtype=torch.float32, device=dev)
             ts_l = torch.empty(M_live, 2, dtype=torch.float32, device=dev)
             sigmas_l = torch.empty(M_live, dtype=torch.float32, device=dev)
-            albedo_l = torch.empty(M_live, ch, dtype=albedo.dtype, device=dev)
+            albedo_l = torch.empty(M_live if albedo.shape[0] else 0, ch, dtype=albedo.dtype, device=dev)
+            sigma_fd_l = torch.empty(M_live, 6, dtype=torch.float32, device=dev) if st.shading else None
         if 0 < M_live < M:
+            moved = albedo.shape[0] > 0
             _lib.check(L.dwg_nerf_train_gather_live(
                 _lib.ptr(rays), _lib.ptr(rays_live), N, M, M_live, _lib.ptr(xyzs), _lib.ptr(xyzs_l), _lib.ptr(ts), _lib.ptr(ts_l),
-                _lib.ptr(sigmas), _lib.ptr(sigmas_l), _lib.ptr(albedo), _lib.ptr(albedo_l), ch, int(spec.precision), _st(rays_o)),
-                "dwg_nerf_train_gather_live")
+                _lib.ptr(sigmas), _lib.ptr(sigmas_l), _lib.ptr(albedo) if moved else None, _lib.ptr(albedo_l) if moved else None, ch,
+                int(spec.precision), _st(rays_o)), "dwg_nerf_train_gather_live")
+            if st.shading:
+                _lib.check(L.dwg_nerf_train_gather_live_rows(_lib.ptr(rays), _lib.ptr(rays_live), N, M, M_live, _lib.ptr(sigma_fd),
+                                                             _lib.ptr(sigma_fd_l), 6, _st(rays_o)), "dwg_nerf_train_gather_live_rows")
         ctx.st = st
-        ctx.save_for_backward(xyzs_l, ts_l, sigmas_l, albedo_l, rays_live, weights_sum, depth, image, embeddings, sigma_scale, *wb)
+        if st.shading:
+            ctx.save_for_backward(xyzs_l, ts_l, sigmas_l, albedo_l, rays_live, weights_sum, depth, image, embeddings, sigma_scale, *wb,
+                                  sigma_fd_l, st.light_d)
+        else:
+            ctx.save_for_backward(xyzs_l, ts_l, sigmas_l, albedo_l, rays_live, weights_sum, depth, image, embeddings, sigma_scale, *wb)
         if st.debug is not None:
             st.debug.update(rays=rays, rays_live=rays_live)
+            if st.shading:
+                st.debug.update(xyzs_live=xyzs_l, ts_live=ts_l, sigmas_live=sigmas_l, albedo_live=albedo_l, sigma_fd_live=sigma_fd_l)
         return weights_sum, depth, image
 
     @staticmethod
@@ -189,6 +221,8 @@ class _RenderRaysTrain(Function):
     def backward(ctx, grad_weights_sum, grad_depth, grad_image):
         xyzs, ts, sigmas, albedo, rays_live, weights_sum, depth, image, embeddings, sigma_scale, *wb = ctx.saved_tensors
         st, need = ctx.st, ctx.needs_input_grad
+        if st.shading:
+            *wb, sigma_fd, _ = wb                                           # the last one is st.light_d, kept alive with the graph
         spec, L = st.spec, _lib.lib()
         M, N, ch = xyzs.shape[0], rays_live.shape[0], spec.out_dim - 1
         n_in = 10 + len(wb)
@@ -209,7 +243,11 @@ class _RenderRaysTrain(Function):
         def g(t, like):
             return torch.zeros_like(like) if t is None else t.float().contiguous()
         # 1. the composite backward over the live rows; its temporaries go before the field backward allocates its workspace
-        rgbs = albedo.float()
+        if st.shading:                                                      # the colours of the live rows again: the forward's bits
+            rgbs = torch.empty(M, ch, dtype=torch.float32, device=xyzs.device)
+            _shade_train(L, st, sigma_fd, albedo, M, ch, rgbs, _st(xyzs))
+        else:
+            rgbs = albedo.float()
         grad_weights = torch.zeros(M, dtype=torch.float32, device=xyzs.device)
         grad_sigmas = torch.zeros(M, dtype=torch.float32, device=xyzs.device)
         grad_rgbs = torch.zeros(M, ch, dtype=torch.float32, device=xyzs.device)
@@ -219,7 +257,18 @@ class _RenderRaysTrain(Function):
         del rgbs, grad_weights
         if st.debug is not None:
             st.debug.update(grad_sigmas_live=grad_sigmas, grad_rgbs_live=grad_rgbs)
-        dalbedo = grad_rgbs.to(albedo.dtype)
+        if st.shading:
+            # 1b. the shade backward: d colour -> d of the six shifted densities, and the albedo's gradient where the shading reads it
+            dsigma_fd = torch.empty(M, 6, dtype=torch.float32, device=xyzs.device)
+            dalbedo = torch.empty(M, ch, dtype=albedo.dtype, device=xyzs.device) if st.shading == 3 else None
+            _lib.check(L.dwg_nerf_train_shade_backward(
+                st.shading, _lib.ptr(sigma_fd), _lib.ptr(albedo) if st.shading == 3 else None, int(albedo.dtype == torch.float16),
+                _lib.ptr(st.light_d), ctypes.c_float(st.ratio), ctypes.c_float(st.eps), M, ch, _lib.ptr(grad_rgbs), _lib.ptr(dsigma_fd),
+                _lib.ptr(dalbedo), _st(xyzs)), "dwg_nerf_train_shade_backward")
+            if st.debug is not None:
+                st.debug.update(dsigma_fd_live=dsigma_fd, dalbedo_live=dalbedo)
+        else:
+            dalbedo = grad_rgbs.to(albedo.dtype)
         del grad_rgbs
         # 2. the field backward over the live rows
         gr = _lib.NerfFieldGradsC()
@@ -232,8 +281,13 @@ class _RenderRaysTrain(Function):
         d = spec.desc(embeddings, sigma_scale, wb)
         nbytes = int(L.dwg_nerf_field_backward_workspace_bytes(ctypes.byref(d), M))
         ws = torch.empty(max(nbytes, 1), device=xyzs.device, dtype=torch.uint8)
-        _lib.check(L.dwg_nerf_field_backward(ctypes.byref(d), _lib.ptr(xyzs), M, _lib.ptr(grad_sigmas), _lib.ptr(dalbedo), ctypes.byref(gr),
-                                             _lib.ptr(ws), nbytes, _st(xyzs)), "dwg_nerf_field_backward")
+        if st.shading:
+            _lib.check(L.dwg_nerf_field_backward_fd(ctypes.byref(d), _lib.ptr(xyzs), M, ctypes.c_float(st.eps), _lib.ptr(grad_sigmas),
+                                                    _lib.ptr(dalbedo), _lib.ptr(dsigma_fd), ctypes.byref(gr), _lib.ptr(ws), nbytes, _st(xyzs)),
+                       "dwg_nerf_field_backward_fd")
+        else:
+            _lib.check(L.dwg_nerf_field_backward(ctypes.byref(d), _lib.ptr(xyzs), M, _lib.ptr(grad_sigmas), _lib.ptr(dalbedo), ctypes.byref(gr),
+                                                 _lib.ptr(ws), nbytes, _st(xyzs)), "dwg_nerf_field_backward")
         return out
 
 
@@ -244,7 +298,7 @@ class _TrainSettings:
 def render_rays_train(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_size, encoder, sigma_net, sigma_scale, bound, *,
                       density_activation, density_prior, albedo_sigmoid, perturb=True, noises=None, dt_gamma=0, max_steps=1024,
                       T_thresh=1e-4, binarize=False, contract=False, precision=None, counter=None, return_weights=False, return_sigmas=False,
-                      return_stats=False, _debug=None):
+                      return_stats=False, _debug=None, shading='albedo', light_d=None, ambient_ratio=1.0, epsilon=1e-3):
     """The training render (boundary B18): what the training branch of run_cuda computes for shading 'albedo'
     (core/nerf/nerf_renderer.py:334-349) -- raymarch.march_rays_train -> nerf.nerf_field -> raymarch.composite_rays_train -- as one
     autograd function that keeps, for the backward, only the samples the composite used.  A ray stops at the first sample after which
@@ -259,7 +313,17 @@ def render_rays_train(rays_o, rays_d, nears, fars, density_bitfield, cascade, gr
     overrides the torch.rand(N) draw).  counter: an int32 device tensor whose first element the march adds M to (default: a private
     zero).  precision: None follows autocast, 0 f32, 1 f16.  Host reads: the march's read of M, and 4 bytes of M_live; the backward reads
     nothing.  Under no_grad / inference_mode, or when no parameter requires grad, nothing is gathered or saved.  The parameter gradients
-    are the composition's up to the order of the fp32 sums over samples (with T_thresh = 0, where no sample is culled, bit-equal)."""
+    are the composition's up to the order of the fp32 sums over samples (with T_thresh = 0, where no sample is culled, bit-equal).
+
+    shading 'normal' / 'textureless' / 'lambertian' (boundary B19): the colours come from the finite-difference normal with step epsilon
+    (seven field evaluations per sample in one launch, dwg_nerf_field_forward_fd) and forward()'s shading with light_d [3] fp32 on the
+    device (needed by the lambert shadings, never read on the host) and ambient_ratio; the backward goes through the shading and the
+    normal into the six shifted densities (csrc/shade_math.h restates torch autograd there) and through the field at all seven point
+    sets, over the live rows.  weights_sum, depth, weights, sigmas and live are the 'albedo' call's bits.  'lambertian' with a latent
+    field is ill-formed in the reference and refused; the lambert shadings are refused in f16 (the reference's normal @ -l is a
+    half-precision product under autocast, not restated); 'normal' runs in both precisions."""
+    if shading not in SHADINGS:
+        raise RuntimeError("shading must be one of %s, got %r" % (", ".join(sorted(SHADINGS)), shading))
     st = _TrainSettings()
     wb = []
     try:
@@ -287,6 +351,23 @@ def render_rays_train(rays_o, rays_d, nears, fars, density_bitfield, cascade, gr
         raise RuntimeError("render_rays_train takes fewer than 2^31 rays")
     dev = rays_o.device
     others = []
+    st.shading, st.light_d, st.ratio, st.eps = SHADINGS[shading], None, float(ambient_ratio), float(epsilon)
+    if st.shading:
+        if not st.eps > 0:
+            raise RuntimeError("epsilon must be positive, got %r" % (epsilon,))
+        if st.ratio != st.ratio:
+            raise RuntimeError("ambient_ratio is NaN")
+        if st.shading >= 2:
+            if light_d is None:
+                raise RuntimeError("shading %r needs light_d" % shading)
+            _check("light_d", light_d, torch.float32, (3,))
+            others.append(("light_d", light_d))
+            st.light_d = light_d.detach()
+            if spec.precision:
+                raise RuntimeError("shading %r is not taken in f16: the reference's normal @ -l is a half-precision product there" % shading)
+        if st.shading == 3 and spec.out_dim == 5:
+            raise RuntimeError("shading 'lambertian' with four albedo channels (latent mode) is ill-formed in the reference: five channels "
+                               "into a four-channel image")
     if noises is not None:
         _check("noises", noises, torch.float32, (N,))
         others.append(("noises", noises))
@@ -365,11 +446,23 @@ def _covered_state(ref, rays_o, rays_d):
     return True
 
 
-def covered_train_call(ref, rays_o, rays_d, shading):
+def covered_train_call(ref, rays_o, rays_d, shading, light_d=None):
     """The native training render takes this run_cuda call: the network bound with train_render, in training mode, shading 'albedo',
-    rays that need no gradient, and covered_call's conditions on the rays, the bitfield, the parameters and autocast."""
-    if not ref.training or shading != 'albedo' or not getattr(ref, "_dwg_train_render", False) or not getattr(ref, "cuda_ray", False):
+    rays that need no gradient, and covered_call's conditions on the rays, the bitfield, the parameters and autocast.  Bound with
+    train_render='shaded' (B19) also the shadings covered_call takes for a shaded evaluation view, on the same terms: 'normal' always,
+    'textureless' and rgb 'lambertian' without autocast, a given light_d a [3] fp32 tensor on the rays' device."""
+    if not ref.training or not getattr(ref, "_dwg_train_render", False) or not getattr(ref, "cuda_ray", False):
         return False
+    if shading != 'albedo':
+        if not getattr(ref, "_dwg_train_shaded", False) or shading not in SHADINGS:
+            return False
+        if shading != 'normal' and torch.is_autocast_enabled():
+            return False
+        if shading == 'lambertian' and ref.sigma_net.net[-1].out_features - 1 != 3:
+            return False
+        if light_d is not None and not (isinstance(light_d, torch.Tensor) and light_d.dtype == torch.float32 and tuple(light_d.shape) == (3,)
+                                        and isinstance(rays_o, torch.Tensor) and light_d.device == rays_o.device):
+            return False
     if not _covered_state(ref, rays_o, rays_d) or rays_o.requires_grad or rays_d.requires_grad:
         return False
     sc = getattr(ref, "step_counter", None)
@@ -384,13 +477,13 @@ def run_cuda(ref, orig, rays_o, rays_d, light_d=None, ambient_ratio=1.0, shading
              T_thresh=1e-4, **kwargs):
     """run_cuda of a bound network.  Calls the native renders do not take (perturb in evaluation, CPU, bf16 autocast; a shading other
     than 'albedo' unless the network was bound with shaded_render, see covered_call; a training call unless it was bound with
-    train_render, see covered_train_call) go to `orig` unchanged.  The native branches keep the original's statements around the render:
+    train_render, a shaded one unless with train_render='shaded', see covered_train_call) go to `orig` unchanged.  The native branches keep the original's statements around the render:
     near_far_from_aabb with aabb_infer (aabb_train in training), the light_d draw (it consumes the device generator as the original
     does), in training the step counter's statements, the reshapes and mask = nears < fars.  Evaluation: results['xyzs'], ['sigmas'] and
     ['rgbs'] -- in the original the last loop iteration's leftovers, read by nothing outside training -- are None.  Training
     (render_rays_train, B18): results['weights'] and ['sigmas'] are the full [M] arrays, detached; ['xyzs'] and ['rgbs'] are None; the
     march adds its sample count into the step counter's row."""
-    train = covered_train_call(ref, rays_o, rays_d, shading)
+    train = covered_train_call(ref, rays_o, rays_d, shading, light_d) and (shading == 'albedo' or isinstance(ambient_ratio, (int, float)))
     if not train and (not covered_call(ref, rays_o, rays_d, shading, perturb, light_d) or not isinstance(ambient_ratio, (int, float))):
         return orig(rays_o, rays_d, light_d=light_d, ambient_ratio=ambient_ratio, shading=shading, perturb=perturb, dt_gamma=dt_gamma,
                     max_steps=max_steps, T_thresh=T_thresh, **kwargs)
@@ -420,7 +513,8 @@ def run_cuda(ref, orig, rays_o, rays_d, light_d=None, ambient_ratio=1.0, shading
         weights_sum, depth, image, weights, sigmas = render_rays_train(
             rays_o, rays_d, nears.float().contiguous(), fars.float().contiguous(), *field, density_activation=ref.opt.density_activation,
             density_prior=ref.density_prior_type, albedo_sigmoid=not latent, perturb=perturb, dt_gamma=dt_gamma, max_steps=max_steps,
-            T_thresh=T_thresh, counter=counter, return_weights=True, return_sigmas=True)
+            T_thresh=T_thresh, counter=counter, return_weights=True, return_sigmas=True,
+            **({} if shading == 'albedo' else dict(shading=shading, light_d=light_d.contiguous(), ambient_ratio=ambient_ratio)))
         results['weights'] = weights
     else:
         weights_sum, depth, image = render_rays(

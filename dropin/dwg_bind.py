@@ -76,8 +76,10 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              calc_gradients, tp_scheduler, pipe, decode_latents, isinstance checks) is the reference's own.
 
 Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's field network (B7) on the reference path
-             DWG_BIND_NERF_TRAIN = 1                  also bind the NeRF stage's training render (B18, nerf_render.render_rays_train); unset or
-                                                     any other value: training calls of run_cuda stay on the reference's statements
+             DWG_BIND_NERF_TRAIN = 1                  also bind the NeRF stage's training render (B18, nerf_render.render_rays_train);
+                                 = shaded             and its shaded training views (B19: shading 'normal', 'textureless', 'lambertian', as the
+                                                     normal-adapted guidance renders them); unset or any other value: training calls of run_cuda
+                                                     stay on the reference's statements
              DWG_BIND_INIT = 0                        leave the avatar constructor's geometry (B11) on the reference path (igl + pytorch3d)
              DWG_BIND_POINTCLOUD = 0                  leave the NeRF-to-Gaussian point-cloud export (B12) on the reference path
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
@@ -232,7 +234,9 @@ def bind_nerf(ref):
         return ref
     _pkg()
     from dreamwaltz_g_amd.nerf import bind_nerf_network
-    if os.environ.get("DWG_BIND_NERF_TRAIN", "0") == "1":
+    if os.environ.get("DWG_BIND_NERF_TRAIN", "0") == "shaded":
+        reason = bind_nerf_network(ref, shaded_render=True, train_render='shaded')
+    elif os.environ.get("DWG_BIND_NERF_TRAIN", "0") == "1":
         reason = bind_nerf_network(ref, shaded_render=True, train_render=True)
     else:
         reason = bind_nerf_network(ref, shaded_render=True)

@@ -73,6 +73,26 @@ size_t dwg_nerf_field_backward_workspace_bytes(const dwg_nerf_field_desc* desc, 
 int dwg_nerf_field_backward(const dwg_nerf_field_desc* desc, const float* x, uint64_t M, const float* dsigma, const void* dalbedo,
                             const dwg_nerf_field_grads* grads, void* workspace, size_t workspace_bytes, dwg_stream_t stream);
 
+/* The field at x and the density at the six shifted points of the finite-difference normal (_NeRFNetwork.normal, nerf_model.py:146-159),
+ * in one launch (boundary B19): per tile of 64 points seven passes of the field, at x and at (x +- epsilon e_a).clamp(-bound, bound) for
+ * the shifts +x, -x, +y, -y, +z, -z, made in registers -- the shifted points never touch memory.  sigma / albedo are
+ * dwg_nerf_field_forward's bit for bit; sigma_fd [M, 6] fp32, column s is dwg_nerf_field_forward's density at the points of shift s bit
+ * for bit (the prior is taken at the shifted point).  desc->raw must be 0, epsilon > 0.  M == 0 launches nothing. */
+int dwg_nerf_field_forward_fd(const dwg_nerf_field_desc* desc, const float* x /*[M,3]*/, uint64_t M, float epsilon, float* sigma, void* albedo,
+                              float* sigma_fd, dwg_stream_t stream);
+
+/* The backward of dwg_nerf_field_forward_fd with respect to the parameters (x is not differentiated): dsigma [M], dalbedo [M, out_dim - 1]
+ * in the albedo dtype or NULL (the albedo has no gradient: no buffer of zeros is read), dsigma_fd [M, 6] fp32.  The chunk loop of
+ * dwg_nerf_field_backward with seven launches per chunk, one per point set (the six shifted sets of every chunk first, in their +-
+ * pairs, then the points: the opposite-signed gradients of a pair cancel before smaller terms are added); the weight-gradient partials
+ * accumulate across passes and chunks and are summed once at the end, the encoding gradient of a pass goes through dwg_grid_encode_backward_slabs (accumulate = 1)
+ * before the next pass reuses its buffer.  The result is what seven dwg_nerf_field_backward calls (accumulate = 1) on the shifted points
+ * give, up to the order of the fp32 sums; two runs are bit-identical.  workspace: dwg_nerf_field_backward_workspace_bytes(desc, M)
+ * bytes -- no more than one dwg_nerf_field_backward call takes --, 256-byte aligned. */
+int dwg_nerf_field_backward_fd(const dwg_nerf_field_desc* desc, const float* x, uint64_t M, float epsilon, const float* dsigma,
+                               const void* dalbedo, const float* dsigma_fd, const dwg_nerf_field_grads* grads, void* workspace,
+                               size_t workspace_bytes, dwg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,8 +13,8 @@
  * is the composite of the full rows, bit for bit.
  *
  * All pointers are device pointers; buffers are caller-allocated.  Every function checks its arguments before any launch (DWG_E_ARG,
- * DWG_E_CAPACITY) and runs on `stream`.  No float arithmetic, no atomics, no cross-workgroup flags: integer adds in a fixed order and
- * bit-for-bit copies.
+ * DWG_E_CAPACITY) and runs on `stream`.  No atomics, no cross-workgroup flags: integer adds in a fixed order, bit-for-bit copies and,
+ * in the two shade kernels, per-sample float arithmetic.
  */
 #ifndef DWG_NERF_TRAIN_H
 #define DWG_NERF_TRAIN_H
@@ -41,6 +41,30 @@ int dwg_nerf_train_gather_live(const int32_t* rays /*[N,2]*/, const int32_t* ray
                                const float* xyzs, float* xyzs_live, const float* ts, float* ts_live, const float* sigmas,
                                float* sigmas_live, const void* rgbs, void* rgbs_live, uint32_t channels /*3 or 4*/, uint32_t rgbs_f16,
                                dwg_stream_t stream);
+
+/* dwg_nerf_train_gather_live's rule for one more per-sample array of fp32 rows (boundary B19: the six shifted densities): src
+ * [M, floats_per_row] -> dst [M_live, floats_per_row], bit for bit, the same rays skipped.  1 <= floats_per_row <= 64. */
+int dwg_nerf_train_gather_live_rows(const int32_t* rays /*[N,2]*/, const int32_t* rays_live /*[N,2]*/, uint32_t N, uint32_t M, uint32_t M_live,
+                                    const float* src, float* dst, uint32_t floats_per_row, dwg_stream_t stream);
+
+/* The shaded training render (boundary B19) puts two per-sample kernels between the field and the composite:
+ *   dwg_raymarch_march_rays_train -> dwg_nerf_field_forward_fd (dwg_nerf.h) -> dwg_nerf_train_shade_forward -> composite ... and back:
+ *   composite backward -> dwg_nerf_train_shade_backward -> dwg_nerf_field_backward_fd, on the live rows.
+ * shade_forward: the colour of forward() (nerf_model.py:86-103) from sigma_fd [M, 6] (the densities at the six shifted points), the
+ * normal n = nan_to_num(safe_normalize(-0.5 (s+ - s-) / epsilon)): shading 1 'normal' (n + 1) / 2; 2 'textureless' and 3 'lambertian'
+ * from lam = ratio + (1 - ratio) clamp(n . -light_d, min=0).  albedo [M, channels] fp32 (albedo_f16 == 0) or fp16 is read by 'lambertian'
+ * only (NULL otherwise), which takes channels == 3.  light_d: device [3], NULL for 'normal'.  rgbs [M, channels] fp32; with channels ==
+ * 4 the fourth is the reference's zero pad.
+ * shade_backward: grad_rgbs [M, channels] fp32 -> dsigma_fd [M, 6] fp32 and, when dalbedo is given ('lambertian' must), dalbedo
+ * [M, channels] in the albedo dtype (zero for the other shadings).  It restates torch autograd for those statements: clamp(min) passes
+ * the gradient where its input is >= min, nan_to_num where its input is finite; the pad's gradient is dropped.
+ * sigma_fd and dsigma_fd are 8-byte aligned.  M == 0 launches nothing. */
+int dwg_nerf_train_shade_forward(uint32_t shading, const float* sigma_fd, const void* albedo, uint32_t albedo_f16, const float* light_d,
+                                 float ambient_ratio, float epsilon, uint32_t M, uint32_t channels /*3 or 4*/, float* rgbs,
+                                 dwg_stream_t stream);
+int dwg_nerf_train_shade_backward(uint32_t shading, const float* sigma_fd, const void* albedo, uint32_t albedo_f16, const float* light_d,
+                                  float ambient_ratio, float epsilon, uint32_t M, uint32_t channels, const float* grad_rgbs,
+                                  float* dsigma_fd, void* dalbedo, dwg_stream_t stream);
 
 #ifdef __cplusplus
 }

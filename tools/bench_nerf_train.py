@@ -2,7 +2,13 @@
 replaces -- raymarch.march_rays_train -> nerf.nerf_field -> raymarch.composite_rays_train, the entry points a bound network ran before
 it -- in one process, on the body cases of tools/bench_nerf_field.py (C = 2, H = 128, f16 as the recipe's --optim.fp16 runs it).
 
-    python tools/bench_nerf_train.py [--reps 7] [--sizes 128,256,512] [--limit 120]
+    python tools/bench_nerf_train.py [--reps 7] [--sizes 128,256,512] [--limit 120] [--shading normal|textureless|lambertian]
+
+--shading (boundary B19): the shaded training render against ITS composition, the statements a bound network's forward ran for the same
+call: march_rays_train -> seven launches of the fused field (the points and their six shifts) -> the torch statements of the normal and
+the shading (core/nerf/nerf_model.py:84-105, 146-169) -> composite_rays_train, and autograd through all of it.  'normal' runs under fp16
+autocast like the 'albedo' table; 'textureless' and 'lambertian' run in f32, where both paths take them.  weights_sum and depth are
+compared bit for bit, the image by its largest difference.
 
 Density levels:
   present    the network of tools/bench_nerf_field.py as it is (random weights, no density prior)
@@ -38,6 +44,29 @@ from tests import raymarch_cases as rc  # noqa: E402
 
 C, H, MAX_STEPS = 2, 128, 1024
 KW = dict(density_activation='exp', density_prior='none', albedo_sigmoid=True)
+AMBIENT, EPSILON = 0.1, 1e-3
+
+
+def shaded_composition(field, bound, x, light, shading):
+    """forward() and normal() of the reference's network over the fused field: (sigma, colour)."""
+    def sigma_at(p):
+        return nerf.nerf_field(p, *field, **KW)[0]
+    sigma, albedo = nerf.nerf_field(x, *field, **KW)
+    d = []
+    for a in range(3):
+        for sign in (1.0, -1.0):
+            v = [0.0, 0.0, 0.0]
+            v[a] = sign * EPSILON
+            d.append(sigma_at((x + torch.tensor([v], device=x.device)).clamp(-bound, bound)))
+    normal = - 0.5 * torch.stack([d[0] - d[1], d[2] - d[3], d[4] - d[5]], dim=-1) / EPSILON
+    normal = normal / torch.sqrt(torch.clamp(torch.sum(normal * normal, -1, keepdim=True), min=1e-20))
+    normal = torch.nan_to_num(normal)
+    if shading == 'normal':
+        return sigma, (normal + 1.0) / 2.0
+    lambertian = AMBIENT + (1 - AMBIENT) * (normal @ -light).clamp(min=0)
+    if shading == 'textureless':
+        return sigma, lambertian.unsqueeze(-1).repeat(1, 3)
+    return sigma, albedo * lambertian.unsqueeze(-1)
 
 
 @contextlib.contextmanager
@@ -81,7 +110,11 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sizes", default="128,256,512")
     ap.add_argument("--limit", type=int, default=120)
+    ap.add_argument("--shading", default="albedo", choices=["albedo", "normal", "textureless", "lambertian"])
     args = ap.parse_args()
+    shading = args.shading
+    f16 = shading in ("albedo", "normal")
+    light = torch.tensor([0.3, -0.5, 0.8]) / torch.tensor([0.3, -0.5, 0.8]).norm()
     if not torch.cuda.is_available():
         raise SystemExit("bench_nerf_train needs a GPU")
     if args.reps < 5:
@@ -89,6 +122,8 @@ def main():
     bound = nc.BOUND
     dt_min = 2.0 * math.sqrt(3.0) / MAX_STEPS
     aabb = torch.tensor([-bound] * 3 + [bound] * 3, device="cuda")
+    light = light.cuda()
+    shade_kw = {} if shading == "albedo" else dict(shading=shading, light_d=light, ambient_ratio=AMBIENT, epsilon=EPSILON)
     _, bits = rc.make_grid(C, H, bound, "body")
     bits = torch.from_numpy(bits).cuda()
     nets = {"present": nc.make_network(seed=0).cuda(), "opaque": nc.make_network(seed=0).cuda()}
@@ -112,14 +147,17 @@ def main():
             field = (net.encoder, net.sigma_net, net.sigma_scale, bound)
 
             def native(stats=False):
-                with torch.autocast("cuda", dtype=torch.float16):
+                with torch.autocast("cuda", dtype=torch.float16, enabled=f16):
                     return nerf_render.render_rays_train(o, d, nears, fars, bits, C, H, *field, **KW, noises=noises, max_steps=MAX_STEPS,
-                                                         T_thresh=T_thresh, return_stats=stats)
+                                                         T_thresh=T_thresh, return_stats=stats, **shade_kw)
 
             def composition():
-                with torch.autocast("cuda", dtype=torch.float16):
+                with torch.autocast("cuda", dtype=torch.float16, enabled=f16):
                     xyzs, dirs, ts, rays = rm.march_rays_train(o, d, bound, bits, C, H, nears, fars, False, 0, MAX_STEPS, noises=noises)
-                    sigmas, rgbs = nerf.nerf_field(xyzs, *field, **KW)
+                    if shading == "albedo":
+                        sigmas, rgbs = nerf.nerf_field(xyzs, *field, **KW)
+                    else:
+                        sigmas, rgbs = shaded_composition(field, bound, xyzs, light, shading)
                     return rm.composite_rays_train(sigmas, rgbs, ts, rays, T_thresh)[1:]
 
             def step(path, backward):
@@ -133,7 +171,8 @@ def main():
             with _limit(args.limit, "%d^2 %s set-up" % (W, level)):
                 *out_n, st = native(stats=True)
                 out_c = composition()
-                same = all(torch.equal(a, b) for a, b in zip(out_n, out_c))
+                same = all(torch.equal(a, b) for a, b in zip(out_n[:2] if shade_kw else out_n, out_c))
+                image_diff = float((out_n[2] - out_c[2]).abs().max()) if N else 0.0
                 live = st["live"]
                 has = live[live > 0]
                 live_med = float(has.float().median()) if has.numel() else 0.0
@@ -151,7 +190,7 @@ def main():
                 with _limit(args.limit, "%d^2 %s %s peak" % (W, level, name)):
                     peak = _peak(step(path, True))
                 row = dict(rays=N, density=level, T_thresh=T_thresh, M=st["M"], M_live=st["M_live"],
-                           culled=(st["M"] - st["M_live"]) / max(st["M"], 1), live_median=live_med, path=name, outputs_equal=same,
+                           culled=(st["M"] - st["M_live"]) / max(st["M"], 1), live_median=live_med, path=name, outputs_equal=same, shading=shading, image_max_diff=image_diff,
                            fwd_ms=_stats(times[(name, False)]), fwd_bwd_ms=_stats(times[(name, True)]), peak_bytes=peak)
                 rows.append(row)
 
@@ -163,7 +202,8 @@ def main():
             n, c_ = rows[-2], rows[-1]
             print("       %-9s native / composition: fwd %.3f, fwd + bwd %.3f (medians); composition's own f+b spread %.2f ms; outputs %s"
                   % (level, n["fwd_ms"]["median"] / c_["fwd_ms"]["median"], n["fwd_bwd_ms"]["median"] / c_["fwd_bwd_ms"]["median"],
-                     c_["fwd_bwd_ms"]["max"] - c_["fwd_bwd_ms"]["min"], "bit-equal" if same else "DIFFER"), flush=True)
+                     c_["fwd_bwd_ms"]["max"] - c_["fwd_bwd_ms"]["min"],
+                     ("bit-equal" if same else "DIFFER") + (" (weights_sum, depth; image max |diff| %.2g)" % image_diff if shade_kw else "")), flush=True)
         del o, d, nears, fars, noises
         torch.cuda.empty_cache()
     print(json.dumps(rows))
