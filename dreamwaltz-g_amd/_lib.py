@@ -256,6 +256,12 @@ SIGNATURES = {
     "dwg_image_loss_forward": (ctypes.c_int, [_i32] * 5 + [_f32] + [_vp, _i64, _i64, _i64, _i64] * 2 + [_vp, _vp, _vp, _vp, _sz, _vp]),
     "dwg_image_loss_backward": (ctypes.c_int, [_i32] * 5 + [ctypes.c_double] * 2 + [_vp, _i64, _i64, _i64, _i64] * 2
                                 + [_vp, _vp, _i32, _vp, _vp]),
+    # include/dwg_nerf_view.h
+    "dwg_nerf_view_rays": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dwg_nerf_view_compose_workspace_bytes": (_sz, [_u32]),
+    "dwg_nerf_view_compose_forward": (ctypes.c_int, [_u32, _u32, _u32, _vp, _vp, _vp, _u32] + [ctypes.c_double] * 4 + [_vp, _vp, _vp, _sz, _vp]),
+    "dwg_nerf_view_compose_backward": (ctypes.c_int, [_u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32] + [ctypes.c_double] * 4
+                                       + [_vp, _sz, _vp, _vp, _vp, _vp]),
     # include/dwg_graph.h
     "dwg_graph_begin_capture": (ctypes.c_int, [_vp]),
     "dwg_graph_end_capture": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),

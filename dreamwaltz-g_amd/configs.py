@@ -77,6 +77,36 @@ class OptimConfig:
 class NeRFConfig:
     lr: float = 0.001
     bound: float = 2.0
+    # what the stage-I model and trainer read (nerf_model.NeRFNetwork, nerf_trainer.NeRFSDSTrainer; configs/__init__.py:9-91)
+    desired_resolution: int = 2048
+    num_levels: int = 16
+    level_dim: int = 2
+    base_resolution: int = 16
+    density_activation: str = 'exp'
+    cuda_ray: bool = True
+    grid_size: int = 128
+    max_steps: int = 1024
+    update_extra_interval: int = 16
+    density_thresh: float = 10
+    dt_gamma: float = 0
+    min_near: float = 0.1
+    backbone: str = 'tiledgrid'
+    nerf_type: str = 'rgb'
+    structure: str = 'shared_mlp'
+    density_prior: str = 'none'
+    bg_mode: str = 'gray'
+    bg_radius: float = 3.0
+    rand_bg_prob: Optional[float] = None
+    detach_bg_weights_sum: bool = False
+    dmtet: bool = False
+    optimizer: str = 'adam'
+    bg_lr: float = 0.001
+    lr_policy: str = 'constant'
+    lambda_opacity: float = 0.0
+    lambda_entropy: float = 0.0
+    lambda_emptiness: float = 0.0
+    sparsity_multiplier: float = 20
+    sparsity_step: float = 1.0
 
 
 @dataclass

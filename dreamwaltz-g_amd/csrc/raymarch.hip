@@ -38,19 +38,8 @@ __global__ void k_near_far(const float* __restrict__ rays_o, const float* __rest
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     const Ray r = load_ray(rays_o + 3 * n, rays_d + 3 * n);
-    float near = (aabb[0] - r.ox) * r.rdx, far = (aabb[3] - r.ox) * r.rdx;
-    if (near > far) { float c = near; near = far; far = c; }
-    float ny = (aabb[1] - r.oy) * r.rdy, fy = (aabb[4] - r.oy) * r.rdy;
-    if (ny > fy) { float c = ny; ny = fy; fy = c; }
-    if (near > fy || ny > far) { nears[n] = fars[n] = FLT_MAX; return; }
-    if (ny > near) near = ny;
-    if (fy < far) far = fy;
-    float nz = (aabb[2] - r.oz) * r.rdz, fz = (aabb[5] - r.oz) * r.rdz;
-    if (nz > fz) { float c = nz; nz = fz; fz = c; }
-    if (near > fz || nz > far) { nears[n] = fars[n] = FLT_MAX; return; }
-    if (nz > near) near = nz;
-    if (fz < far) far = fz;
-    if (near < min_near) near = min_near;
+    float near, far;
+    near_far_ray(r, aabb, min_near, near, far);
     nears[n] = near;
     fars[n] = far;
 }

@@ -59,6 +59,27 @@ __device__ __forceinline__ Ray load_ray(const float* o, const float* d) {
     return r;
 }
 
+// The slab test of near_far_from_aabb (raymarching.cu:92-138) for one ray: near clamped to min_near, both FLT_MAX on a miss.  One copy
+// for raymarch.hip's k_near_far and nerf_view.hip's ray kernel, which computes the interval of the ray it has just stored.
+__device__ __forceinline__ void near_far_ray(const Ray& r, const float* __restrict__ aabb, float min_near, float& near_out, float& far_out) {
+#pragma clang fp contract(off)
+    float near = (aabb[0] - r.ox) * r.rdx, far = (aabb[3] - r.ox) * r.rdx;
+    if (near > far) { float c = near; near = far; far = c; }
+    float ny = (aabb[1] - r.oy) * r.rdy, fy = (aabb[4] - r.oy) * r.rdy;
+    if (ny > fy) { float c = ny; ny = fy; fy = c; }
+    if (near > fy || ny > far) { near_out = far_out = 3.402823466e+38f; return; }
+    if (ny > near) near = ny;
+    if (fy < far) far = fy;
+    float nz = (aabb[2] - r.oz) * r.rdz, fz = (aabb[5] - r.oz) * r.rdz;
+    if (nz > fz) { float c = nz; nz = fz; fz = c; }
+    if (near > fz || nz > far) { near_out = far_out = 3.402823466e+38f; return; }
+    if (nz > near) near = nz;
+    if (fz < far) far = fz;
+    if (near < min_near) near = min_near;
+    near_out = near;
+    far_out = far;
+}
+
 __device__ __forceinline__ float start_t(const MarchP& p, float t0, float noise) {
 #pragma clang fp contract(off)
     return t0 + clampf_(t0 * p.dt_gamma, p.dt_min, p.dt_max) * noise;

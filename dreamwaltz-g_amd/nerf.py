@@ -263,7 +263,7 @@ def bind_nerf_network(ref, shaded_render=False, train_render=False):
     train_render: the installed run_cuda also takes the training view with shading 'albedo' (nerf_render.render_rays_train, B18: the
     backward runs over the samples the composite used); off, training calls stay on the original method.  train_render='shaded': also
     the training views with shading 'normal', 'textureless' and 'lambertian' (B19, nerf_render.covered_train_call); with True they stay
-    on the original method."""
+    on the original method.  render() itself is bound by bind_nerf_view (B20), on request."""
     reason = unbound_reason(ref)
     if reason is not None:
         ref._dwg_nerf_unbound = reason
@@ -390,9 +390,39 @@ def _bind_run_cuda(ref):
     ref.run_cuda = run_cuda
 
 
+def bind_nerf_view(ref):
+    """Opt-in, on a network bind_nerf_network has bound (boundary B20): ref.render becomes nerf_view.render_view for the calls
+    nerf_view.covered_view takes -- rays, run_cuda's native branches and the background mix with the planar image, one launch each
+    around the render.  dmtet, a network without cuda_ray, staged, several cameras, a camera that is not fp32 on the device, a 'nerf'
+    background and the run_cuda calls the native renders do not take (a training view needs train_render) go to the original render,
+    decided before anything is drawn.  Returns None when bound, else the reason.  unbind_nerf_network removes it."""
+    if not getattr(ref, "_dwg_nerf_bound", False):
+        return "the network is not bound (bind_nerf_network first)"
+    if not hasattr(type(ref), "render"):
+        return "%s has no render method" % type(ref).__name__
+    _bind_render(ref)
+    return None
+
+
+def _bind_render(ref):
+    if "render" in ref.__dict__:
+        return
+    from . import nerf_view
+    orig_render = ref.render
+
+    def render(data, shading='albedo', bg_mode=None, staged=False, **kwargs):
+        if set(kwargs) - {"light_d", "ambient_ratio", "dt_gamma", "max_steps", "T_thresh"} or not nerf_view.covered_view(
+                ref, data, shading, bg_mode, staged, kwargs.get("light_d"), kwargs.get("ambient_ratio", 1.0)):
+            return orig_render(data, shading=shading, bg_mode=bg_mode, staged=staged, **kwargs)
+        return nerf_view.render_view(ref, data, shading=shading, bg_mode=bg_mode, **kwargs)
+
+    render.__wrapped__ = orig_render
+    ref.render = render
+
+
 def unbind_nerf_network(ref):
     """Undo bind_nerf_network (the instance attributes go; the class methods show through again)."""
-    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "run_cuda", "_dwg_occupancy", "_dwg_shaded_render",
+    for name in ("common_forward", "local_geometry_forward", "update_extra_state", "run_cuda", "render", "_dwg_occupancy", "_dwg_shaded_render",
                  "_dwg_train_render", "_dwg_train_shaded"):
         if name in ref.__dict__:
             del ref.__dict__[name]

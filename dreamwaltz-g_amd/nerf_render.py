@@ -490,10 +490,19 @@ def run_cuda(ref, orig, rays_o, rays_d, light_d=None, ambient_ratio=1.0, shading
     prefix = rays_o.shape[:-1]
     rays_o = rays_o.contiguous().view(-1, 3)
     rays_d = rays_d.contiguous().view(-1, 3)
-    device = rays_o.device
 
     # pre-calculate near far
     nears, fars = ref.raymarching.near_far_from_aabb(rays_o, rays_d, ref.aabb_train if train else ref.aabb_infer)
+    return run_cuda_native(ref, train, prefix, rays_o, rays_d, nears, fars, light_d, ambient_ratio, shading, perturb, dt_gamma, max_steps,
+                           T_thresh)
+
+
+def run_cuda_native(ref, train, prefix, rays_o, rays_d, nears, fars, light_d, ambient_ratio, shading, perturb, dt_gamma, max_steps, T_thresh,
+                    noises=None):
+    """run_cuda's native branches behind near_far_from_aabb: rays_o / rays_d [N, 3] and nears / fars [N] as that statement leaves them
+    (nerf_view.render_view gets all four from one launch).  train: the training render (covered_train_call held), else the evaluation
+    render (covered_call held).  noises [N]: the training march's perturbation instead of its torch.rand(N) draw."""
+    device = rays_o.device
 
     # random sample light_d if not provided
     if light_d is None:
@@ -513,7 +522,7 @@ def run_cuda(ref, orig, rays_o, rays_d, light_d=None, ambient_ratio=1.0, shading
         weights_sum, depth, image, weights, sigmas = render_rays_train(
             rays_o, rays_d, nears.float().contiguous(), fars.float().contiguous(), *field, density_activation=ref.opt.density_activation,
             density_prior=ref.density_prior_type, albedo_sigmoid=not latent, perturb=perturb, dt_gamma=dt_gamma, max_steps=max_steps,
-            T_thresh=T_thresh, counter=counter, return_weights=True, return_sigmas=True,
+            T_thresh=T_thresh, counter=counter, return_weights=True, return_sigmas=True, noises=noises,
             **({} if shading == 'albedo' else dict(shading=shading, light_d=light_d.contiguous(), ambient_ratio=ambient_ratio)))
         results['weights'] = weights
     else:

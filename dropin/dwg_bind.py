@@ -80,6 +80,9 @@ Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's fie
                                  = shaded             and its shaded training views (B19: shading 'normal', 'textureless', 'lambertian', as the
                                                      normal-adapted guidance renders them); unset or any other value: training calls of run_cuda
                                                      stay on the reference's statements
+             DWG_BIND_NERF_VIEW = 1                   also bind the NeRF network's render() (B20, nerf.bind_nerf_view: rays, the background
+                                                     mix and the planar image in one launch each); unset or any other value: render() is the
+                                                     reference's
              DWG_BIND_INIT = 0                        leave the avatar constructor's geometry (B11) on the reference path (igl + pytorch3d)
              DWG_BIND_POINTCLOUD = 0                  leave the NeRF-to-Gaussian point-cloud export (B12) on the reference path
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
@@ -242,6 +245,11 @@ def bind_nerf(ref):
         reason = bind_nerf_network(ref, shaded_render=True)
     if reason is not None:
         print("[dwg_bind] NeRF field left on the reference path: %s" % reason, file=sys.stderr)
+    elif os.environ.get("DWG_BIND_NERF_VIEW", "0") == "1":
+        from dreamwaltz_g_amd.nerf import bind_nerf_view
+        reason = bind_nerf_view(ref)
+        if reason is not None:
+            print("[dwg_bind] NeRF render() left on the reference path: %s" % reason, file=sys.stderr)
     return ref
 
 
