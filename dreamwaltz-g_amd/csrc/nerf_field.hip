@@ -388,47 +388,32 @@ struct RenderP {
 };
 
 struct ShadeP {                             // the shaded render (boundary B15): forward() of nerf_model.py:86-103 per sample
-    uint32_t shading;                       // 1 normal, 2 textureless, 3 lambertian
-    const float* light_d;                   // [3]; read for 2 and 3
+    uint32_t shading;                       // shade_math.h: DWG_SHADE_NORMAL, _TEXTURELESS, _LAMBERTIAN
+    const float* light_d;                   // [3]; read for the last two
     float ratio, one_minus_ratio;           // ambient_ratio and the Python scalar 1 - ambient_ratio as torch hands it to the kernel
     float eps, bound;                       // normal()'s epsilon; the clamp of the shifted points
 };
 
-// The statements of k_composite_rays (raymarch.hip) for one sample, in their order and without FP contraction, as that file compiles
-// them.  Returns true when the transmittance before the sample was below T_thresh (the sample is composited all the same).
-template <int NC>
-__device__ __forceinline__ bool composite_sample(float sigma, const float (&rgb)[NC], float t, float dt, float T_thresh, bool binarize,
-                                                 float& ws, float& d, float (&col)[NC]) {
-#pragma clang fp contract(off)
-    const float real_alpha = 1.f - expf(-sigma * dt);
-    const float alpha = binarize ? (real_alpha > 0.5f ? 1.f : 0.f) : real_alpha;
-    const float T = 1.f - ws;
-    const float w = alpha * T;
-    ws = ws + w;
-    d = d + w * t;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) col[k] = col[k] + w * rgb[k];
-    return T < T_thresh;
-}
-
-// The colour of a sample from its density gradient g (fd_normal.h) and albedo: forward()'s statements for shading 'normal',
-// 'textureless' and 'lambertian', without FP contraction.  l = -light_d.  (shade_math.h's shade_color holds the same statements for the
-// training kernels and the host build; this copy stays as the inference kernels were compiled with it.)
+// The colour of a sample from its density gradient g (shade_math.h: fd_normalize) and albedo: forward()'s statements for shading
+// 'normal', 'textureless' and 'lambertian', without FP contraction.  l = -light_d.  shade_math.h's shade_color holds the same three
+// statements for the training kernels and the host build.  Calling it here with the constant NC gives the same bits, but the compiler
+// then schedules k_nf_render_shaded differently and the f32 render measured 2 - 5 % slower on an MI355X; with this copy the kernel's
+// instructions are the ones it had.
 template <int NC>
 __device__ __forceinline__ void shade_sample(const ShadeP& sh, float lx, float ly, float lz, float g0, float g1, float g2, const float (&alb)[NC],
                                              float (&rgb)[NC]) {
 #pragma clang fp contract(off)
-    float n0, n1, n2;
-    fd_normalize(g0, g1, g2, n0, n1, n2);
+    float n[3];
+    fd_normalize(g0, g1, g2, n);
 #pragma unroll
     for (int k = 0; k < NC; ++k) rgb[k] = 0.f;
-    if (sh.shading == 1u) {
-        rgb[0] = (n0 + 1.f) / 2.f; rgb[1] = (n1 + 1.f) / 2.f; rgb[2] = (n2 + 1.f) / 2.f;
+    if (sh.shading == DWG_SHADE_NORMAL) {
+        rgb[0] = (n[0] + 1.f) / 2.f; rgb[1] = (n[1] + 1.f) / 2.f; rgb[2] = (n[2] + 1.f) / 2.f;
         return;
     }
-    const float dot = (n0 * lx + n1 * ly) + n2 * lz;
+    const float dot = (n[0] * lx + n[1] * ly) + n[2] * lz;
     const float lam = sh.ratio + sh.one_minus_ratio * (dot < 0.f ? 0.f : dot);      // clamp(min=0): NaN stays NaN
-    if (sh.shading == 2u) { rgb[0] = lam; rgb[1] = lam; rgb[2] = lam; }
+    if (sh.shading == DWG_SHADE_TEXTURELESS) { rgb[0] = lam; rgb[1] = lam; rgb[2] = lam; }
     else {
 #pragma unroll
         for (int k = 0; k < NC; ++k) rgb[k] = alb[k] * lam;
@@ -442,7 +427,7 @@ __device__ __forceinline__ void shade_sample(const ShadeP& sh, float lx, float l
 //
 // SHADED (k_nf_render_shaded): field_tile runs seven times on every 64 pending samples, through XStagedFd: the samples, then their six
 // shifts.  The owner keeps the sample's density and albedo from pass 0, one density of each +- pair and the three components of the
-// gradient in named registers, and shades before it composites.  NC is the width of the image: with four channels the colour of
+// gradient in named registers, and shades (shade_sample) before it composites (raymarch_common.h: composite_sample).  NC is the width of the image: with four channels the colour of
 // 'normal' and 'textureless' is the reference's zero pad in the fourth.
 template <typename T, int NC, bool SHADED>
 __device__ __forceinline__ void nf_render(const NfP& p, const MarchP& m, const RenderP& q, const ShadeP& sh, unsigned char* smem) {
@@ -458,7 +443,7 @@ __device__ __forceinline__ void nf_render(const NfP& p, const MarchP& m, const R
     const bool binarize = q.binarize != 0;
     float lx = 0.f, ly = 0.f, lz = 0.f;                                         // -l
     if constexpr (SHADED) {
-        if (sh.shading >= 2u) { lx = -sh.light_d[0]; ly = -sh.light_d[1]; lz = -sh.light_d[2]; }
+        if (sh.shading >= DWG_SHADE_TEXTURELESS) { lx = -sh.light_d[0]; ly = -sh.light_d[1]; lz = -sh.light_d[2]; }
     }
     Ray ray = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float t = 0.f, far = 0.f, ws = 0.f, d = 0.f, col[NC];
@@ -523,7 +508,7 @@ __device__ __forceinline__ void nf_render(const NfP& p, const MarchP& m, const R
                         const float sg = nf_sigma(p, (float)o[0], sx + 3 * r, es);     // sx holds the shifted point: the prior is taken there
                         if (pass == 0u) {
                             sigma = sg;
-                            if (sh.shading == 3u) {
+                            if (sh.shading == DWG_SHADE_LAMBERTIAN) {
 #pragma unroll
                                 for (int k = 0; k < NC; ++k) {
                                     float v = (float)o[1 + k];
@@ -1109,8 +1094,9 @@ int dwg_nerf_render_shaded(const dwg_nerf_field_desc* desc, const float* rays_o,
     size_t lds = 0;
     int rc = render_args(desc, p, lds, bound, max_steps, C, H);
     if (rc) return rc;
-    if (shading < 1u || shading > 3u || (shading >= 2u && !light_d) || !(epsilon > 0.f)) return DWG_E_ARG;
-    if (shading == 3u && desc->out_dim == 5) return DWG_E_ARG;      // albedo [., 4] * lambertian plus the zero pad: five channels into four
+    if (shading < DWG_SHADE_NORMAL || shading > DWG_SHADE_LAMBERTIAN || (shading >= DWG_SHADE_TEXTURELESS && !light_d) || !(epsilon > 0.f))
+        return DWG_E_ARG;
+    if (shading == DWG_SHADE_LAMBERTIAN && desc->out_dim == 5) return DWG_E_ARG;      // albedo [., 4] * lambertian plus the zero pad: five channels into four
     if (N == 0) return DWG_OK;
     if (!rays_o || !rays_d || !nears || !fars || !bitfield || !weights_sum || !depth || !image) return DWG_E_ARG;
     const MarchP m = make_march(bitfield, bound, contract, dt_gamma, max_steps, C, H);

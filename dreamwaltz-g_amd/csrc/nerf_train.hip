@@ -7,13 +7,15 @@
 //   - scan_counts (scan_common.h, the deterministic three-launch exclusive scan that raymarch.hip's training march uses too) over
 //     live[], written as (offset, live) pairs -- the `rays` layout the composite backward reads.
 //   - k_nt_gather: one wave per ray (kRaysPerWave consecutive rays per wave, as the composite) walks the ray's live rows and copies the
-//     words of every per-sample array from the ray's range in the full buffers to its range in the live ones.  Consecutive lanes take
-//     consecutive words of a contiguous range: coalesced on both sides.
+//     elements of every per-sample array in its table of slots (GatherSlot: source, destination, elements per row, element size) from
+//     the ray's range in the full buffers to its range in the live ones.  Consecutive lanes take consecutive elements of a contiguous
+//     range: coalesced on both sides.  dwg_nerf_train_gather_live fills up to four slots, dwg_nerf_train_gather_live_rows one.
 // Integer adds and bit-for-bit copies only: no float arithmetic, no atomics.
 //
-// The shaded training render (boundary B19) adds k_nt_gather_rows (the same copy for one more per-sample array, the six shifted
-// densities) and the two streaming kernels over shade_math.h, one sample per thread: k_nt_shade_fwd (six densities, albedo -> colour) and
-// k_nt_shade_bwd (d colour -> d of the six densities, d albedo).  Per-sample arithmetic only: nothing is summed across samples.
+// The shaded training render (boundary B19) gathers one more per-sample array through the rows entry (the six shifted densities) and
+// adds the two streaming kernels over shade_math.h, one sample per thread: k_nt_shade_fwd (six densities, albedo -> colour) and
+// k_nt_shade_bwd (d colour -> d of the six densities, d albedo), which load a sample through one helper and launch through one
+// function.  Per-sample arithmetic only: nothing is summed across samples.
 #include "dwg_common.h"
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_nerf_train.h"
@@ -49,12 +51,15 @@ __device__ __forceinline__ void copy_rows(const T* __restrict__ src, T* __restri
     for (size_t i = (size_t)lane; i < n; i += 64) d[i] = s[i];
 }
 
+// One per-sample array of the gather: rows of `w` elements of `esz` bytes -- 4, or 2 where a row may start on a half-word.
+struct GatherSlot {
+    const void* src; void* dst;
+    uint32_t w, esz;
+};
+constexpr uint32_t kGatherSlots = 4;
 struct GatherP {
-    const uint32_t* xyzs; uint32_t* xyzs_live;
-    const uint32_t* ts; uint32_t* ts_live;
-    const uint32_t* sigmas; uint32_t* sigmas_live;
-    const void* rgbs; void* rgbs_live;
-    uint32_t channels, rgbs_f16;
+    GatherSlot s[kGatherSlots];
+    uint32_t n;                             // slots filled
 };
 
 __global__ __launch_bounds__(256) void k_nt_gather(GatherP p, const int32_t* __restrict__ rays, const int32_t* __restrict__ rays_live, uint32_t N,
@@ -68,61 +73,60 @@ __global__ __launch_bounds__(256) void k_nt_gather(GatherP p, const int32_t* __r
         const int2 dst = *reinterpret_cast<const int2*>(rays_live + 2 * (size_t)n);
         const uint32_t so = (uint32_t)src.x, sc = (uint32_t)src.y, dof = (uint32_t)dst.x, cnt = (uint32_t)dst.y;
         if (cnt == 0 || cnt > sc || so > M || sc > M - so || dof > M_live || cnt > M_live - dof) continue;
-        if (p.xyzs) copy_rows<uint32_t>(p.xyzs, p.xyzs_live, so, dof, cnt, 3, lane);
-        if (p.ts) copy_rows<uint32_t>(p.ts, p.ts_live, so, dof, cnt, 2, lane);
-        if (p.sigmas) copy_rows<uint32_t>(p.sigmas, p.sigmas_live, so, dof, cnt, 1, lane);
-        if (p.rgbs) {
-            if (p.rgbs_f16 && p.channels == 4)                  // 8-byte rows: whole words, as the fp32 arrays
-                copy_rows<uint32_t>((const uint32_t*)p.rgbs, (uint32_t*)p.rgbs_live, so, dof, cnt, 2, lane);
-            else if (p.rgbs_f16)                                // 6-byte rows start on any half-word
-                copy_rows<uint16_t>((const uint16_t*)p.rgbs, (uint16_t*)p.rgbs_live, so, dof, cnt, 3, lane);
-            else
-                copy_rows<uint32_t>((const uint32_t*)p.rgbs, (uint32_t*)p.rgbs_live, so, dof, cnt, p.channels, lane);
+#pragma unroll
+        for (uint32_t j = 0; j < kGatherSlots; ++j) {
+            if (j >= p.n) break;
+            const GatherSlot& g = p.s[j];
+            if (g.esz == 2u) copy_rows<uint16_t>((const uint16_t*)g.src, (uint16_t*)g.dst, so, dof, cnt, g.w, lane);
+            else copy_rows<uint32_t>((const uint32_t*)g.src, (uint32_t*)g.dst, so, dof, cnt, g.w, lane);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_nt_gather_rows(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t w,
-                                                        const int32_t* __restrict__ rays, const int32_t* __restrict__ rays_live, uint32_t N, uint32_t M,
-                                                        uint32_t M_live) {
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = dwg_lane();
-    for (uint32_t r = 0; r < kRaysPerWave; ++r) {
-        const uint32_t n = wave * kRaysPerWave + r;
-        if (n >= N) return;
-        const int2 s = *reinterpret_cast<const int2*>(rays + 2 * (size_t)n);
-        const int2 d = *reinterpret_cast<const int2*>(rays_live + 2 * (size_t)n);
-        const uint32_t so = (uint32_t)s.x, sc = (uint32_t)s.y, dof = (uint32_t)d.x, cnt = (uint32_t)d.y;
-        if (cnt == 0 || cnt > sc || so > M || sc > M - so || dof > M_live || cnt > M_live - dof) continue;
-        copy_rows<uint32_t>(src, dst, so, dof, cnt, w, lane);
-    }
+// What the two gather entry points share: the checks on the ray tables and the slots, and the launch.
+int gather(const GatherP& p, const int32_t* rays, const int32_t* rays_live, uint32_t N, uint32_t M, uint32_t M_live, hipStream_t stream) {
+    if (M_live > M) return DWG_E_ARG;
+    if (N == 0 || M == 0 || M_live == 0) return DWG_OK;
+    if (!rays || !rays_live || ((uintptr_t)rays & 7) || ((uintptr_t)rays_live & 7)) return DWG_E_ARG;
+    for (uint32_t j = 0; j < p.n; ++j)
+        if (!p.s[j].src || !p.s[j].dst || (((uintptr_t)p.s[j].src | (uintptr_t)p.s[j].dst) & (p.s[j].esz - 1))) return DWG_E_ARG;
+    if (p.n == 0) return DWG_OK;
+    const uint32_t waves = (N + kRaysPerWave - 1) / kRaysPerWave;
+    DWG_LAUNCH("nt_gather", k_nt_gather, dim3((waves + 3) / 4), dim3(256), 0, stream, p, rays, rays_live, N, M, M_live);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
 }
 
 struct ShadeTrainP {
-    uint32_t shading;                       // shade_math.h: 1 normal, 2 textureless, 3 lambertian
-    const float* light_d;                   // [3] on the device; read for 2 and 3
+    uint32_t shading;                       // shade_math.h: DWG_SHADE_NORMAL, _TEXTURELESS, _LAMBERTIAN
+    const float* light_d;                   // [3] on the device; read for the last two
     float ratio, one_minus_ratio, eps;
     uint32_t M, ch;
 };
 
-// T: the albedo's type (read by 'lambertian' only, which has three channels)
+// What both shade kernels read of sample i: l = -light_d (the lambert shadings), the six densities, the albedo ('lambertian' only, which
+// has three channels).  T: the albedo's type.
+template <typename T>
+__device__ __forceinline__ void shade_load(const ShadeTrainP& p, const float* __restrict__ sigma_fd, const T* __restrict__ albedo, uint32_t i,
+                                           float (&l)[3], float (&s)[6], float (&alb)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) l[k] = p.shading >= DWG_SHADE_TEXTURELESS ? -p.light_d[k] : 0.f;
+    const float2* sp = reinterpret_cast<const float2*>(sigma_fd) + 3 * (size_t)i;
+    const float2 a = sp[0], b = sp[1], c = sp[2];
+    s[0] = a.x; s[1] = a.y; s[2] = b.x; s[3] = b.y; s[4] = c.x; s[5] = c.y;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) alb[k] = p.shading == DWG_SHADE_LAMBERTIAN ? (float)albedo[3 * (size_t)i + k] : 0.f;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_nt_shade_fwd(ShadeTrainP p, const float* __restrict__ sigma_fd, const T* __restrict__ albedo,
                                                       float* __restrict__ rgbs) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= p.M) return;
-    float lx = 0.f, ly = 0.f, lz = 0.f;                                             // -l
-    if (p.shading >= DWG_SHADE_TEXTURELESS) { lx = -p.light_d[0]; ly = -p.light_d[1]; lz = -p.light_d[2]; }
-    const float2* sp = reinterpret_cast<const float2*>(sigma_fd) + 3 * (size_t)i;
-    const float2 a = sp[0], b = sp[1], c = sp[2];
-    const float s[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
-    float n[3], alb[3] = {0.f, 0.f, 0.f}, rgb[3];
+    float l[3], s[6], alb[3], n[3], rgb[3];
+    shade_load(p, sigma_fd, albedo, i, l, s, alb);
     shade_normal(s, p.eps, n);
-    if (p.shading == DWG_SHADE_LAMBERTIAN) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) alb[k] = (float)albedo[3 * (size_t)i + k];
-    }
-    shade_color(p.shading, p.ratio, p.one_minus_ratio, lx, ly, lz, n[0], n[1], n[2], alb, 3, rgb);
+    shade_color(p.shading, p.ratio, p.one_minus_ratio, l[0], l[1], l[2], n[0], n[1], n[2], alb, 3, rgb);
     float* o = rgbs + (size_t)p.ch * i;
     o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2];
     if (p.ch == 4u) o[3] = 0.f;                                                     // the reference's zero pad of a latent colour
@@ -133,19 +137,11 @@ __global__ __launch_bounds__(256) void k_nt_shade_bwd(ShadeTrainP p, const float
                                                       const float* __restrict__ grad_rgbs, float* __restrict__ dsigma_fd, T* __restrict__ dalbedo) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= p.M) return;
-    float lx = 0.f, ly = 0.f, lz = 0.f;
-    if (p.shading >= DWG_SHADE_TEXTURELESS) { lx = -p.light_d[0]; ly = -p.light_d[1]; lz = -p.light_d[2]; }
-    const float2* sp = reinterpret_cast<const float2*>(sigma_fd) + 3 * (size_t)i;
-    const float2 a = sp[0], b = sp[1], c = sp[2];
-    const float s[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
+    float l[3], s[6], alb[3], ds[6], da[3] = {0.f, 0.f, 0.f};
+    shade_load(p, sigma_fd, albedo, i, l, s, alb);
     const float* gp = grad_rgbs + (size_t)p.ch * i;
     const float g[3] = {gp[0], gp[1], gp[2]};                                       // a fourth channel is the pad's: dropped
-    float alb[3] = {0.f, 0.f, 0.f}, ds[6], da[3] = {0.f, 0.f, 0.f};
-    if (p.shading == DWG_SHADE_LAMBERTIAN) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) alb[k] = (float)albedo[3 * (size_t)i + k];
-    }
-    shade_backward(p.shading, p.ratio, p.one_minus_ratio, lx, ly, lz, p.eps, s, alb, g, ds, da);
+    shade_backward(p.shading, p.ratio, p.one_minus_ratio, l[0], l[1], l[2], p.eps, s, alb, g, ds, da);
     float2* dp = reinterpret_cast<float2*>(dsigma_fd) + 3 * (size_t)i;
     dp[0] = make_float2(ds[0], ds[1]); dp[1] = make_float2(ds[2], ds[3]); dp[2] = make_float2(ds[4], ds[5]);
     if (dalbedo) {
@@ -154,14 +150,29 @@ __global__ __launch_bounds__(256) void k_nt_shade_bwd(ShadeTrainP p, const float
     }
 }
 
-// the checks the two shade entry points share
-int shade_args(uint32_t shading, const float* sigma_fd, const void* albedo, const float* light_d, float ratio, float eps, uint32_t ch,
-               uint32_t albedo_f16) {
+// What the two shade entry points share: the checks (with M == 0 of the scalars only), the parameter block and the launch by the
+// albedo's type.  grad_rgbs == NULL: the forward into out [M, ch]; else the backward into out [M, 6] and dalbedo.
+int shade(uint32_t shading, const float* sigma_fd, const void* albedo, uint32_t albedo_f16, const float* light_d, float ratio, float eps, uint32_t M,
+          uint32_t ch, const float* grad_rgbs, float* out, void* dalbedo, hipStream_t stream) {
     if (shading < DWG_SHADE_NORMAL || shading > DWG_SHADE_LAMBERTIAN || (ch != 3 && ch != 4) || albedo_f16 > 1) return DWG_E_ARG;
     if (!(eps > 0.f) || ratio != ratio) return DWG_E_ARG;
+    if (shading == DWG_SHADE_LAMBERTIAN && ch != 3) return DWG_E_ARG;               // four albedo channels plus the pad: five into four
+    if (M == 0) return DWG_OK;
     if (shading >= DWG_SHADE_TEXTURELESS && !light_d) return DWG_E_ARG;
-    if (shading == DWG_SHADE_LAMBERTIAN && (ch != 3 || !albedo)) return DWG_E_ARG;   // four albedo channels plus the pad: five into four
+    if (shading == DWG_SHADE_LAMBERTIAN && !albedo) return DWG_E_ARG;
     if (!sigma_fd || ((uintptr_t)sigma_fd & 7)) return DWG_E_ARG;
+    const ShadeTrainP p{shading, light_d, ratio, (float)(1.0 - (double)ratio), eps, M, ch};
+    const dim3 grid((M + 255u) / 256u);
+    if (!grad_rgbs) {
+        if (albedo_f16) DWG_LAUNCH("nt_shade_fwd", k_nt_shade_fwd<_Float16>, grid, dim3(256), 0, stream, p, sigma_fd, (const _Float16*)albedo, out);
+        else DWG_LAUNCH("nt_shade_fwd", k_nt_shade_fwd<float>, grid, dim3(256), 0, stream, p, sigma_fd, (const float*)albedo, out);
+    } else if (albedo_f16) {
+        DWG_LAUNCH("nt_shade_bwd", k_nt_shade_bwd<_Float16>, grid, dim3(256), 0, stream, p, sigma_fd, (const _Float16*)albedo, grad_rgbs, out,
+                   (_Float16*)dalbedo);
+    } else {
+        DWG_LAUNCH("nt_shade_bwd", k_nt_shade_bwd<float>, grid, dim3(256), 0, stream, p, sigma_fd, (const float*)albedo, grad_rgbs, out, (float*)dalbedo);
+    }
+    DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }
 
@@ -189,68 +200,39 @@ int dwg_nerf_train_gather_live(const int32_t* rays, const int32_t* rays_live, ui
     if (channels != 3 && channels != 4) return DWG_E_ARG;
     if (rgbs_f16 > 1) return DWG_E_ARG;
     if (!xyzs != !xyzs_live || !ts != !ts_live || !sigmas != !sigmas_live || !rgbs != !rgbs_live) return DWG_E_ARG;
-    if (M_live > M) return DWG_E_ARG;
-    if (N == 0 || M == 0 || M_live == 0) return DWG_OK;
-    if (!rays || !rays_live || ((uintptr_t)rays & 7) || ((uintptr_t)rays_live & 7)) return DWG_E_ARG;
-    if (((uintptr_t)xyzs | (uintptr_t)xyzs_live | (uintptr_t)ts | (uintptr_t)ts_live | (uintptr_t)sigmas | (uintptr_t)sigmas_live) & 3)
-        return DWG_E_ARG;
-    if (((uintptr_t)rgbs | (uintptr_t)rgbs_live) & (rgbs_f16 && channels == 3 ? 1 : 3)) return DWG_E_ARG;
-    if (!xyzs && !ts && !sigmas && !rgbs) return DWG_OK;
-    GatherP p;
-    p.xyzs = (const uint32_t*)xyzs; p.xyzs_live = (uint32_t*)xyzs_live;
-    p.ts = (const uint32_t*)ts; p.ts_live = (uint32_t*)ts_live;
-    p.sigmas = (const uint32_t*)sigmas; p.sigmas_live = (uint32_t*)sigmas_live;
-    p.rgbs = rgbs; p.rgbs_live = rgbs_live;
-    p.channels = channels; p.rgbs_f16 = rgbs_f16;
-    const uint32_t waves = (N + kRaysPerWave - 1) / kRaysPerWave;
-    DWG_LAUNCH("nt_gather", k_nt_gather, dim3((waves + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, rays, rays_live, N, M, M_live);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
+    // f16 colours: 8-byte latent rows are two words; 6-byte rgb rows start on any half-word
+    const GatherSlot slots[kGatherSlots] = {{xyzs, xyzs_live, 3, 4}, {ts, ts_live, 2, 4}, {sigmas, sigmas_live, 1, 4},
+                                            {rgbs, rgbs_live, rgbs_f16 ? (channels == 4 ? 2u : 3u) : channels, rgbs_f16 && channels == 3 ? 2u : 4u}};
+    GatherP p{};
+    for (const GatherSlot& s : slots)
+        if (s.src) p.s[p.n++] = s;
+    return gather(p, rays, rays_live, N, M, M_live, (hipStream_t)stream);
 }
 
 int dwg_nerf_train_gather_live_rows(const int32_t* rays, const int32_t* rays_live, uint32_t N, uint32_t M, uint32_t M_live, const float* src,
                                     float* dst, uint32_t floats_per_row, dwg_stream_t stream) {
     if (floats_per_row == 0 || floats_per_row > 64) return DWG_E_ARG;
-    if (M_live > M) return DWG_E_ARG;
-    if (N == 0 || M == 0 || M_live == 0) return DWG_OK;
-    if (!rays || !rays_live || ((uintptr_t)rays & 7) || ((uintptr_t)rays_live & 7)) return DWG_E_ARG;
-    if (!src || !dst || (((uintptr_t)src | (uintptr_t)dst) & 3)) return DWG_E_ARG;
-    const uint32_t waves = (N + kRaysPerWave - 1) / kRaysPerWave;
-    DWG_LAUNCH("nt_gather_rows", k_nt_gather_rows, dim3((waves + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)src, (uint32_t*)dst,
-               floats_per_row, rays, rays_live, N, M, M_live);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
+    GatherP p{};
+    p.s[p.n++] = {src, dst, floats_per_row, 4};
+    return gather(p, rays, rays_live, N, M, M_live, (hipStream_t)stream);
 }
 
 int dwg_nerf_train_shade_forward(uint32_t shading, const float* sigma_fd, const void* albedo, uint32_t albedo_f16, const float* light_d,
                                  float ambient_ratio, float epsilon, uint32_t M, uint32_t channels, float* rgbs, dwg_stream_t stream) {
-    if (M == 0) return shade_args(shading, (const float*)8, (const void*)8, (const float*)8, ambient_ratio, epsilon, channels, albedo_f16);
-    int rc = shade_args(shading, sigma_fd, albedo, light_d, ambient_ratio, epsilon, channels, albedo_f16);
-    if (rc) return rc;
-    if (!rgbs || ((uintptr_t)rgbs & 3)) return DWG_E_ARG;
-    const ShadeTrainP p{shading, light_d, ambient_ratio, (float)(1.0 - (double)ambient_ratio), epsilon, M, channels};
-    const dim3 grid((M + 255u) / 256u);
-    if (albedo_f16) DWG_LAUNCH("nt_shade_fwd", k_nt_shade_fwd<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, p, sigma_fd, (const _Float16*)albedo, rgbs);
-    else DWG_LAUNCH("nt_shade_fwd", k_nt_shade_fwd<float>, grid, dim3(256), 0, (hipStream_t)stream, p, sigma_fd, (const float*)albedo, rgbs);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
+    if (M && (!rgbs || ((uintptr_t)rgbs & 3))) return DWG_E_ARG;
+    return shade(shading, sigma_fd, albedo, albedo_f16, light_d, ambient_ratio, epsilon, M, channels, nullptr, rgbs, nullptr, (hipStream_t)stream);
 }
 
 int dwg_nerf_train_shade_backward(uint32_t shading, const float* sigma_fd, const void* albedo, uint32_t albedo_f16, const float* light_d,
                                   float ambient_ratio, float epsilon, uint32_t M, uint32_t channels, const float* grad_rgbs, float* dsigma_fd,
                                   void* dalbedo, dwg_stream_t stream) {
-    if (M == 0) return shade_args(shading, (const float*)8, (const void*)8, (const float*)8, ambient_ratio, epsilon, channels, albedo_f16);
-    int rc = shade_args(shading, sigma_fd, albedo, light_d, ambient_ratio, epsilon, channels, albedo_f16);
-    if (rc) return rc;
-    if (!grad_rgbs || !dsigma_fd || (((uintptr_t)grad_rgbs) & 3) || ((uintptr_t)dsigma_fd & 7)) return DWG_E_ARG;
-    if (shading == DWG_SHADE_LAMBERTIAN && !dalbedo) return DWG_E_ARG;
-    if ((uintptr_t)dalbedo & (albedo_f16 ? 1 : 3)) return DWG_E_ARG;
-    const ShadeTrainP p{shading, light_d, ambient_ratio, (float)(1.0 - (double)ambient_ratio), epsilon, M, channels};
-    const dim3 grid((M + 255u) / 256u);
-    if (albedo_f16) DWG_LAUNCH("nt_shade_bwd", k_nt_shade_bwd<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, p, sigma_fd, (const _Float16*)albedo, grad_rgbs, dsigma_fd, (_Float16*)dalbedo);
-    else DWG_LAUNCH("nt_shade_bwd", k_nt_shade_bwd<float>, grid, dim3(256), 0, (hipStream_t)stream, p, sigma_fd, (const float*)albedo, grad_rgbs, dsigma_fd, (float*)dalbedo);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
+    if (M) {
+        if (!grad_rgbs || !dsigma_fd || (((uintptr_t)grad_rgbs) & 3) || ((uintptr_t)dsigma_fd & 7)) return DWG_E_ARG;
+        if (shading == DWG_SHADE_LAMBERTIAN && !dalbedo) return DWG_E_ARG;
+        if ((uintptr_t)dalbedo & (albedo_f16 ? 1 : 3)) return DWG_E_ARG;
+    }
+    return shade(shading, sigma_fd, albedo, albedo_f16, light_d, ambient_ratio, epsilon, M, channels, grad_rgbs, dsigma_fd, dalbedo,
+                 (hipStream_t)stream);
 }
 
 }  // extern "C"

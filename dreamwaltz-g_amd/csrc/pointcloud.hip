@@ -130,10 +130,8 @@ __global__ __launch_bounds__(256) void k_pc_finish(uint64_t n, uint32_t C, const
         // products rounded one by one and summed in k order
         for (int j = 0; j < 3; j++) colors[3u * i + j] = ((a.x * m[0][j] + a.y * m[1][j]) + a.z * m[2][j]) + a.w * m[3][j];
     }
-    const float g0 = fd_gradient(sig6[i], sig6[n + i], eps), g1 = fd_gradient(sig6[2u * n + i], sig6[3u * n + i], eps);
-    const float g2 = fd_gradient(sig6[4u * n + i], sig6[5u * n + i], eps);
-    float* nrm = normals + 3u * i;
-    fd_normalize(g0, g1, g2, nrm[0], nrm[1], nrm[2]);
+    const float s[6] = {sig6[i], sig6[n + i], sig6[2u * n + i], sig6[3u * n + i], sig6[4u * n + i], sig6[5u * n + i]};
+    shade_normal(s, eps, normals + 3u * i);
 }
 
 __global__ __launch_bounds__(256) void k_pc_outside_boxes(uint64_t n, const float* __restrict__ points, uint32_t nb, const double* __restrict__ boxes,

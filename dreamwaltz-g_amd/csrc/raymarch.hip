@@ -373,16 +373,11 @@ __global__ void k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thre
     while (step < n_step) {
         const size_t i = (size_t)n * n_step + step;
         if (ts[2 * i] == 0.f) break;
-        const float real_alpha = 1.f - expf(-sigmas[i] * ts[2 * i + 1]);
-        const float alpha = binarize ? (real_alpha > 0.5f ? 1.f : 0.f) : real_alpha;
-        const float T = 1.f - ws;
-        const float w = alpha * T;
-        ws = ws + w;
         t = ts[2 * i];
-        d = d + w * t;
+        float rgb[NC];
 #pragma unroll
-        for (int k = 0; k < NC; ++k) col[k] = col[k] + w * rgbs[NC * i + k];
-        if (T < T_thresh) break;
+        for (int k = 0; k < NC; ++k) rgb[k] = rgbs[NC * i + k];
+        if (composite_sample<NC>(sigmas[i], rgb, t, ts[2 * i + 1], T_thresh, binarize != 0, ws, d, col)) break;
         ++step;
     }
     if (step < n_step) rays_alive[n] = -1;

@@ -127,3 +127,21 @@ __device__ __forceinline__ bool march_iter(const MarchP& p, const Ray& r, float&
     } while (t < tt);
     return false;
 }
+
+// One sample of the inference composite (kernel_composite_rays, raymarching.cu:843-926), its statements in their order.  One copy for
+// raymarch.hip's k_composite_rays and the one-launch renders (nerf_field.hip's nf_render).  Returns true when the transmittance before
+// the sample was below T_thresh (the sample is composited all the same).
+template <int NC>
+__device__ __forceinline__ bool composite_sample(float sigma, const float (&rgb)[NC], float t, float dt, float T_thresh, bool binarize,
+                                                 float& ws, float& d, float (&col)[NC]) {
+#pragma clang fp contract(off)
+    const float real_alpha = 1.f - expf(-sigma * dt);
+    const float alpha = binarize ? (real_alpha > 0.5f ? 1.f : 0.f) : real_alpha;
+    const float T = 1.f - ws;
+    const float w = alpha * T;
+    ws = ws + w;
+    d = d + w * t;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) col[k] = col[k] + w * rgb[k];
+    return T < T_thresh;
+}

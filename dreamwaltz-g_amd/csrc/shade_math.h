@@ -1,6 +1,9 @@
 // shade_math.h -- per-sample arithmetic of the shaded NeRF views, written once for the HIP kernels (nerf_field.hip's shaded inference
-// render, nerf_train.hip's training shade kernels, pointcloud.hip through fd_normal.h) and compilable by a C compiler for the host
-// (tests/hostmath/shade_math_host.c checks the hand-derived backward against autograd on the CPU; the product runs it on the device).
+// render, nerf_train.hip's training shade kernels, pointcloud.hip's k_pc_finish; the first and the last through fd_normal.h) and
+// compilable by a C compiler for the host (tests/hostmath/shade_math_host.c checks the hand-derived backward against autograd on the
+// CPU; the product runs it on the device).  The normalisation stands once: fd_unit, which the forward (fd_normalize, shade_normal) and
+// the backward both call.  The three shading statements are shade_color; nerf_field.hip's inference render alone keeps a copy of
+// them (shade_sample: why is written there).
 //
 // Forward: the statements of _NeRFNetwork.normal and forward (core/nerf/nerf_model.py:84-105, 155-168) for one sample, from the six
 // densities at the shifted points:
@@ -42,27 +45,26 @@ DWG_SHADE_HD float fd_gradient(float s_pos, float s_neg, float eps) {
     return (-0.5f * (s_pos - s_neg)) / eps;
 }
 
-// nan_to_num(safe_normalize(g))
-#if defined(__cplusplus)
-DWG_SHADE_HD void fd_normalize(float g0, float g1, float g2, float& n0, float& n1, float& n2) {
+// safe_normalize(g) before its nan_to_num: d = g.g, len = sqrt(clamp(d, min=1e-20)) (torch.clamp(min): NaN stays NaN, and with it all
+// three components), u = g / len.  Returns len; *d is what the backward's clamp selects on.
+DWG_SHADE_HD float fd_unit(float g0, float g1, float g2, float* u, float* d) {
     DWG_SHADE_STRICT
-    const float d = (g0 * g0 + g1 * g1) + g2 * g2;
-    const float len = sqrtf(d < 1e-20f ? 1e-20f : d);           // torch.clamp(min): NaN stays NaN, and with it all three components
-    n0 = fd_nan_to_num(g0 / len);
-    n1 = fd_nan_to_num(g1 / len);
-    n2 = fd_nan_to_num(g2 / len);
+    *d = (g0 * g0 + g1 * g1) + g2 * g2;
+    const float len = sqrtf(*d < 1e-20f ? 1e-20f : *d);
+    u[0] = g0 / len; u[1] = g1 / len; u[2] = g2 / len;
+    return len;
 }
-#endif
 
-// the same for arrays: n[3] from the six densities s (+x, -x, +y, -y, +z, -z)
+// n[3] = nan_to_num(safe_normalize(g))
+DWG_SHADE_HD void fd_normalize(float g0, float g1, float g2, float* n) {
+    float u[3], d;
+    fd_unit(g0, g1, g2, u, &d);
+    n[0] = fd_nan_to_num(u[0]); n[1] = fd_nan_to_num(u[1]); n[2] = fd_nan_to_num(u[2]);
+}
+
+// n[3] from the six densities s (+x, -x, +y, -y, +z, -z)
 DWG_SHADE_HD void shade_normal(const float* s, float eps, float* n) {
-    DWG_SHADE_STRICT
-    const float g0 = fd_gradient(s[0], s[1], eps), g1 = fd_gradient(s[2], s[3], eps), g2 = fd_gradient(s[4], s[5], eps);
-    const float d = (g0 * g0 + g1 * g1) + g2 * g2;
-    const float len = sqrtf(d < 1e-20f ? 1e-20f : d);
-    n[0] = fd_nan_to_num(g0 / len);
-    n[1] = fd_nan_to_num(g1 / len);
-    n[2] = fd_nan_to_num(g2 / len);
+    fd_normalize(fd_gradient(s[0], s[1], eps), fd_gradient(s[2], s[3], eps), fd_gradient(s[4], s[5], eps), n);
 }
 
 // The colour of a sample from its normal and albedo.  l = -light_d (read for 'textureless' and 'lambertian'); one_minus_ratio is the
@@ -95,9 +97,8 @@ DWG_SHADE_HD void shade_backward(uint32_t shading, float ratio, float one_minus_
     DWG_SHADE_STRICT
     // the forward again
     const float g[3] = {fd_gradient(s[0], s[1], eps), fd_gradient(s[2], s[3], eps), fd_gradient(s[4], s[5], eps)};
-    const float d = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-    const float len = sqrtf(d < 1e-20f ? 1e-20f : d);
-    const float u[3] = {g[0] / len, g[1] / len, g[2] / len};
+    float u[3], d;
+    const float len = fd_unit(g[0], g[1], g[2], u, &d);
     float dn[3];
     if (shading == DWG_SHADE_NORMAL) {
         dn[0] = grgb[0] / 2.f; dn[1] = grgb[1] / 2.f; dn[2] = grgb[2] / 2.f;

@@ -43,14 +43,24 @@ def _check(name, t, dtype, numel=None):
         raise RuntimeError("%s has %d elements, expected %d" % (name, t.numel(), numel))
 
 
+def _autocast_dtype():
+    """The CUDA autocast dtype, None without autocast."""
+    if not torch.is_autocast_enabled():
+        return None
+    return torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
+
+
 def autocast_precision():
     """1 (f16) under CUDA autocast to float16, 0 (f32) without autocast; other autocast dtypes are not covered."""
-    if not torch.is_autocast_enabled():
-        return 0
-    dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
-    if dt != torch.float16:
+    dt = _autocast_dtype()
+    if dt not in (None, torch.float16):
         raise RuntimeError("the fused NeRF field covers fp16 autocast only, got %s" % dt)
-    return 1
+    return int(dt is not None)
+
+
+def autocast_covered():
+    """autocast_precision() would not raise: autocast is off or to float16."""
+    return _autocast_dtype() in (None, torch.float16)
 
 
 def _host_offsets(encoder):
@@ -133,16 +143,45 @@ class FieldSpec:
             _check("sigma_net.net[%d].bias" % l, wb[2 * l + 1], torch.float32, n)
 
 
+def field_forward(spec, embeddings, sigma_scale, wb, x):
+    """(sigma [M] fp32, albedo [M, out_dim - 1] in the spec's precision) of dwg_nerf_field_forward at x [M, 3]; the caller has checked."""
+    M = x.shape[0]
+    sigma = torch.empty(M, device=x.device, dtype=torch.float32)
+    albedo = torch.empty(M, spec.out_dim - 1, device=x.device, dtype=torch.float16 if spec.precision else torch.float32)
+    d = spec.desc(embeddings, sigma_scale, wb)
+    _lib.check(_lib.lib().dwg_nerf_field_forward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(sigma), _lib.ptr(albedo), _st(x)),
+               "dwg_nerf_field_forward")
+    return sigma, albedo
+
+
+def field_backward(spec, embeddings, sigma_scale, wb, x, dsigma, dalbedo, g_emb, g_ss, g_wb, fd=None, accumulate=0):
+    """dwg_nerf_field_backward over the M rows of x into the wanted gradient tensors (g_emb, g_ss and each of g_wb: None when not
+    wanted); with fd = (eps, dsigma_fd [M, 6]) dwg_nerf_field_backward_fd, which also takes the six shifted point sets.  The table
+    gradient is added into; the others are overwritten unless accumulate."""
+    g = _lib.NerfFieldGradsC()
+    g.embeddings = None if g_emb is None else g_emb.data_ptr()
+    for l in range(spec.num_layers):
+        g.weight[l] = None if g_wb[2 * l] is None else g_wb[2 * l].data_ptr()
+        g.bias[l] = None if g_wb[2 * l + 1] is None else g_wb[2 * l + 1].data_ptr()
+    g.sigma_scale = None if g_ss is None else g_ss.data_ptr()
+    g.accumulate = accumulate
+    d = spec.desc(embeddings, sigma_scale, wb)
+    L, M = _lib.lib(), x.shape[0]
+    nbytes = int(L.dwg_nerf_field_backward_workspace_bytes(ctypes.byref(d), M))
+    ws = torch.empty(max(nbytes, 1), device=x.device, dtype=torch.uint8)
+    tail = (ctypes.byref(g), _lib.ptr(ws), nbytes, _st(x))
+    if fd is None:
+        _lib.check(L.dwg_nerf_field_backward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(dsigma), _lib.ptr(dalbedo), *tail), "dwg_nerf_field_backward")
+    else:
+        _lib.check(L.dwg_nerf_field_backward_fd(ctypes.byref(d), _lib.ptr(x), M, ctypes.c_float(fd[0]), _lib.ptr(dsigma), _lib.ptr(dalbedo),
+                                                _lib.ptr(fd[1]), *tail), "dwg_nerf_field_backward_fd")
+
+
 class _NerfField(Function):
     @staticmethod
     def forward(ctx, spec, x, embeddings, sigma_scale, *wb):
         spec.check(x, embeddings, sigma_scale, wb)
-        M = x.shape[0]
-        sigma = torch.empty(M, device=x.device, dtype=torch.float32)
-        albedo = torch.empty(M, spec.out_dim - 1, device=x.device, dtype=torch.float16 if spec.precision else torch.float32)
-        d = spec.desc(embeddings, sigma_scale, wb)
-        _lib.check(_lib.lib().dwg_nerf_field_forward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(sigma), _lib.ptr(albedo), _st(x)),
-                   "dwg_nerf_field_forward")
+        sigma, albedo = field_forward(spec, embeddings, sigma_scale, wb, x)
         ctx.spec = spec
         ctx.save_for_backward(x, embeddings, sigma_scale, *wb)
         ctx.albedo_dtype = albedo.dtype
@@ -157,24 +196,12 @@ class _NerfField(Function):
         dsigma = torch.zeros(M, device=x.device, dtype=torch.float32) if dsigma is None else dsigma.float().contiguous()
         dalbedo = (torch.zeros(M, spec.out_dim - 1, device=x.device, dtype=ctx.albedo_dtype) if dalbedo is None
                    else dalbedo.to(ctx.albedo_dtype).contiguous())
-        g = _lib.NerfFieldGradsC()
         g_emb = torch.zeros_like(embeddings) if need[2] else None
         g_ss = torch.empty_like(sigma_scale) if (need[3] and spec.act == ACTIVATIONS['scaling']) else None
         g_wb = [torch.empty_like(t) if need[4 + i] else None for i, t in enumerate(wb)]
         if g_emb is None and g_ss is None and all(t is None for t in g_wb):
             return (None,) * (4 + len(wb))
-        g.embeddings = None if g_emb is None else g_emb.data_ptr()
-        for l in range(spec.num_layers):
-            g.weight[l] = None if g_wb[2 * l] is None else g_wb[2 * l].data_ptr()
-            g.bias[l] = None if g_wb[2 * l + 1] is None else g_wb[2 * l + 1].data_ptr()
-        g.sigma_scale = None if g_ss is None else g_ss.data_ptr()
-        g.accumulate = 0
-        d = spec.desc(embeddings, sigma_scale, wb)
-        L = _lib.lib()
-        nbytes = int(L.dwg_nerf_field_backward_workspace_bytes(ctypes.byref(d), M))
-        ws = torch.empty(max(nbytes, 1), device=x.device, dtype=torch.uint8)
-        _lib.check(L.dwg_nerf_field_backward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(dsigma), _lib.ptr(dalbedo), ctypes.byref(g),
-                                             _lib.ptr(ws), nbytes, _st(x)), "dwg_nerf_field_backward")
+        field_backward(spec, embeddings, sigma_scale, wb, x, dsigma, dalbedo, g_emb, g_ss, g_wb)
         return (None, None, g_emb, g_ss if need[3] else None, *g_wb)
 
 
@@ -249,10 +276,7 @@ def _covered_call(x):
     """The kernels take this call: a CUDA fp32 x that needs no gradient, and no autocast dtype but fp16."""
     if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.requires_grad:
         return False
-    if torch.is_autocast_enabled():
-        dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
-        return dt == torch.float16
-    return True
+    return autocast_covered()
 
 
 def bind_nerf_network(ref, shaded_render=False, train_render=False):
@@ -349,10 +373,7 @@ def _bind_update_extra_state(ref):
             return False
         if not (ref.encoder.embeddings.is_cuda and ref.sigma_scale.is_cuda):
             return False
-        if torch.is_autocast_enabled():
-            dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
-            return dt == torch.float16
-        return True
+        return autocast_covered()
 
     def update_extra_state(decay=0.95, S=None, random_sigmas=False):
         if not _native(S):

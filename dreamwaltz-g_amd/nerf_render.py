@@ -37,20 +37,24 @@ _check = pointcloud._dev_check
 SHADINGS = {'albedo': 0, 'normal': 1, 'textureless': 2, 'lambertian': 3}
 
 
-@torch.no_grad()
-def render_rays(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_size, encoder, sigma_net, sigma_scale, bound, *,
-                density_activation, density_prior, albedo_sigmoid, dt_gamma=0, max_steps=1024, T_thresh=1e-4, binarize=False, contract=False,
-                precision=None, return_counts=False, max_workgroups=0, shading='albedo', light_d=None, ambient_ratio=1.0, normal_epsilon=1e-3):
-    """rays_o / rays_d [N, 3], nears / fars [N] fp32 on the device; density_bitfield [cascade * grid_size^3 / 8] uint8.  Returns
-    (weights_sum [N], depth [N], image [N, out_dim - 1]) fp32, and counts [N] int32 (samples composited per ray) with return_counts.
-    precision: None follows autocast, 0 f32, 1 f16.  max_workgroups: the number of persistent workgroups (0: the default).
-    shading: 'albedo', or 'normal' / 'textureless' / 'lambertian' from the finite-difference normal with step normal_epsilon; light_d
-    [3] fp32 on the device (needed by 'textureless' and 'lambertian', never read on the host) and ambient_ratio as forward() takes them.
-    'lambertian' with four albedo channels is ill-formed in the reference and refused."""
+def _grid_shape(cascade, grid_size):
+    """(C, H) as integers when the renders take an occupancy grid of this shape, else None."""
+    C, H = int(cascade), int(grid_size)
+    if C != cascade or H != grid_size or not (1 <= C <= 8 and 2 <= H <= 1024 and C * H ** 3 < 1 << 32) or H & (H - 1):
+        return None
+    return C, H
+
+
+def _check_render(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_size, max_steps, shading, light_d, ambient_ratio, epsilon,
+                  epsilon_name, *field):
+    """What render_rays and render_rays_train both check of a call, before any launch: the shading's name, the field (`field`:
+    pointcloud.field_spec's arguments), the rays, nears / fars, the occupancy grid, max_steps, the shading's arguments (a given light_d,
+    the epsilon under the caller's name for it, ambient_ratio, latent 'lambertian') and that everything is on rays_o's device.
+    -> (spec, embeddings, sigma_scale [1], [w0, b0, ...] detached, N, C, H)."""
     if shading not in SHADINGS:
         raise RuntimeError("shading must be one of %s, got %r" % (", ".join(sorted(SHADINGS)), shading))
     try:
-        spec, emb, ss, wb = pointcloud.field_spec(encoder, sigma_net, sigma_scale, bound, density_activation, density_prior, albedo_sigmoid, precision)
+        spec, emb, ss, wb = pointcloud.field_spec(*field)
     except ValueError as e:
         raise RuntimeError(str(e)) from None
     _check("rays_o", rays_o, torch.float32, (None, 3))
@@ -58,18 +62,14 @@ def render_rays(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_siz
     _check("rays_d", rays_d, torch.float32, (N, 3))
     _check("nears", nears, torch.float32, (N,))
     _check("fars", fars, torch.float32, (N,))
-    C, H = int(cascade), int(grid_size)
-    if C != cascade or H != grid_size or not (1 <= C <= 8 and 2 <= H <= 1024 and C * H ** 3 < 1 << 32) or H & (H - 1):
+    grid = _grid_shape(cascade, grid_size)
+    if grid is None:
         raise RuntimeError("bad occupancy grid shape: cascade %r, grid_size %r (a power of two: a cell's Morton index must stay below "
                            "grid_size^3)" % (cascade, grid_size))
+    C, H = grid
     _check("density_bitfield", density_bitfield, torch.uint8, (C * H ** 3 // 8,))
     if int(max_steps) != max_steps or not 1 <= max_steps < 1 << 31:
         raise RuntimeError("max_steps must be an integer >= 1, got %r" % (max_steps,))
-    if N >= 1 << 32:
-        raise RuntimeError("render_rays takes fewer than 2^32 rays")
-    if int(max_workgroups) != max_workgroups or not 0 <= max_workgroups < 1 << 31:
-        raise RuntimeError("max_workgroups must be a non-negative integer, got %r" % (max_workgroups,))
-    dev = rays_o.device
     others = []
     if SHADINGS[shading]:
         if light_d is not None:
@@ -80,13 +80,39 @@ def render_rays(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_siz
         if SHADINGS[shading] == 3 and spec.out_dim == 5:
             raise RuntimeError("shading 'lambertian' with four albedo channels (latent mode) is ill-formed in the reference: five channels "
                                "into a four-channel image")
-        if not float(normal_epsilon) > 0:
-            raise RuntimeError("normal_epsilon must be positive, got %r" % (normal_epsilon,))
+        if not float(epsilon) > 0:
+            raise RuntimeError("%s must be positive, got %r" % (epsilon_name, epsilon))
         if float(ambient_ratio) != float(ambient_ratio):
             raise RuntimeError("ambient_ratio is NaN")
-    for name, t in [("rays_d", rays_d), ("nears", nears), ("fars", fars), ("density_bitfield", density_bitfield), ("embeddings", emb)] + others:
+    _same_device(rays_o.device, [("rays_d", rays_d), ("nears", nears), ("fars", fars), ("density_bitfield", density_bitfield),
+                                 ("embeddings", emb)] + others)
+    return spec, emb, ss, wb, N, C, H
+
+
+def _same_device(dev, named):
+    for name, t in named:
         if t.device != dev:
             raise RuntimeError("%s is on %s, rays_o on %s" % (name, t.device, dev))
+
+
+@torch.no_grad()
+def render_rays(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_size, encoder, sigma_net, sigma_scale, bound, *,
+                density_activation, density_prior, albedo_sigmoid, dt_gamma=0, max_steps=1024, T_thresh=1e-4, binarize=False, contract=False,
+                precision=None, return_counts=False, max_workgroups=0, shading='albedo', light_d=None, ambient_ratio=1.0, normal_epsilon=1e-3):
+    """rays_o / rays_d [N, 3], nears / fars [N] fp32 on the device; density_bitfield [cascade * grid_size^3 / 8] uint8.  Returns
+    (weights_sum [N], depth [N], image [N, out_dim - 1]) fp32, and counts [N] int32 (samples composited per ray) with return_counts.
+    precision: None follows autocast, 0 f32, 1 f16.  max_workgroups: the number of persistent workgroups (0: the default).
+    shading: 'albedo', or 'normal' / 'textureless' / 'lambertian' from the finite-difference normal with step normal_epsilon; light_d
+    [3] fp32 on the device (needed by 'textureless' and 'lambertian', never read on the host) and ambient_ratio as forward() takes them.
+    'lambertian' with four albedo channels is ill-formed in the reference and refused."""
+    spec, emb, ss, wb, N, C, H = _check_render(
+        rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_size, max_steps, shading, light_d, ambient_ratio, normal_epsilon,
+        "normal_epsilon", encoder, sigma_net, sigma_scale, bound, density_activation, density_prior, albedo_sigmoid, precision)
+    if N >= 1 << 32:
+        raise RuntimeError("render_rays takes fewer than 2^32 rays")
+    if int(max_workgroups) != max_workgroups or not 0 <= max_workgroups < 1 << 31:
+        raise RuntimeError("max_workgroups must be a non-negative integer, got %r" % (max_workgroups,))
+    dev = rays_o.device
     weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
     depth = torch.empty(N, dtype=torch.float32, device=dev)
     image = torch.empty((N, spec.out_dim - 1), dtype=torch.float32, device=dev)
@@ -141,21 +167,19 @@ class _RenderRaysTrain(Function):
             raymarch.march_rays_train_into(*march, xyzs, dirs, ts, rays, count, noises)
             del dirs
         # 2. the field
-        sigmas = torch.empty(M, dtype=torch.float32, device=dev)
-        albedo = torch.empty(M, ch, dtype=torch.float16 if spec.precision else torch.float32, device=dev)
-        sigma_fd = torch.empty(M, 6, dtype=torch.float32, device=dev) if st.shading else None
-        if M and st.shading:
-            d = spec.desc(embeddings, sigma_scale, wb)
-            _lib.check(L.dwg_nerf_field_forward_fd(ctypes.byref(d), _lib.ptr(xyzs), M, ctypes.c_float(st.eps), _lib.ptr(sigmas), _lib.ptr(albedo),
-                                                   _lib.ptr(sigma_fd), _st(rays_o)), "dwg_nerf_field_forward_fd")
-        elif M:
-            d = spec.desc(embeddings, sigma_scale, wb)
-            _lib.check(L.dwg_nerf_field_forward(ctypes.byref(d), _lib.ptr(xyzs), M, _lib.ptr(sigmas), _lib.ptr(albedo), _st(rays_o)),
-                       "dwg_nerf_field_forward")
         if st.shading:
+            sigmas = torch.empty(M, dtype=torch.float32, device=dev)
+            albedo = torch.empty(M, ch, dtype=torch.float16 if spec.precision else torch.float32, device=dev)
+            sigma_fd = torch.empty(M, 6, dtype=torch.float32, device=dev)
+            if M:
+                d = spec.desc(embeddings, sigma_scale, wb)
+                _lib.check(L.dwg_nerf_field_forward_fd(ctypes.byref(d), _lib.ptr(xyzs), M, ctypes.c_float(st.eps), _lib.ptr(sigmas),
+                                                       _lib.ptr(albedo), _lib.ptr(sigma_fd), _st(rays_o)), "dwg_nerf_field_forward_fd")
             rgbs = torch.empty(M, ch, dtype=torch.float32, device=dev)
             _shade_train(L, st, sigma_fd, albedo, M, ch, rgbs, _st(rays_o))
         else:
+            sigma_fd = None
+            sigmas, albedo = nerf.field_forward(spec, embeddings, sigma_scale, wb, xyzs)
             rgbs = albedo.float() if spec.precision else albedo             # the composite reads fp32, as composite_rays_train casts
         # 3. the composite, which also reports where each ray stopped
         weights = torch.zeros(M, dtype=torch.float32, device=dev) if st.return_weights else None
@@ -271,23 +295,8 @@ class _RenderRaysTrain(Function):
             dalbedo = grad_rgbs.to(albedo.dtype)
         del grad_rgbs
         # 2. the field backward over the live rows
-        gr = _lib.NerfFieldGradsC()
-        gr.embeddings = None if g_emb is None else g_emb.data_ptr()
-        for l in range(spec.num_layers):
-            gr.weight[l] = None if g_wb[2 * l] is None else g_wb[2 * l].data_ptr()
-            gr.bias[l] = None if g_wb[2 * l + 1] is None else g_wb[2 * l + 1].data_ptr()
-        gr.sigma_scale = None if g_ss is None else g_ss.data_ptr()
-        gr.accumulate = 0
-        d = spec.desc(embeddings, sigma_scale, wb)
-        nbytes = int(L.dwg_nerf_field_backward_workspace_bytes(ctypes.byref(d), M))
-        ws = torch.empty(max(nbytes, 1), device=xyzs.device, dtype=torch.uint8)
-        if st.shading:
-            _lib.check(L.dwg_nerf_field_backward_fd(ctypes.byref(d), _lib.ptr(xyzs), M, ctypes.c_float(st.eps), _lib.ptr(grad_sigmas),
-                                                    _lib.ptr(dalbedo), _lib.ptr(dsigma_fd), ctypes.byref(gr), _lib.ptr(ws), nbytes, _st(xyzs)),
-                       "dwg_nerf_field_backward_fd")
-        else:
-            _lib.check(L.dwg_nerf_field_backward(ctypes.byref(d), _lib.ptr(xyzs), M, _lib.ptr(grad_sigmas), _lib.ptr(dalbedo), ctypes.byref(gr),
-                                                 _lib.ptr(ws), nbytes, _st(xyzs)), "dwg_nerf_field_backward")
+        nerf.field_backward(spec, embeddings, sigma_scale, wb, xyzs, grad_sigmas, dalbedo, g_emb, g_ss, g_wb,
+                            fd=(st.eps, dsigma_fd) if st.shading else None)
         return out
 
 
@@ -322,52 +331,24 @@ def render_rays_train(rays_o, rays_d, nears, fars, density_bitfield, cascade, gr
     sets, over the live rows.  weights_sum, depth, weights, sigmas and live are the 'albedo' call's bits.  'lambertian' with a latent
     field is ill-formed in the reference and refused; the lambert shadings are refused in f16 (the reference's normal @ -l is a
     half-precision product under autocast, not restated); 'normal' runs in both precisions."""
-    if shading not in SHADINGS:
-        raise RuntimeError("shading must be one of %s, got %r" % (", ".join(sorted(SHADINGS)), shading))
     st = _TrainSettings()
+    st.shading = SHADINGS.get(shading, 0)
+    spec, emb_d, _, _, N, C, H = _check_render(
+        rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_size, max_steps, shading, light_d if st.shading >= 2 else None,
+        ambient_ratio, epsilon, "epsilon", encoder, sigma_net, sigma_scale, bound, density_activation, density_prior, albedo_sigmoid, precision)
     wb = []
-    try:
-        spec, emb_d, _, _ = pointcloud.field_spec(encoder, sigma_net, sigma_scale, bound, density_activation, density_prior, albedo_sigmoid, precision)
-    except ValueError as e:
-        raise RuntimeError(str(e)) from None
     for lin in sigma_net.net:
         wb += [lin.weight, lin.bias]
-    _check("rays_o", rays_o, torch.float32, (None, 3))
-    N = rays_o.shape[0]
-    _check("rays_d", rays_d, torch.float32, (N, 3))
-    _check("nears", nears, torch.float32, (N,))
-    _check("fars", fars, torch.float32, (N,))
     for name, t in (("rays_o", rays_o), ("rays_d", rays_d), ("nears", nears), ("fars", fars)):
         if t.requires_grad:
             raise RuntimeError("render_rays_train does not differentiate the rays: %s requires grad" % name)
-    C, H = int(cascade), int(grid_size)
-    if C != cascade or H != grid_size or not (1 <= C <= 8 and 2 <= H <= 1024 and C * H ** 3 < 1 << 32) or H & (H - 1):
-        raise RuntimeError("bad occupancy grid shape: cascade %r, grid_size %r (a power of two: a cell's Morton index must stay below "
-                           "grid_size^3)" % (cascade, grid_size))
-    _check("density_bitfield", density_bitfield, torch.uint8, (C * H ** 3 // 8,))
-    if int(max_steps) != max_steps or not 1 <= max_steps < 1 << 31:
-        raise RuntimeError("max_steps must be an integer >= 1, got %r" % (max_steps,))
     if N >= 1 << 31:
         raise RuntimeError("render_rays_train takes fewer than 2^31 rays")
+    if st.shading >= 2 and spec.precision:
+        raise RuntimeError("shading %r is not taken in f16: the reference's normal @ -l is a half-precision product there" % shading)
     dev = rays_o.device
+    st.light_d, st.ratio, st.eps = light_d.detach() if st.shading >= 2 else None, float(ambient_ratio), float(epsilon)
     others = []
-    st.shading, st.light_d, st.ratio, st.eps = SHADINGS[shading], None, float(ambient_ratio), float(epsilon)
-    if st.shading:
-        if not st.eps > 0:
-            raise RuntimeError("epsilon must be positive, got %r" % (epsilon,))
-        if st.ratio != st.ratio:
-            raise RuntimeError("ambient_ratio is NaN")
-        if st.shading >= 2:
-            if light_d is None:
-                raise RuntimeError("shading %r needs light_d" % shading)
-            _check("light_d", light_d, torch.float32, (3,))
-            others.append(("light_d", light_d))
-            st.light_d = light_d.detach()
-            if spec.precision:
-                raise RuntimeError("shading %r is not taken in f16: the reference's normal @ -l is a half-precision product there" % shading)
-        if st.shading == 3 and spec.out_dim == 5:
-            raise RuntimeError("shading 'lambertian' with four albedo channels (latent mode) is ill-formed in the reference: five channels "
-                               "into a four-channel image")
     if noises is not None:
         _check("noises", noises, torch.float32, (N,))
         others.append(("noises", noises))
@@ -376,9 +357,7 @@ def render_rays_train(rays_o, rays_d, nears, fars, density_bitfield, cascade, gr
         if counter.numel() < 1:
             raise RuntimeError("counter must hold at least one element")
         others.append(("counter", counter))
-    for name, t in [("rays_d", rays_d), ("nears", nears), ("fars", fars), ("density_bitfield", density_bitfield), ("embeddings", emb_d)] + others:
-        if t.device != dev:
-            raise RuntimeError("%s is on %s, rays_o on %s" % (name, t.device, dev))
+    _same_device(dev, others)
     st.spec, st.bound, st.C, st.H = spec, float(bound), C, H
     st.contract, st.dt_gamma, st.max_steps = bool(contract), float(dt_gamma), int(max_steps)
     st.T_thresh, st.binarize = float(T_thresh), bool(binarize)
@@ -404,6 +383,21 @@ def render_rays_train(rays_o, rays_d, nears, fars, density_bitfield, cascade, gr
     return tuple(out)
 
 
+def _covered_shading(ref, flag, shading, light_d, rays_o):
+    """A bound network takes this shading: 'albedo' always; with the opt-in `flag` set on it also 'normal' and, without autocast only,
+    'textureless' and rgb 'lambertian'.  A given light_d must be a [3] fp32 tensor on the rays' device."""
+    if shading == 'albedo':
+        return True
+    if not getattr(ref, flag, False) or shading not in SHADINGS:
+        return False
+    if shading != 'normal' and torch.is_autocast_enabled():
+        return False
+    if shading == 'lambertian' and ref.sigma_net.net[-1].out_features - 1 != 3:
+        return False
+    return light_d is None or (isinstance(light_d, torch.Tensor) and light_d.dtype == torch.float32 and tuple(light_d.shape) == (3,)
+                               and isinstance(rays_o, torch.Tensor) and light_d.device == rays_o.device)
+
+
 def covered_call(ref, rays_o, rays_d, shading, perturb, light_d=None):
     """The native render takes this run_cuda call: evaluation mode, no perturbation, CUDA fp32 rays, the bitfield and the parameters on
     the device, and no autocast dtype but fp16.  shading 'albedo' always; with the network bound with shaded_render, also 'normal' (the
@@ -412,17 +406,7 @@ def covered_call(ref, rays_o, rays_d, shading, perturb, light_d=None):
     'lambertian' is ill-formed).  A given light_d must be a [3] fp32 tensor on the rays' device."""
     if ref.training or perturb or not getattr(ref, "cuda_ray", False):
         return False
-    if shading != 'albedo':
-        if not getattr(ref, "_dwg_shaded_render", False) or shading not in SHADINGS:
-            return False
-        if shading != 'normal' and torch.is_autocast_enabled():
-            return False
-        if shading == 'lambertian' and ref.sigma_net.net[-1].out_features - 1 != 3:
-            return False
-        if light_d is not None and not (isinstance(light_d, torch.Tensor) and light_d.dtype == torch.float32 and tuple(light_d.shape) == (3,)
-                                        and isinstance(rays_o, torch.Tensor) and light_d.device == rays_o.device):
-            return False
-    return _covered_state(ref, rays_o, rays_d)
+    return _covered_shading(ref, "_dwg_shaded_render", shading, light_d, rays_o) and _covered_state(ref, rays_o, rays_d)
 
 
 def _covered_state(ref, rays_o, rays_d):
@@ -434,16 +418,13 @@ def _covered_state(ref, rays_o, rays_d):
     if not isinstance(bits, torch.Tensor) or not bits.is_cuda or bits.dtype != torch.uint8 or not bits.is_contiguous():
         return False
     C, H = ref.cascade, ref.grid_size
-    if not (isinstance(C, int) and isinstance(H, int) and 1 <= C <= 8 and 2 <= H <= 1024 and not H & (H - 1) and C * H ** 3 < 1 << 32):
+    if not (isinstance(C, int) and isinstance(H, int) and _grid_shape(C, H)):
         return False
     if bits.numel() * 8 != C * H ** 3 or ref.sigma_net.net[-1].out_features - 1 not in (3, 4):
         return False
     if not (ref.encoder.embeddings.is_cuda and ref.sigma_scale.is_cuda and all(p.is_cuda for p in ref.sigma_net.parameters())):
         return False
-    if torch.is_autocast_enabled():
-        dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
-        return dt == torch.float16
-    return True
+    return nerf.autocast_covered()
 
 
 def covered_train_call(ref, rays_o, rays_d, shading, light_d=None):
@@ -453,16 +434,8 @@ def covered_train_call(ref, rays_o, rays_d, shading, light_d=None):
     'textureless' and rgb 'lambertian' without autocast, a given light_d a [3] fp32 tensor on the rays' device."""
     if not ref.training or not getattr(ref, "_dwg_train_render", False) or not getattr(ref, "cuda_ray", False):
         return False
-    if shading != 'albedo':
-        if not getattr(ref, "_dwg_train_shaded", False) or shading not in SHADINGS:
-            return False
-        if shading != 'normal' and torch.is_autocast_enabled():
-            return False
-        if shading == 'lambertian' and ref.sigma_net.net[-1].out_features - 1 != 3:
-            return False
-        if light_d is not None and not (isinstance(light_d, torch.Tensor) and light_d.dtype == torch.float32 and tuple(light_d.shape) == (3,)
-                                        and isinstance(rays_o, torch.Tensor) and light_d.device == rays_o.device):
-            return False
+    if not _covered_shading(ref, "_dwg_train_shaded", shading, light_d, rays_o):
+        return False
     if not _covered_state(ref, rays_o, rays_d) or rays_o.requires_grad or rays_d.requires_grad:
         return False
     sc = getattr(ref, "step_counter", None)

@@ -216,14 +216,6 @@ def outside_boxes(points, boxes):
     return keep
 
 
-def _field_forward(spec, d, x):
-    M = x.shape[0]
-    sigma = torch.empty(M, device=x.device, dtype=torch.float32)
-    albedo = torch.empty(M, spec.out_dim - 1, device=x.device, dtype=torch.float16 if spec.precision else torch.float32)
-    _lib.check(_lib.lib().dwg_nerf_field_forward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(sigma), _lib.ptr(albedo), _st(x)), "dwg_nerf_field_forward")
-    return sigma, albedo
-
-
 def field_spec(encoder, sigma_net, sigma_scale, bound, density_activation='exp', density_prior='none', albedo_sigmoid=True, precision=None):
     """(spec, embeddings, sigma_scale [1], [w0, b0, w1, ...]) of a field, checked against dwg_nerf.h's limits and the export's (3 or 4
     albedo channels); ValueError when the kernels do not take it.  Launches nothing."""
@@ -252,7 +244,7 @@ def field_spec(encoder, sigma_net, sigma_scale, bound, density_activation='exp',
 def field_forward(spec, embeddings, sigma_scale, wb, x):
     """(sigma [M] fp32, albedo [M, out_dim - 1]) of dwg_nerf_field_forward at x [M, 3], without autograd."""
     _dev_check("x", x, torch.float32, (None, 3))
-    return _field_forward(spec, spec.desc(embeddings, sigma_scale, wb), x)
+    return nerf.field_forward(spec, embeddings, sigma_scale, wb, x)
 
 
 @torch.no_grad()
@@ -269,7 +261,6 @@ def export_point_cloud(encoder, sigma_net, sigma_scale, bound, *, resolution, sp
     thresh = float(np.float32(density_thresh))
     ax = axis_table(resolution, dev)
     M = resolution ** 3
-    d = spec.desc(emb, ss, wb)
     with torch.cuda.device(dev):
         sigma_all, minmax = lattice_sigma(spec, emb, ss, wb, ax, ax, ax, split)
         idx, count = select_above(sigma_all, thresh)
@@ -284,9 +275,9 @@ def export_point_cloud(encoder, sigma_net, sigma_scale, bound, *, resolution, sp
         idx = idx[:n].clone()
         points = lattice_points(idx, ax, ax, ax, split)
         del idx
-        sigma, albedo = _field_forward(spec, d, points)
+        sigma, albedo = nerf.field_forward(spec, emb, ss, wb, points)
         shifted = fd_points(points, epsilon, float(bound))
-        sig6, _ = _field_forward(spec, d, shifted.view(-1, 3))
+        sig6, _ = nerf.field_forward(spec, emb, ss, wb, shifted.view(-1, 3))
         del shifted, _
         colors, normals = finish(albedo.float() if albedo.dtype != torch.float32 else albedo, sig6.view(6, n), epsilon)
     return PointCloud(points, colors, normals, sigma.view(n, 1), info)

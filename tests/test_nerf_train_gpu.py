@@ -386,6 +386,50 @@ def test_compact_offsets_against_cumsum(N):
     assert total.tolist() == [int(csum[-1])]
 
 
+def test_gather_entry_points_against_torch_indexing():
+    """dwg_nerf_train_gather_live and dwg_nerf_train_gather_live_rows on their own, torch.equal to torch indexing: bit copies.  Nine
+    rays: two waves of four and a tail of one; counts of 70 and 130 take more than one trip of a wave's 64 lanes.  Ray 1 has live == 0,
+    ray 2 live == count, ray 7's source range ends past M and is skipped, so its four live rows keep the fill, as every row no ray
+    owns would.  Odd offsets on both sides (5, 79, 83 / 3, 73, 75) put the 6-byte f16 rgb rows on odd half-words.  Colours f32 with 3
+    and 4 channels, f16 with 3 (half-word slot) and 4 (two-word slot); some arrays NULL; rows of 6 floats and of 1."""
+    from dreamwaltz_g_amd import _lib
+    L = _lib.lib()
+    counts, live = [5, 3, 70, 1, 4, 130, 2, 6, 7], [3, 0, 70, 1, 1, 65, 2, 4, 5]
+    N, M, M_live = len(counts), sum(counts), sum(live)
+    rays = torch.tensor([[sum(counts[:i]), c] for i, c in enumerate(counts)], dtype=torch.int32)
+    rays[7, 0] = M - 2                                              # 6 rows from M - 2: past the end
+    rays_live = torch.tensor([[sum(live[:i]), c] for i, c in enumerate(live)], dtype=torch.int32)
+    src_rows = torch.cat([torch.arange(o, o + c) for n, ((o, _), c) in enumerate(zip(rays.tolist(), live)) if n != 7])
+    dst_rows = torch.cat([torch.arange(o, o + c) for n, (o, c) in enumerate(rays_live.tolist()) if n != 7])
+    assert len(dst_rows) == M_live - 4
+    rays, rays_live, src_rows, dst_rows = rays.cuda(), rays_live.cuda(), src_rows.cuda(), dst_rows.cuda()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g = torch.Generator().manual_seed(9)
+
+    def pair(width, dtype=torch.float32):
+        shape = (M,) if width == 0 else (M, width)
+        src = torch.randn(*shape, generator=g).to(dtype).cuda()
+        dst = torch.full((M_live,) + shape[1:], -7.0, dtype=dtype, device="cuda")
+        want = dst.clone()
+        want[dst_rows] = src[src_rows]
+        return src, dst, want
+
+    for ch, f16, absent in [(3, False, ()), (4, False, ("ts",)), (3, True, ("xyzs", "sigmas")), (4, True, ()), (3, False, ("rgbs",))]:
+        arrays = {"xyzs": pair(3), "ts": pair(2), "sigmas": pair(0), "rgbs": pair(ch, torch.float16 if f16 else torch.float32)}
+        args = []
+        for name in ("xyzs", "ts", "sigmas", "rgbs"):
+            args += [None, None] if name in absent else [_lib.ptr(arrays[name][0]), _lib.ptr(arrays[name][1])]
+        _lib.check(L.dwg_nerf_train_gather_live(_lib.ptr(rays), _lib.ptr(rays_live), N, M, M_live, *args, ch, int(f16), stream),
+                   "dwg_nerf_train_gather_live")
+        for name, (src, dst, want) in arrays.items():
+            assert torch.equal(dst, torch.full_like(dst, -7.0) if name in absent else want), (ch, f16, name)
+    for width in (6, 1):
+        src, dst, want = pair(width)
+        _lib.check(L.dwg_nerf_train_gather_live_rows(_lib.ptr(rays), _lib.ptr(rays_live), N, M, M_live, _lib.ptr(src), _lib.ptr(dst), width,
+                                                     stream), "dwg_nerf_train_gather_live_rows")
+        assert torch.equal(dst, want), width
+
+
 def _bound_net(c, **kw):
     nerf.unbind_nerf_network(c.net)
     assert nerf.bind_nerf_network(c.net, **kw) is None

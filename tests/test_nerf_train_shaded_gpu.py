@@ -206,43 +206,28 @@ def test_shade_forward_against_the_compositions_colours(shading, f16, latent):
 # ----------------------------------------------------------------------------------------------------------------------------------
 # 2. the seven-point-set field backward alone
 # ----------------------------------------------------------------------------------------------------------------------------------
-def _backward_fd(net, x, f16, dsigma, dalbedo, dsigma_fd):
-    spec, d, (emb, ss, wb) = _spec(net, f16, prior='none', bound=nc.BOUND)
-    L = _lib.lib()
-    M = x.shape[0]
+def _grads(emb, wb, fill):
     grads = {'embeddings': torch.zeros_like(emb)}
-    gr = _lib.NerfFieldGradsC()
-    gr.embeddings = grads['embeddings'].data_ptr()
-    for l in range(spec.num_layers):
-        grads['w%d' % l], grads['b%d' % l] = torch.full_like(wb[2 * l], 7.0), torch.full_like(wb[2 * l + 1], 7.0)      # overwritten
-        gr.weight[l], gr.bias[l] = grads['w%d' % l].data_ptr(), grads['b%d' % l].data_ptr()
-    gr.accumulate = 0
-    nbytes = int(L.dwg_nerf_field_backward_workspace_bytes(ctypes.byref(d), M))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    _lib.check(L.dwg_nerf_field_backward_fd(ctypes.byref(d), _lib.ptr(x), M, ctypes.c_float(EPS), _lib.ptr(dsigma), _lib.ptr(dalbedo),
-                                            _lib.ptr(dsigma_fd), ctypes.byref(gr), _lib.ptr(ws), nbytes, _stream()), "dwg_nerf_field_backward_fd")
+    for l in range(len(wb) // 2):
+        grads['w%d' % l], grads['b%d' % l] = torch.full_like(wb[2 * l], fill), torch.full_like(wb[2 * l + 1], fill)
+    return grads, [grads[k] for k in grads if k != 'embeddings']
+
+
+def _backward_fd(net, x, f16, dsigma, dalbedo, dsigma_fd):
+    spec, _, (emb, ss, wb) = _spec(net, f16, prior='none', bound=nc.BOUND)
+    grads, g_wb = _grads(emb, wb, 7.0)                                      # overwritten
+    nerf.field_backward(spec, emb, ss, wb, x, dsigma, dalbedo, grads['embeddings'], None, g_wb, fd=(EPS, dsigma_fd))
     return grads
 
 
 def _seven_backwards(net, x, f16, dsigma, dalbedo, dsigma_fd):
-    spec, d, (emb, ss, wb) = _spec(net, f16, prior='none', bound=nc.BOUND)
-    L = _lib.lib()
-    M = x.shape[0]
-    grads = {'embeddings': torch.zeros_like(emb)}
-    gr = _lib.NerfFieldGradsC()
-    gr.embeddings = grads['embeddings'].data_ptr()
-    for l in range(spec.num_layers):
-        grads['w%d' % l], grads['b%d' % l] = torch.zeros_like(wb[2 * l]), torch.zeros_like(wb[2 * l + 1])
-        gr.weight[l], gr.bias[l] = grads['w%d' % l].data_ptr(), grads['b%d' % l].data_ptr()
-    gr.accumulate = 1
-    nbytes = int(L.dwg_nerf_field_backward_workspace_bytes(ctypes.byref(d), M))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    zero = torch.zeros(M, spec.out_dim - 1, dtype=torch.float16 if f16 else torch.float32, device="cuda")
+    spec, _, (emb, ss, wb) = _spec(net, f16, prior='none', bound=nc.BOUND)
+    grads, g_wb = _grads(emb, wb, 0.0)
+    zero = torch.zeros(x.shape[0], spec.out_dim - 1, dtype=torch.float16 if f16 else torch.float32, device="cuda")
     sets = [(x, dsigma, zero if dalbedo is None else dalbedo)]
     sets += [(p.contiguous(), dsigma_fd[:, s].contiguous(), zero) for s, p in enumerate(_torch_shifted(x, nc.BOUND))]
     for p, ds, da in sets:
-        _lib.check(L.dwg_nerf_field_backward(ctypes.byref(d), _lib.ptr(p), M, _lib.ptr(ds), _lib.ptr(da), ctypes.byref(gr), _lib.ptr(ws), nbytes,
-                                             _stream()), "dwg_nerf_field_backward")
+        nerf.field_backward(spec, emb, ss, wb, p, ds, da, grads['embeddings'], None, g_wb, accumulate=1)
     return grads
 
 
