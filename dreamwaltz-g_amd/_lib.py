@@ -31,6 +31,10 @@ class AdamGroupC(ctypes.Structure):
                 ("n", ctypes.c_int64), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("hyper_row", ctypes.c_int32)]
 
 
+ADAM_MAX_GROUPS = 16        # include/dwg_elementwise.h DWG_ADAM_MAX_GROUPS
+SCALER_MAX_SLOTS = 2048     # include/dwg_grad_scaler.h DWG_SCALER_MAX_SLOTS
+
+
 class SegmentC(ctypes.Structure):
     """include/dwg_gaussian.h dwg_segment."""
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("count", ctypes.c_int64)]
@@ -182,6 +186,12 @@ SIGNATURES = {
     "dwg_adam_step": (ctypes.c_int, [_i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _f32, _vp]),
     "dwg_adam_step_dev": (ctypes.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp]),
     "dwg_adam_step_groups_dev": (ctypes.c_int, [_i32, _vp, _vp, _vp]),
+    # include/dwg_grad_scaler.h
+    "dwg_grads_nonfinite_slots": (_i32, [_i64]),
+    "dwg_grads_nonfinite": (ctypes.c_int, [_i64, _vp, _vp, _vp]),
+    "dwg_scaler_prepare": (ctypes.c_int, [_i32, _vp, _vp, _vp, _i32, _u32, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "dwg_adam_step_groups_scaled_dev": (ctypes.c_int, [_i32, _vp, _vp, _vp]),
+    "dwg_scaler_update": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _i32, _vp]),
     # include/dwg_nn.h
     "dwg_groupnorm_forward": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp]),
     "dwg_groupnorm_backward": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),

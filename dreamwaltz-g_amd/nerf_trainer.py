@@ -8,7 +8,11 @@
 
 Method and dictionary-key names are the reference's.  `diffusion` is any callable with the guidance's call signature that returns a
 dict with 'diffusion_loss'.  The model is nerf_model.NeRFNetwork (or anything with its surface); the optimizers are
-NeRFNetwork.get_optimizer's flat dict.  Single view, single GPU, fp32, as the reference's stage-I loop.
+NeRFNetwork.get_optimizer's flat dict.  Single view, single GPU, as the reference's stage-I loop.
+
+cfg.optim.fp16 (every published stage-I recipe; boundary B21): update_extra_state and the forward run under fp16 autocast, the loss is
+scaled by grad_scaler.FlatGradScaler, every optimizer is stepped through it and the scale is updated, all without a host read
+(trainer.py:840-896 with torch.cuda.amp.GradScaler).  Without it the step is the fp32 one and `scaler` stays None.
 """
 import os
 from random import random
@@ -16,6 +20,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
+from . import grad_scaler
 from . import nerf_model
 from . import nerf_view
 from . import sigma_guidance
@@ -28,8 +33,6 @@ class NeRFSDSTrainer:
         if getattr(cfg, "stage", 'nerf') != 'nerf':
             raise RuntimeError("NeRFSDSTrainer is the stage-I ('nerf') trainer, got stage %r (stage II: trainer.SDSTrainer)" % (cfg.stage,))
         nerf_model.check_optimizer_config(cfg.nerf)
-        if getattr(cfg.optim, "fp16", False):
-            raise NotImplementedError("the native stage-I step is fp32 (optim.fp16 needs the GradScaler's loop)")
         self.cfg, self.model, self.diffusion, self.optimizers = cfg, model, diffusion, optimizers
         self.smpl_model = smpl_model
         self.text_embeds_dict = text_embeds_dict if text_embeds_dict is not None else {}
@@ -38,6 +41,8 @@ class NeRFSDSTrainer:
         self.train_step_index = 0                   # the reference's self.train_step (the name is the loop body's here, as in SDSTrainer)
         self.max_step = cfg.optim.iters if max_step is None else max_step
         self.scaler = None                          # GradScaler(enabled=False) in the fp32 recipes: pass-through
+        if getattr(cfg.optim, "fp16", False):
+            self.scaler = grad_scaler.FlatGradScaler(device=model.sigma_scale.device)        # GradScaler's defaults (trainer.py:372)
         self.schedulers = {}
         self.losses = {'sparsity': nerf_view.SparsityLoss(cfg.nerf)}
         self.time_to_snapshot = False               # logging is the caller's: calc_sigma_loss reads it (its statistics are host reads)
@@ -52,7 +57,7 @@ class NeRFSDSTrainer:
         state = {'train_step': self.train_step_index, 'checkpoints': self.past_checkpoints}
         if full:
             state['optimizers'] = [optimizer.state_dict() for optimizer in self.optimizers.values()]
-            state['scaler'] = {}
+            state['scaler'] = self.scaler.state_dict() if self.scaler is not None else {}
             state['render_state'] = {k: getattr(self.model, k) for k in ('local_step', 'mean_count', 'iter_density', 'mean_density')
                                      if hasattr(self.model, k)}
         state['model'] = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
@@ -86,6 +91,8 @@ class NeRFSDSTrainer:
         if self.optimizers is not None and 'optimizers' in d:
             for optimizer, sd in zip(self.optimizers.values(), d['optimizers']):
                 optimizer.load_state_dict(sd)
+        if self.scaler is not None and d.get('scaler'):
+            self.scaler.load_state_dict(d['scaler'])
 
     # -- the step --------------------------------------------------------------------------------------------------------------------
     def render(self, data, bg_mode=None, **kwargs):
@@ -175,6 +182,8 @@ class NeRFSDSTrainer:
     def train_step(self, data, render_kwargs: Optional[dict] = None, **forced):
         """One iteration of the loop (trainer.py:840-896): -> (loss, render_outputs, sd_outputs, text)."""
         cfg = self.cfg
+        if self.scaler is not None:
+            return self._train_step_fp16(data, render_kwargs, forced)
         # Update Density Grid
         if self.model.cuda_ray and self.train_step_index % cfg.nerf.update_extra_interval == 0:
             self.model.update_extra_state()
@@ -194,6 +203,37 @@ class NeRFSDSTrainer:
         # Optimizer Step
         for optimizer in self.optimizers.values():
             optimizer.step()
+
+        # Scheduler Step
+        for scheduler in self.schedulers.values():
+            if scheduler is not None:
+                scheduler.step()
+        return loss, render_outputs, sd_outputs, text
+
+    def _train_step_fp16(self, data, render_kwargs, forced):
+        """train_step under cfg.optim.fp16: the same statements with the reference's autocast region and its scaler calls."""
+        cfg = self.cfg
+        with torch.autocast('cuda', dtype=torch.float16):
+            # Update Density Grid
+            if self.model.cuda_ray and self.train_step_index % cfg.nerf.update_extra_interval == 0:
+                self.model.update_extra_state()
+
+            # Update Iteration Step
+            self.train_step_index += 1
+
+            # Forward
+            loss, render_outputs, sd_outputs, text = self.train_forward(data, render_kwargs=render_kwargs, **forced)
+
+        # Optimizer Clear Gradient
+        for optimizer in self.optimizers.values():
+            optimizer.zero_grad()
+
+        self._backward(self.scaler.scale(loss))
+
+        # Optimizer Step: the check for Inf / NaN, the skip and the unscale are the device's
+        for optimizer in self.optimizers.values():
+            self.scaler.step(optimizer)
+        self.scaler.update()
 
         # Scheduler Step
         for scheduler in self.schedulers.values():

@@ -122,6 +122,9 @@ class FlatOptimizer:
         self.t = 0
         self.current_iteration = 0
         self.grad_scale = 1.0        # 1 / world size for the multi-view step (mean of the all-reduced sum)
+        self._dev = None             # step_scaled's device block (step counts, learning rates, hyper rows, found, the scan's slots)
+        self._dev_seeded = False     # the device step counts equal the host's pg["t"]
+        self._dev_ahead = False      # the device step counts hold steps the host's pg["t"] lack (step_scaled ran since the last sync)
         if spec.gaussian is not None:
             ga = spec.gaussian
             self.num_iterations = ga["iterations"]
@@ -157,6 +160,7 @@ class FlatOptimizer:
         a group that sat a step out -- its parameter was just replaced by the densifier, `grad is None` in the reference -- does not age.
         `participation`: one bool per group, decided by the caller (the multi-rank step agrees on it across the ranks, trainer._reduce_and_step)
         instead of this process's own record of which parameters its backward touched."""
+        self._host_counts_move("step")
         self.t += 1
         self.current_iteration += 1
         PARAM_EPOCH[0] += 1
@@ -182,6 +186,7 @@ class FlatOptimizer:
         """HOST half of step(): step counts and this step's scalars of every group -> rows base, base + 1, ... of the (pinned) hyper table
         {lr / (1 - b1^t), sqrt(1 - b2^t), grad_scale, 0}.  Returns the number of rows used.  (Participation is not consulted: a captured
         step replays the same launches every time.)"""
+        self._host_counts_move("prepare_step")
         self.t += 1
         self.current_iteration += 1
         PARAM_EPOCH[0] += 1
@@ -209,6 +214,85 @@ class FlatOptimizer:
                                                     float(pg["betas"][1]), float(pg["eps"]), st), "dwg_adam_step_dev")
         return len(self.param_groups)
 
+    # -- the step under a loss scaler (grad_scaler.FlatGradScaler.step): every decision that depends on the gradient's values is the device's -----
+    def _host_counts_move(self, what):
+        """step() / prepare_step() count steps in pg["t"] on the host; step_scaled() counts them on the device.  Going from the device's
+        counts back to the host's needs a sync (state_dict() reads them back, load_state_dict() uploads): without one it is an error."""
+        if self._dev_ahead:
+            raise RuntimeError("FlatOptimizer %r: %s() after step_scaled() without a sync -- the per-group step counts live on the device "
+                               "once a loss scaler steps this optimizer; state_dict() reads them back" % (self.name, what))
+        self._dev_seeded = False
+
+    def _device_state(self):
+        """The device block of step_scaled, created on first use; the step counts are seeded from the host's pg["t"] whenever those moved."""
+        dev = self.buf.flat.device
+        if self._dev is None:
+            self._dev = {"steps": torch.zeros(_lib.ADAM_MAX_GROUPS, dtype=torch.int32, device=dev),
+                         "lr": torch.zeros(_lib.ADAM_MAX_GROUPS, device=dev), "lr_host": None,
+                         "hyper": torch.zeros(_lib.ADAM_MAX_GROUPS, 4, device=dev), "found": torch.zeros(1, device=dev),
+                         "slots": torch.zeros(_lib.SCALER_MAX_SLOTS, dtype=torch.int32, device=dev)}
+        d = self._dev
+        if not self._dev_seeded:
+            t = [int(pg.get("t", 0)) for pg in self.param_groups]
+            d["steps"].copy_(torch.tensor(t + [0] * (_lib.ADAM_MAX_GROUPS - len(t)), dtype=torch.int32))
+            self._dev_seeded = True
+        lr = [float(pg["lr"]) for pg in self.param_groups]
+        if lr != d["lr_host"]:                                               # a changed learning rate is an upload, not a rebuild
+            d["lr"].copy_(torch.tensor(lr + [0.0] * (_lib.ADAM_MAX_GROUPS - len(lr)), dtype=torch.float32))
+            d["lr_host"] = lr
+        return d
+
+    def device_step_counts(self):
+        """The per-group step counts as step_scaled keeps them (a host read), None before its first use."""
+        return None if self._dev is None or not self._dev_seeded else self._dev["steps"][:len(self.param_groups)].tolist()
+
+    def step_scaled(self, scaler, participation=None):
+        """step() under grad_scaler.FlatGradScaler, with no host read: scan this optimizer's gradient range for Inf / NaN, decide on the
+        device (dwg_scaler_prepare: found, the groups' step counts, their scalars with grad_scale / scale as the gradient factor, or the
+        skip flag), then one fused Adam launch over the participating groups that returns at once on the skip flag.  WHICH groups take part
+        is decided here as step() decides it (skip_once, empty groups, the touched-parameters record); WHETHER the step happens is the
+        device's.  pg["t"] is not touched: the device counts are authoritative until state_dict() / load_state_dict() sync them.  The flat
+        gradient stays scaled."""
+        if len(self.param_groups) > _lib.ADAM_MAX_GROUPS:
+            raise RuntimeError("step_scaled covers at most %d param groups per optimizer, got %d" % (_lib.ADAM_MAX_GROUPS, len(self.param_groups)))
+        self.t += 1
+        self.current_iteration += 1
+        PARAM_EPOCH[0] += 1
+        if self.end <= self.start:
+            return
+        b = self.buf
+        mask, groups = 0, []
+        for gi, pg in enumerate(self.param_groups):
+            if pg.pop("skip_once", False):
+                continue
+            if pg["end"] <= pg["start"]:
+                continue
+            if participation is not None:
+                if not participation[gi]:
+                    continue
+            elif self.buf.tracking and pg.get('params') and not any(getattr(p, "_dwg_touched", False) for p in pg['params']):
+                continue
+            n, off = pg["end"] - pg["start"], pg["start"] * 4
+            mask |= 1 << gi
+            groups.append(_lib.AdamGroupC(b.flat.data_ptr() + off, b.grad.data_ptr() + off, b.m.data_ptr() + off, b.v.data_ptr() + off, n,
+                                          float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), gi))
+        d = self._device_state()
+        L = _lib.lib()
+        st = ctypes.c_void_p(torch.cuda.current_stream(b.flat.device).cuda_stream)
+        n = self.end - self.start
+        _lib.check(L.dwg_grads_nonfinite(n, ctypes.c_void_p(b.grad.data_ptr() + 4 * self.start), _lib.ptr(d["slots"]), st), "dwg_grads_nonfinite")
+        G = len(self.param_groups)
+        b1 = (ctypes.c_float * G)(*[float(pg["betas"][0]) for pg in self.param_groups])
+        b2 = (ctypes.c_float * G)(*[float(pg["betas"][1]) for pg in self.param_groups])
+        _lib.check(L.dwg_scaler_prepare(L.dwg_grads_nonfinite_slots(n), _lib.ptr(d["slots"]), scaler.state_ptr(), _lib.ptr(d["found"]), G, mask,
+                                        _lib.ptr(d["lr"]), ctypes.cast(b1, ctypes.c_void_p), ctypes.cast(b2, ctypes.c_void_p),
+                                        float(self.grad_scale), _lib.ptr(d["steps"]), _lib.ptr(d["hyper"]), st), "dwg_scaler_prepare")
+        self._dev_ahead = True
+        if groups:
+            arr = (_lib.AdamGroupC * len(groups))(*groups)
+            _lib.check(L.dwg_adam_step_groups_scaled_dev(len(groups), ctypes.cast(arr, ctypes.c_void_p), _lib.ptr(d["hyper"]), st),
+                       "dwg_adam_step_groups_scaled_dev")
+
     def _launch(self, pg):
         """The fused Adam launch of one group over its slice of the flat buffers (csrc/elementwise.hip k_adam)."""
         b = self.buf
@@ -220,7 +304,12 @@ class FlatOptimizer:
                    "dwg_adam_step")
 
     def state_dict(self):
-        """Same information a torch Adam state_dict carries, flat: step count, per-group hyper-parameters and the two moments."""
+        """Same information a torch Adam state_dict carries, flat: step count, per-group hyper-parameters and the two moments.  After
+        step_scaled the per-group step counts are read back from the device first (a host read: checkpoint time)."""
+        if self._dev_ahead:
+            for pg, t in zip(self.param_groups, self._dev["steps"].tolist()):
+                pg["t"] = int(t)
+            self._dev_ahead = False
         return {"t": self.t, "current_iteration": self.current_iteration,
                 "param_groups": [{k: v for k, v in pg.items() if k != 'params'} for pg in self.param_groups],
                 "exp_avg": self.buf.m[self.start:self.end].clone(), "exp_avg_sq": self.buf.v[self.start:self.end].clone()}
@@ -231,6 +320,7 @@ class FlatOptimizer:
             pg["lr"] = s["lr"]
             pg["t"] = int(s.get("t", sd["t"]))
         self.buf.m[self.start:self.end].copy_(sd["exp_avg"]); self.buf.v[self.start:self.end].copy_(sd["exp_avg_sq"])
+        self._dev_ahead, self._dev_seeded = False, False                     # the loaded counts are uploaded by the next step_scaled
 
 
 class FlatOptimizerDict(dict):

@@ -7,13 +7,19 @@ the NeRF side -- at 64^2, 128^2, 256^2 and 512^2:
              render_rays_train, a torch mix + permute + SparsityLoss, torch.optim.Adam
   view       the two view kernels alone against their torch compositions (rays + near/far; compose forward + backward)
 
-    python tools/bench_nerf_step.py [--sizes 64,128,256,512] [--repeats 20] [--warmup 3] [--guidance] [--profile]
+    python tools/bench_nerf_step.py [--sizes 64,128,256,512] [--repeats 20] [--warmup 3] [--guidance] [--profile] [--fp16]
 
 Per size the composed form runs FIRST and LAST with the native form between them, so the output carries the composed form's own
 run-to-run spread; every figure is min / median / max of host-clock times around a device synchronise, after warm-up steps of the same
 shape.  Both forms render the same network, grid and camera with the same perturbation; the occupancy update is kept out of the timed
 steps (it is B13's, and the same in both forms).  --profile adds torch launches per step for both forms (torch.profiler, a pass of its
-own).  --guidance adds, at 512^2, the native step with the real guidance object (full-width random weights).  Needs a GPU."""
+own).  --guidance adds, at 512^2, the native step with the real guidance object (full-width random weights).
+
+--fp16 (boundary B21) times instead, per size, the step under cfg.optim.fp16 in two forms that share every kernel but the scaler's:
+  native fp16     NeRFSDSTrainer.train_step with grad_scaler.FlatGradScaler: scan, decision, unscale, step counts and scale on the device
+  torch scaler    the same forward under autocast with torch.amp.GradScaler('cuda') driving the same kind of FlatOptimizer (unscale_ over
+                  its .grad views, the found_inf read on the host, then FlatOptimizer.step()): the composition the device scaler replaces
+Each form steps a network and optimizer of its own from the same state; "torch scaler" runs first and last.  Needs a GPU."""
 import argparse
 import os
 import statistics
@@ -138,6 +144,66 @@ class Composed:
         return loss
 
 
+class TorchScalerStep:
+    """The fp16 step with torch.amp.GradScaler('cuda') around the flat optimizers instead of grad_scaler.FlatGradScaler."""
+
+    def __init__(self, tr):
+        self.tr, self.ts = tr, torch.amp.GradScaler('cuda')
+
+    def step(self, data, noises):
+        tr = self.tr
+        with torch.autocast('cuda', dtype=torch.float16):
+            tr.train_step_index += 1
+            out = tr.train_forward(data, render_kwargs=dict(noises=noises))
+        for optimizer in tr.optimizers.values():
+            optimizer.zero_grad()
+        self.ts.scale(out[0]).backward()
+        for optimizer in tr.optimizers.values():
+            self.ts.step(optimizer)
+        self.ts.update()
+        return out
+
+
+def fp16_rows(args, cfg, net):
+    """The --fp16 table: both forms on networks of their own that start from `net`'s parameters and occupancy grid."""
+    cfg.optim.fp16 = True
+    text = {'pos': torch.zeros(1, 77, 8, device=DEV)}
+    print("size   form                 step ms min / median / max      scale after the run (2^16 at its start; halved by every skipped step)")
+    for res in [int(s) for s in args.sizes.split(",")]:
+        data = camera(res, net.bound)
+        noises = torch.rand(res * res, generator=torch.Generator().manual_seed(res)).to(DEV)
+        stub = Stub(res)
+        forms = []
+        for _ in range(2):
+            n = make_network(cfg)
+            n.load_state_dict(net.state_dict())
+            o, _s = n.get_optimizer(cfg.nerf)
+            tr = nerf_trainer.NeRFSDSTrainer(cfg, n, stub, o, text_embeds_dict=dict(text), use_controlnet=False)
+            tr.train_step_index = 1                            # the occupancy update ran before; none inside the timed steps
+            forms.append(tr)
+        nat, comp = forms[0], TorchScalerStep(forms[1])
+
+        def native_step():
+            return nat.train_step(data, render_kwargs=dict(noises=noises))
+
+        def torch_scaler_step():
+            return comp.step(data, noises)
+        first = timed(torch_scaler_step, args.warmup, args.repeats)
+        mid = timed(native_step, args.warmup, args.repeats)
+        last = timed(torch_scaler_step, args.warmup, args.repeats)
+        for name, ts, sc in (("torch scaler (first)", first, None), ("native fp16", mid, nat.scaler.get_scale()),
+                             ("torch scaler (last)", last, comp.ts.get_scale())):
+            print("%4d^2 %-20s %s   %s" % (res, name, fmt(ts), "" if sc is None else "%g" % sc))
+        spread = abs(statistics.median(first) - statistics.median(last))
+        cmed = statistics.median(first + last)
+        print("       native fp16 / torch scaler %.3f (medians; torch scaler = both runs); torch scaler first-to-last spread %.3f ms; "
+              "native - torch scaler %+.3f ms" % (statistics.median(mid) / cmed, spread, statistics.median(mid) - cmed))
+        if args.profile:
+            nk, no = launches(native_step)
+            ck, co = launches(torch_scaler_step)
+            print("       launches per step: native fp16 %d device kernels (%d top-level aten ops), torch scaler %d (%d)" % (nk, no, ck, co))
+
+
 def timed(fn, warmup, repeats):
     for _ in range(warmup):
         fn()
@@ -208,6 +274,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--guidance", action="store_true", help="at 512^2, also the native step with the real guidance object")
     ap.add_argument("--profile", action="store_true", help="torch launches per step for both forms (a pass of its own)")
+    ap.add_argument("--fp16", action="store_true", help="the step under optim.fp16: the device-resident scaler against torch.amp.GradScaler")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_nerf_step needs a GPU: a CPU run says nothing about the step's time")
@@ -220,6 +287,8 @@ def main():
     print("network: bound %g, grid %d^3 x %d cascades, %d table rows; occupied cells %d; lambdas %s; stub guidance" % (
         net.bound, net.grid_size, net.cascade, net.encoder.embeddings.shape[0],
         int(torch.tensor([bin(v).count("1") for v in range(256)], device=DEV)[net.density_bitfield.long()].sum()), LAMBDAS))
+    if args.fp16:
+        return fp16_rows(args, cfg, net)
     print("size   form                 step ms min / median / max      M samples (each form's own count, last step of the run)")
     for res in [int(s) for s in args.sizes.split(",")]:
         data = camera(res, net.bound)
