@@ -40,9 +40,10 @@ __device__ __forceinline__ float dwg_wave_sum_all(float v) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 __device__ __forceinline__ int dwg_lane() { return (int)(threadIdx.x & 63); }
-// erf for the GELU epilogues of the bf16 layers: Abramowitz-Stegun 7.1.26, branch-free, one exp + one rcp + 6 fma.  Absolute
-// error 6e-7 in fp32 (libm's erff costs ~3x the instructions with both branches executed under divergence); the results are
-// rounded to bf16 (relative 4e-3) right after, and the fp32 MLPs of the avatar do not use GELU.
+// erf for the GELU epilogues (GEMM epilogue, GEGLU) in every element type: Abramowitz-Stegun 7.1.26, branch-free, one exp + one rcp +
+// 6 fma.  Absolute error 6e-7 in fp32 (libm's erff costs ~3x the instructions with both branches executed under divergence).  The 16-bit
+// plans round the result to bf16 / fp16 (relative 4e-3 / 5e-4) right after; the f32 and f32x denoiser plans use it too and keep that 6e-7,
+// which is inside their 1e-5-of-the-output-scale bar (tests/test_gemm_x_gpu.py).  The fp32 MLPs of the avatar do not use GELU.
 __device__ __forceinline__ float dwg_erf_fast(float x) {
     const float ax = fabsf(x);
     const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));      // v_rcp_f32 (HIP's __frcp_rn is an out-of-line call: stack + clobbers)

@@ -558,6 +558,10 @@ static void gn_reduce_geometry(int HW, int C, int* pix_per_block, int* chunks) {
 // finalize folded into the apply pass: few partials, and four threads per (group, statistic) fit one workgroup
 static bool gn_fold(int rchunks, int G) { return rchunks <= GN_FOLD_MAX_CHUNKS && 2 * G * 4 <= 256; }
 
+// f32x rows addressed element by element (ld1 / st1 -> dwg_x_get1 / dwg_x_put1): every row has to start on a 32-byte group, i.e. a 16-byte
+// aligned base and a row stride in whole groups of 8 elements -- any other stride puts the hi / lo halves of a row into its neighbours' groups
+static bool x_rows_ok(const void* base, long long ld) { return ((uintptr_t)base & 15) == 0 && ld % 8 == 0; }
+
 }  // namespace
 
 // element-type dispatch of the entry points (DWG_DTYPE_* of include/dwg_types.h)
@@ -683,6 +687,7 @@ int dwg_geglu_forward(int64_t M, int32_t F, const void* x, void* out, dwg_stream
 int dwg_softmax_rows_forward_dt(int32_t dtype, int32_t rows, int32_t n, float scale, const float* S, int64_t lds, void* P, int64_t ldp,
                                 dwg_stream_t stream) {
     if (rows < 0 || n <= 0 || !S || !P) return DWG_E_ARG;
+    if (dtype == DWG_DTYPE_F32X && !x_rows_ok(P, ldp)) return DWG_E_ARG;
     if (rows == 0) return DWG_OK;
     DWG_DT_SWITCH(dtype, DWG_LAUNCH("softmax_rows", k_softmax_rows<T>, dim3(dwg_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, rows, n, scale,
                                     S, (long long)lds, (T*)P, (long long)ldp))
@@ -698,6 +703,7 @@ int dwg_softmax_rows_forward(int32_t rows, int32_t n, float scale, const float* 
 int dwg_softmax_rows_backward_dt(int32_t dtype, int32_t rows, int32_t n, float scale, const void* P, int64_t ldp, const float* dP, int64_t lddp,
                                  void* dS, int64_t ldds, dwg_stream_t stream) {
     if (rows < 0 || n <= 0 || !P || !dP || !dS) return DWG_E_ARG;
+    if (dtype == DWG_DTYPE_F32X && !(x_rows_ok(P, ldp) && x_rows_ok(dS, ldds))) return DWG_E_ARG;
     if (rows == 0) return DWG_OK;
     DWG_DT_SWITCH(dtype, DWG_LAUNCH("softmax_rows_bwd", k_softmax_rows_bwd<T>, dim3(dwg_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, rows, n,
                                     scale, (const T*)P, (long long)ldp, dP, (long long)lddp, (T*)dS, (long long)ldds))

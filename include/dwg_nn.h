@@ -49,10 +49,15 @@ int dwg_softmax_rows_forward(int32_t rows, int32_t n, float scale, const float* 
 int dwg_softmax_rows_backward(int32_t rows, int32_t n, float scale, const void* P, int64_t ldp, const float* dP, int64_t lddp,
                               void* dS, int64_t ldds, dwg_stream_t stream);
 
-/* The same layers for any activation element type: `dtype` = DWG_DTYPE_BF16 | DWG_DTYPE_F16 | DWG_DTYPE_F32 (dwg_types.h) of every
- * `void*` activation argument; affine parameters, statistics and scratch stay fp32.  The un-suffixed entry points above are the
+/* The same layers for any activation element type: `dtype` = DWG_DTYPE_BF16 | DWG_DTYPE_F16 | DWG_DTYPE_F32 | DWG_DTYPE_F32X (dwg_types.h)
+ * of every `void*` activation argument; affine parameters, statistics and scratch stay fp32.  The un-suffixed entry points above are the
  * DWG_DTYPE_BF16 case.  fp32 is the precision the reference runs the 3DGS stage in (/root/reference/configs/__init__.py:236,241 --
- * `--optim.fp16` is only passed to the NeRF stages), fp16 is its autocast storage type (configs/__init__.py:462, trainer.py:844,859). */
+ * `--optim.fp16` is only passed to the NeRF stages), fp16 is its autocast storage type (configs/__init__.py:462, trainer.py:844,859);
+ * F32X is the split-precision storage of the f32x plans (csrc/dwg_xfmt.h: 32-byte groups of 8 elements, fp32-grade values).
+ * Strides: the GroupNorm / LayerNorm / GEGLU tensors are dense (C, F % 8 == 0, so every row is whole groups).  The row softmax takes any
+ * `lds` / `lddp` (fp32) and, for the 2- and 4-byte element types, any `ldp` / `ldds`; with DWG_DTYPE_F32X every P / dS row must start on a
+ * group: `ldp` / `ldds` % 8 == 0 and a 16-byte aligned P / dS, DWG_E_ARG otherwise (n itself may be anything: a row's last group is then
+ * written in part, element by element). */
 int dwg_groupnorm_forward_dt(int32_t dtype, int32_t B, int32_t HW, int32_t C, int32_t G, const void* x, const float* gamma,
                              const float* beta, float eps, int32_t fuse_silu, void* y, float* stats, float* workspace,
                              dwg_stream_t stream);
