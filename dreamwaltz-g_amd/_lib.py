@@ -62,6 +62,17 @@ class NerfFieldGradsC(ctypes.Structure):
                 ("sigma_scale", ctypes.c_void_p), ("accumulate", ctypes.c_uint32)]
 
 
+class NerfBgDescC(ctypes.Structure):
+    """struct dwg_nerf_bg_desc (include/dwg_nerf_background.h)."""
+    _fields_ = [("degree", ctypes.c_uint32), ("num_layers", ctypes.c_uint32), ("hidden", ctypes.c_uint32), ("out_dim", ctypes.c_uint32),
+                ("weight", ctypes.c_void_p * 3), ("bias", ctypes.c_void_p * 3), ("sigmoid", ctypes.c_uint32), ("precision", ctypes.c_uint32)]
+
+
+class NerfBgGradsC(ctypes.Structure):
+    """struct dwg_nerf_bg_grads (include/dwg_nerf_background.h)."""
+    _fields_ = [("weight", ctypes.c_void_p * 3), ("bias", ctypes.c_void_p * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares must be listed here (tests check it)
 _vp, _i32, _i64, _f32, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _u32 = ctypes.c_uint32
@@ -272,6 +283,11 @@ SIGNATURES = {
     "dwg_nerf_view_compose_forward": (ctypes.c_int, [_u32, _u32, _u32, _vp, _vp, _vp, _u32] + [ctypes.c_double] * 4 + [_vp, _vp, _vp, _sz, _vp]),
     "dwg_nerf_view_compose_backward": (ctypes.c_int, [_u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32] + [ctypes.c_double] * 4
                                        + [_vp, _sz, _vp, _vp, _vp, _vp]),
+    # include/dwg_nerf_background.h
+    "dwg_nerf_freq_encode": (ctypes.c_int, [_u32, _vp, _u32, _vp, _vp]),
+    "dwg_nerf_bg_forward": (ctypes.c_int, [_u32, _vp, ctypes.POINTER(NerfBgDescC), _vp, _vp]),
+    "dwg_nerf_bg_backward_workspace_bytes": (_sz, [ctypes.POINTER(NerfBgDescC)]),
+    "dwg_nerf_bg_backward": (ctypes.c_int, [_u32, _vp, _vp, ctypes.POINTER(NerfBgDescC), ctypes.POINTER(NerfBgGradsC), _vp, _sz, _vp]),
     # include/dwg_graph.h
     "dwg_graph_begin_capture": (ctypes.c_int, [_vp]),
     "dwg_graph_end_capture": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),

@@ -414,9 +414,12 @@ def _bind_run_cuda(ref):
 def bind_nerf_view(ref):
     """Opt-in, on a network bind_nerf_network has bound (boundary B20): ref.render becomes nerf_view.render_view for the calls
     nerf_view.covered_view takes -- rays, run_cuda's native branches and the background mix with the planar image, one launch each
-    around the render.  dmtet, a network without cuda_ray, staged, several cameras, a camera that is not fp32 on the device, a 'nerf'
-    background and the run_cuda calls the native renders do not take (a training view needs train_render) go to the original render,
-    decided before anything is drawn.  Returns None when bound, else the reason.  unbind_nerf_network removes it."""
+    around the render.  The learned 'nerf' background is rendered natively too (boundary B22, nerf_background.learned_background) when
+    the network has a bg_net of supported biased nn.Linear layers on the camera's device, an encoder_bg of 3 inputs with a supported
+    degree and no decoder_layer -- a reference _NeRFNetwork built with bg_mode='nerf' has them.  dmtet, a network without cuda_ray,
+    staged, several cameras, a camera that is not fp32 on the device, a 'nerf' background on a network without such a bg_net and the
+    run_cuda calls the native renders do not take (a training view needs train_render) go to the original render, decided before anything
+    is drawn.  Returns None when bound, else the reason.  unbind_nerf_network removes it."""
     if not getattr(ref, "_dwg_nerf_bound", False):
         return "the network is not bound (bind_nerf_network first)"
     if not hasattr(type(ref), "render"):

@@ -8,10 +8,14 @@ the package's own pieces.
       .update_extra_state                         OccupancyGrid.update (B13) + the reference's step-counter statements
       .render                                     nerf_view.render_view (B20 over B14 / B15 / B18 / B19)
       .get_optimizer(cfg)                         the flat fused Adam of optim.build_flat_optimizers
+  BackgroundNeRFNetwork(cfg, device)   NeRFNetwork with the learned background (bg_mode 'nerf', boundary B22): encoder_bg
+                             (nerf_background.FreqEncoder(3, 6)) + bg_net, rendered through nerf_background.learned_background, and a
+                             'bg_net' group at cfg.bg_lr in the same flat Adam
+  build_nerf_network(cfg, device)      the class cfg.bg_mode asks for, as the reference's build_NeRFNetwork picks its class
 
 Covered: structure 'shared_mlp', backbone 'tiledgrid' / 'hashgrid', nerf_type 'rgb' / 'latent', cuda_ray, optimizer 'adam' with
-lr_policy 'constant' / 'none'.  The learned 'nerf' background, dmtet, run() without cuda_ray, the other optimizers and the
-learning-rate schedulers are refused by name.
+lr_policy 'constant' / 'none'.  dmtet, run() without cuda_ray, the other optimizers and the learning-rate schedulers are refused by
+name; NeRFNetwork itself refuses the learned 'nerf' background (BackgroundNeRFNetwork builds it).
 """
 import math
 
@@ -20,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import nerf
+from . import nerf_background
 from . import nerf_view
 from . import occupancy
 from . import optim
@@ -60,6 +65,7 @@ class NeRFNetwork(nn.Module):
     _dwg_train_render = True
     _dwg_train_shaded = True
     dmtet = False
+    _learned_background = False         # BackgroundNeRFNetwork: cfg.bg_mode 'nerf' is accepted
 
     def __init__(self, cfg, device=None, num_layers=3, hidden_dim=64):
         super().__init__()
@@ -73,8 +79,9 @@ class NeRFNetwork(nn.Module):
             raise NotImplementedError("dmtet is not built natively")
         if not cfg.cuda_ray:
             raise NotImplementedError("run() without cuda_ray is not built natively")
-        if cfg.bg_mode == 'nerf':
-            raise NotImplementedError("the learned 'nerf' background is not built natively")
+        if cfg.bg_mode == 'nerf' and not self._learned_background:
+            raise NotImplementedError("the learned 'nerf' background is not built natively by NeRFNetwork "
+                                      "(BackgroundNeRFNetwork / build_nerf_network build it)")
         if cfg.density_prior not in nerf.PRIORS:
             raise NotImplementedError("density_prior %r is not covered (%s)" % (cfg.density_prior, ", ".join(sorted(nerf.PRIORS))))
         if cfg.density_activation not in nerf.ACTIVATIONS:
@@ -204,15 +211,49 @@ class NeRFNetwork(nn.Module):
         return nerf_view.render_view(self, data, shading=shading, bg_mode=bg_mode, **kwargs)
 
     # -- optimizer ---------------------------------------------------------------------------------------------------------------------
+    def _param_groups(self, cfg):
+        lr = cfg.lr
+        return [
+            {'params': list(self.encoder.parameters()), 'lr': lr * 10, 'name': 'encoder'},
+            {'params': list(self.sigma_net.parameters()), 'lr': lr, 'name': 'sigma_net'},
+            {'params': [self.sigma_scale], 'lr': lr, 'name': 'sigma_scale'},
+        ]
+
     def get_optimizer(self, cfg, diffusion=None):
         """_NeRFNetwork.get_optimizer (nerf_model.py:297-329) with build_optimizer's 'adam' (:171-173): encoder at lr x 10, sigma_net at lr,
         sigma_scale at lr, betas (0.9, 0.99), eps 1e-15 -- as one named optimizer 'nerf' over the flat buffers, a fused launch per group.
         Returns (optimizers, scheduler) like the reference; the scheduler of lr_policy 'constant' / 'none' is None."""
         check_optimizer_config(cfg)
-        lr = cfg.lr
-        spec = optim.AdamSpec([
-            {'params': list(self.encoder.parameters()), 'lr': lr * 10, 'name': 'encoder'},
-            {'params': list(self.sigma_net.parameters()), 'lr': lr, 'name': 'sigma_net'},
-            {'params': [self.sigma_scale], 'lr': lr, 'name': 'sigma_scale'},
-        ], betas=(0.9, 0.99), eps=1e-15)
+        spec = optim.AdamSpec(self._param_groups(cfg), betas=(0.9, 0.99), eps=1e-15)
         return optim.build_flat_optimizers({'nerf': spec}, self.sigma_scale.device), None
+
+
+class BackgroundNeRFNetwork(NeRFNetwork):
+    """NeRFNetwork with the reference's learned background (nerf_model.py:248-256, bg_radius > 0): encoder_bg = FreqEncoder(3, 6) and
+    bg_net = MLP(39, 3 + additional_dim_size, hidden_dim_bg, num_layers_bg), state-dict keys bg_net.net.{l}.{weight,bias}.  The render
+    takes bg_mode 'nerf' through nerf_background.learned_background (boundary B22)."""
+    _learned_background = True
+
+    def __init__(self, cfg, device=None, num_layers=3, hidden_dim=64, num_layers_bg=2, hidden_dim_bg=64):
+        super().__init__(cfg, device=None, num_layers=num_layers, hidden_dim=hidden_dim)
+        self.bg_radius = cfg.bg_radius
+        self.num_layers_bg, self.hidden_dim_bg = num_layers_bg, hidden_dim_bg
+        self.encoder_bg = nerf_background.FreqEncoder(input_dim=3, degree=6)
+        self.in_dim_bg = self.encoder_bg.output_dim
+        self.bg_net = MLP(self.in_dim_bg, 3 + self.additional_dim_size, hidden_dim_bg, num_layers_bg, bias=True)
+        reason = nerf_background.unsupported_reason(self.encoder_bg, self.bg_net)
+        if reason is not None:
+            raise NotImplementedError("this learned background is not built natively: %s" % reason)
+        if device is not None:
+            self.to(device)
+
+    def _param_groups(self, cfg):
+        """The reference's groups (nerf_model.py:312-314): bg_net at bg_lr.  Its encoder_bg group at bg_lr x 10 is empty (the frequency
+        encoding has no parameters) and is not created."""
+        return super()._param_groups(cfg) + [{'params': list(self.bg_net.parameters()), 'lr': cfg.bg_lr, 'name': 'bg_net'}]
+
+
+def build_nerf_network(cfg, device=None, **kw):
+    """The stage-I network cfg asks for: BackgroundNeRFNetwork when cfg.bg_mode is 'nerf', else NeRFNetwork."""
+    cls = BackgroundNeRFNetwork if cfg.bg_mode == 'nerf' else NeRFNetwork
+    return cls(cfg, device=device, **kw)

@@ -7,8 +7,9 @@
                                                    forward; zero_grad; backward; the fused Adam step
 
 Method and dictionary-key names are the reference's.  `diffusion` is any callable with the guidance's call signature that returns a
-dict with 'diffusion_loss'.  The model is nerf_model.NeRFNetwork (or anything with its surface); the optimizers are
-NeRFNetwork.get_optimizer's flat dict.  Single view, single GPU, as the reference's stage-I loop.
+dict with 'diffusion_loss'.  The model is what nerf_model.build_nerf_network(cfg.nerf) returns -- NeRFNetwork, or BackgroundNeRFNetwork
+for the learned 'nerf' background (boundary B22: bg_net steps in its own group of the same flat Adam) -- or anything with its surface;
+the optimizers are its get_optimizer's flat dict.  Single view, single GPU, as the reference's stage-I loop.
 
 cfg.optim.fp16 (every published stage-I recipe; boundary B21): update_extra_state and the forward run under fp16 autocast, the loss is
 scaled by grad_scaler.FlatGradScaler, every optimizer is stepped through it and the scale is updated, all without a host read

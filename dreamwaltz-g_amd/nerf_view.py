@@ -6,7 +6,8 @@ csrc/nerf_view.hip through include/dwg_nerf_view.h.
   view_compose(image_fg, weights_sum, bg, ..)  the background mix written planar ([1, C, H, W], what the guidance takes) and the
                                                sparsity loss of weights_sum, one autograd function; backward in one launch
   SparsityLoss(cfg)                            the reference's fields and schedule; the loss itself is the fused one
-  render_view(net, data, shading, bg_mode)     render() of a cuda_ray network: rays -> nerf_render.run_cuda_native -> compose
+  render_view(net, data, shading, bg_mode)     render() of a cuda_ray network: rays -> nerf_render.run_cuda_native -> the background
+                                               (the learned 'nerf' one through nerf_background.learned_background, B22) -> compose
   covered_view(ref, data, ...)                 which render() calls of a bound reference network render_view takes
 
 No CPU fallback; every tensor is checked (CUDA, fp32, shape, contiguity) and a violation raises RuntimeError before any launch.
@@ -18,6 +19,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
+from . import nerf_background
 from . import nerf_render
 
 BG_NONE, BG_CONSTANT, BG_IMAGE = 0, 1, 2
@@ -247,10 +249,21 @@ def _camera_ok(t, tail):
             and not t.requires_grad)
 
 
+def _learned_background_reason(net, device=None):
+    """None when the learned 'nerf' background of this network is built natively (boundary B22), else why not: a bg_net whose `.net` holds
+    supported biased nn.Linear layers (on `device`), an encoder_bg of 3 inputs with a supported degree, and no decoder_layer."""
+    if getattr(net, "bg_net", None) is None:
+        return "the network has no bg_net"
+    if getattr(net, "decoder_layer", None) is not None:
+        return "a decoder_layer is not covered"
+    return nerf_background.unsupported_reason(getattr(net, "encoder_bg", None), net.bg_net, device)
+
+
 def covered_view(ref, data, shading='albedo', bg_mode=None, staged=False, light_d=None, ambient_ratio=1.0):
     """render_view takes this render() call of a network: cuda_ray (no dmtet, not staged), one fp32 camera on the device, a background
-    mode other than the learned 'nerf' one, and a run_cuda call the native renders take (nerf_render.covered_train_call in training,
-    covered_call in evaluation: shading, autocast, the bitfield and the parameters on the device).  Decided before anything is drawn."""
+    mode it builds -- the learned 'nerf' one only with a bg_net and encoder_bg the kernels take (_learned_background_reason) --, and a
+    run_cuda call the native renders take (nerf_render.covered_train_call in training, covered_call in evaluation: shading, autocast,
+    the bitfield and the parameters on the device).  Decided before anything is drawn."""
     if getattr(ref, "dmtet", False) or not getattr(ref, "cuda_ray", False) or staged:
         return False
     try:
@@ -263,9 +276,12 @@ def covered_view(ref, data, shading='albedo', bg_mode=None, staged=False, light_
     if not isinstance(H, int) or not isinstance(W, int) or not (1 <= H <= MAX_SIZE and 1 <= W <= MAX_SIZE):
         return False
     mode = ref.bg_mode if bg_mode is None else bg_mode
-    if shading != 'normal' and (mode == 'nerf' or (mode not in ('none', None, 'disable', 'zero', 'zeros', 'normal', 'uniform')
-                                                   and mode not in getattr(ref, "bg_colors", {}))):
-        return False                                  # shading 'normal' never asks for a background
+    if shading != 'normal':                           # shading 'normal' never asks for a background
+        if mode == 'nerf':
+            if _learned_background_reason(ref, c2w.device) is not None:
+                return False
+        elif mode not in ('none', None, 'disable', 'zero', 'zeros', 'normal', 'uniform') and mode not in getattr(ref, "bg_colors", {}):
+            return False
     if not isinstance(ambient_ratio, (int, float)):
         return False
     aabb = ref.aabb_train if ref.training else ref.aabb_infer
@@ -289,8 +305,9 @@ def render_view(net, data, shading='albedo', bg_mode=None, *, sparsity=None, noi
     of this step; the fused loss comes back as 'sparsity_loss'.  noises [H W]: the training march's perturbation instead of its draw.
 
     The host and device generators are consumed as the reference consumes them: run_cuda's light_d draw, the march's perturbation,
-    rand_bg_prob's random(), 'uniform''s torch.rand(img_dims), 'normal''s randn_like.  The learned 'nerf' background is not built:
-    NotImplementedError.  A call the native renders do not take (nerf_render.covered_train_call / covered_call) is an error here; a
+    rand_bg_prob's random(), 'uniform''s torch.rand(img_dims), 'normal''s randn_like.  The learned 'nerf' background
+    (nerf_background.learned_background of the rays' directions) needs a network with a bg_net and encoder_bg the kernels take and no
+    decoder_layer: otherwise NotImplementedError.  A call the native renders do not take (nerf_render.covered_train_call / covered_call) is an error here; a
     bound reference network sends such calls to its original method instead (covered_view)."""
     if kwargs.pop('staged', False):
         raise RuntimeError("render_view does not stage: cuda_ray never does")
@@ -305,7 +322,7 @@ def render_view(net, data, shading='albedo', bg_mode=None, *, sparsity=None, noi
     W = data['image_width']
     train = bool(net.training)
     mode_now = net.bg_mode if bg_mode is None else bg_mode
-    if shading != 'normal' and mode_now == 'nerf':
+    if shading != 'normal' and mode_now == 'nerf' and _learned_background_reason(net) is not None:
         raise NotImplementedError("the learned 'nerf' background is not built natively")
 
     # rays_o, rays_d: [B, N, 3], assumes B == 1
@@ -332,7 +349,7 @@ def render_view(net, data, shading='albedo', bg_mode=None, *, sparsity=None, noi
         image_bg, channels_out = None, 3
     else:
         # mix background color
-        image_bg, channels_out = _background(net, image_fg, bg_mode), None
+        image_bg, channels_out = _background(net, image_fg, bg_mode, rays_d), None
         if image_bg is not None:
             results['image_bg'] = image_bg.expand_as(image_fg)
             results['image_fg'] = image_fg
@@ -345,9 +362,9 @@ def render_view(net, data, shading='albedo', bg_mode=None, *, sparsity=None, noi
     return results
 
 
-def _background(net, image, bg_mode):
-    """_NeRFNetwork.background (core/nerf/nerf_model.py:107-144) without the learned mode: None, a colour [C] or an image like
-    `image`, with the reference's draws."""
+def _background(net, image, bg_mode, rays_d):
+    """_NeRFNetwork.background (core/nerf/nerf_model.py:107-144): None, a colour [C] or an image like `image`, with the reference's
+    draws.  rays_d [B, H W, 3]: read by the learned mode."""
     if bg_mode is None:
         bg_mode = net.bg_mode
 
@@ -365,5 +382,6 @@ def _background(net, image, bg_mode):
     elif bg_mode == 'uniform':
         return torch.rand(net.img_dims).to(image).contiguous()
     elif bg_mode == 'nerf':
-        raise NotImplementedError("the learned 'nerf' background is not built natively")
+        h = nerf_background.learned_background(rays_d.view(-1, 3), net.encoder_bg, net.bg_net, sigmoid=not net.latent_mode)
+        return h.reshape(image.shape)
     return net.bg_colors[bg_mode].to(image).contiguous()

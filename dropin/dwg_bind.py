@@ -81,8 +81,9 @@ Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's fie
                                                      normal-adapted guidance renders them); unset or any other value: training calls of run_cuda
                                                      stay on the reference's statements
              DWG_BIND_NERF_VIEW = 1                   also bind the NeRF network's render() (B20, nerf.bind_nerf_view: rays, the background
-                                                     mix and the planar image in one launch each); unset or any other value: render() is the
-                                                     reference's
+                                                     mix and the planar image in one launch each; a network built with bg_mode 'nerf' -- it
+                                                     has a bg_net and an encoder_bg -- also gets its learned background from one launch, B22:
+                                                     dreamwaltz_g_amd.nerf_background); unset or any other value: render() is the reference's
              DWG_BIND_INIT = 0                        leave the avatar constructor's geometry (B11) on the reference path (igl + pytorch3d)
              DWG_BIND_POINTCLOUD = 0                  leave the NeRF-to-Gaussian point-cloud export (B12) on the reference path
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)

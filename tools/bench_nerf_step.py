@@ -7,7 +7,7 @@ the NeRF side -- at 64^2, 128^2, 256^2 and 512^2:
              render_rays_train, a torch mix + permute + SparsityLoss, torch.optim.Adam
   view       the two view kernels alone against their torch compositions (rays + near/far; compose forward + backward)
 
-    python tools/bench_nerf_step.py [--sizes 64,128,256,512] [--repeats 20] [--warmup 3] [--guidance] [--profile] [--fp16]
+    python tools/bench_nerf_step.py [--sizes 64,128,256,512] [--repeats 20] [--warmup 3] [--guidance] [--profile] [--fp16] [--bg-mode nerf]
 
 Per size the composed form runs FIRST and LAST with the native form between them, so the output carries the composed form's own
 run-to-run spread; every figure is min / median / max of host-clock times around a device synchronise, after warm-up steps of the same
@@ -19,7 +19,11 @@ own).  --guidance adds, at 512^2, the native step with the real guidance object 
   native fp16     NeRFSDSTrainer.train_step with grad_scaler.FlatGradScaler: scan, decision, unscale, step counts and scale on the device
   torch scaler    the same forward under autocast with torch.amp.GradScaler('cuda') driving the same kind of FlatOptimizer (unscale_ over
                   its .grad views, the found_inf read on the host, then FlatOptimizer.step()): the composition the device scaler replaces
-Each form steps a network and optimizer of its own from the same state; "torch scaler" runs first and last.  Needs a GPU."""
+Each form steps a network and optimizer of its own from the same state; "torch scaler" runs first and last.
+
+--bg-mode nerf (boundary B22) times the same forms with the learned background: the native step on nerf_model.BackgroundNeRFNetwork
+(nerf_background.learned_background, the 'bg_net' group in the flat Adam), the composed step with the frequency encoding restated in
+torch, bg_net, the sigmoid and a fourth torch.optim.Adam group.  Needs a GPU."""
 import argparse
 import os
 import statistics
@@ -37,22 +41,22 @@ DEV = "cuda"
 LAMBDAS = (5e-3, 1e-3, 0.5)
 
 
-def make_cfg():
+def make_cfg(bg_mode='gray'):
     cfg = configs.TrainConfig()
     cfg.stage, cfg.device = 'nerf', DEV
     cfg.nerf = configs.NeRFConfig(bound=2.0, grid_size=128, density_prior='gaussian', lambda_opacity=LAMBDAS[0], lambda_entropy=LAMBDAS[1],
-                                  lambda_emptiness=LAMBDAS[2], update_extra_interval=1 << 30)
+                                  lambda_emptiness=LAMBDAS[2], update_extra_interval=1 << 30, bg_mode=bg_mode)
     cfg.prompt.text_augmentation = False
     cfg.optim.iters = 10000
     return cfg
 
 
 def make_network(cfg, seed=0):
-    net = nerf_model.NeRFNetwork(cfg.nerf)
+    net = nerf_model.build_nerf_network(cfg.nerf)
     g = torch.Generator().manual_seed(seed)
     with torch.no_grad():
         net.encoder.embeddings.copy_((torch.rand(net.encoder.embeddings.shape, generator=g) * 2 - 1) * 0.1)
-        for lin in net.sigma_net.net:
+        for lin in list(net.sigma_net.net) + (list(net.bg_net.net) if net.bg_net is not None else []):
             lin.weight.copy_(torch.randn(lin.weight.shape, generator=g) * (1.0 / lin.in_features) ** 0.5)
             lin.bias.copy_(torch.randn(lin.bias.shape, generator=g) * 0.1)
     return net.to(DEV).train()
@@ -92,6 +96,15 @@ def torch_get_rays(c2w, intrinsics, H, W):
     return rays_o, rays_d
 
 
+def torch_freq_encode(x, degree):
+    """The frequency encoding (FreqEncoder's layout) in torch: x, then per frequency the sines and the cosines of 2^f x."""
+    cols = [x]
+    for f in range(degree):
+        v = x * (2.0 ** f)
+        cols += [torch.sin(v), torch.cos(v)]
+    return torch.cat(cols, -1)
+
+
 def torch_sparsity(ws):
     lo, le, lm = LAMBDAS
     al = ws.clamp(1e-6, 1 - 1e-6)
@@ -117,8 +130,11 @@ class Composed:
         self.net = make_network(cfg)
         self.net.load_state_dict(src.state_dict())
         n = self.net
-        self.opt = torch.optim.Adam([{'params': n.encoder.parameters(), 'lr': cfg.nerf.lr * 10}, {'params': n.sigma_net.parameters(), 'lr': cfg.nerf.lr},
-                                     {'params': n.sigma_scale, 'lr': cfg.nerf.lr}], betas=(0.9, 0.99), eps=1e-15)
+        groups = [{'params': n.encoder.parameters(), 'lr': cfg.nerf.lr * 10}, {'params': n.sigma_net.parameters(), 'lr': cfg.nerf.lr},
+                  {'params': n.sigma_scale, 'lr': cfg.nerf.lr}]
+        if n.bg_net is not None:
+            groups.append({'params': n.bg_net.parameters(), 'lr': cfg.nerf.bg_lr})
+        self.opt = torch.optim.Adam(groups, betas=(0.9, 0.99), eps=1e-15)
         self.stub, self.bg = stub, torch.tensor([0.5, 0.5, 0.5])
 
     def step(self, data, noises):
@@ -135,7 +151,11 @@ class Composed:
             density_activation=n.opt.density_activation, density_prior=n.density_prior_type, albedo_sigmoid=True, perturb=True, noises=noises,
             counter=counter)
         image_fg, ws4 = image.reshape(1, H, W, -1), ws.reshape(1, H, W, 1)
-        image = image_fg + (1 - ws4) * self.bg.to(image_fg).expand_as(image_fg)
+        if n.bg_mode == 'nerf':
+            image_bg = torch.sigmoid(n.bg_net(torch_freq_encode(rays_d, n.encoder_bg.degree))).reshape_as(image_fg)
+        else:
+            image_bg = self.bg.to(image_fg).expand_as(image_fg)
+        image = image_fg + (1 - ws4) * image_bg
         sd_inputs = image.permute(0, 3, 1, 2).contiguous()
         loss = self.stub(sd_inputs)['diffusion_loss'] * 1.0 + torch_sparsity(ws4)
         self.opt.zero_grad()
@@ -275,18 +295,19 @@ def main():
     ap.add_argument("--guidance", action="store_true", help="at 512^2, also the native step with the real guidance object")
     ap.add_argument("--profile", action="store_true", help="torch launches per step for both forms (a pass of its own)")
     ap.add_argument("--fp16", action="store_true", help="the step under optim.fp16: the device-resident scaler against torch.amp.GradScaler")
+    ap.add_argument("--bg-mode", default="gray", choices=["gray", "nerf"], help="'nerf': the learned background in both forms")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_nerf_step needs a GPU: a CPU run says nothing about the step's time")
     print("== python tools/bench_nerf_step.py " + " ".join(sys.argv[1:]))
     torch.manual_seed(0)
-    cfg = make_cfg()
+    cfg = make_cfg(args.bg_mode)
     net = make_network(cfg)
     net.update_extra_state()
     opts, _ = net.get_optimizer(cfg.nerf)
-    print("network: bound %g, grid %d^3 x %d cascades, %d table rows; occupied cells %d; lambdas %s; stub guidance" % (
+    print("network: bound %g, grid %d^3 x %d cascades, %d table rows; occupied cells %d; lambdas %s; background %r; stub guidance" % (
         net.bound, net.grid_size, net.cascade, net.encoder.embeddings.shape[0],
-        int(torch.tensor([bin(v).count("1") for v in range(256)], device=DEV)[net.density_bitfield.long()].sum()), LAMBDAS))
+        int(torch.tensor([bin(v).count("1") for v in range(256)], device=DEV)[net.density_bitfield.long()].sum()), LAMBDAS, net.bg_mode))
     if args.fp16:
         return fp16_rows(args, cfg, net)
     print("size   form                 step ms min / median / max      M samples (each form's own count, last step of the run)")
