@@ -9,10 +9,6 @@ import torch
 from . import _lib
 
 
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 class _Assemble(torch.autograd.Function):
     """`mlp`: the deformation network's packed output [N, ld] = [warp 3 | scaling 3 | rest]: its column blocks are read in place and their
     gradient comes back as ONE [N, ld] tensor (zeros in the unused columns) -- no slice copies, no slice-backward zero-fill + copy pairs."""
@@ -33,7 +29,7 @@ class _Assemble(torch.autograd.Function):
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_gaussian_assemble_forward_ld(n, nt, p(positions), p(mlp), init_offset, p(log_scales),
                                                                ctypes.c_void_p(mlp.data_ptr() + 12), ld, init_scale, p(quaternions), p(h), p(pos),
-                                                               p(scl), p(qn), p(col), p(op), _st(h)), "dwg_gaussian_assemble_forward_ld")
+                                                               p(scl), p(qn), p(col), p(op), _lib.stream(h)), "dwg_gaussian_assemble_forward_ld")
         ctx.save_for_backward(log_scales, quaternions, h)
         ctx.k = (n, nt, ld, init_offset, init_scale)
         return pos, scl, qn, col, op
@@ -51,7 +47,7 @@ class _Assemble(torch.autograd.Function):
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_gaussian_assemble_backward_ld(n, nt, io, p(log_scales), isc, p(quaternions), p(h), p(g_pos), p(g_scl),
                                                                 p(g_qn), p(g_col), p(g_op), p(d_p), p(d_mlp), p(d_ls),
-                                                                ctypes.c_void_p(d_mlp.data_ptr() + 12), ld, ld - 6, p(d_q), p(d_h), _st(h)),
+                                                                ctypes.c_void_p(d_mlp.data_ptr() + 12), ld, ld - 6, p(d_q), p(d_h), _lib.stream(h)),
                    "dwg_gaussian_assemble_backward_ld")
         return d_p, d_mlp, d_ls, d_q, d_h, None, None
 
@@ -91,7 +87,7 @@ class _CopySegments(torch.autograd.Function):
             raise ValueError("copy_segments: at most 12 blocks per launch")
         arr = (_lib.SegmentC * max(len(segs), 1))(*[_lib.SegmentC(d, s_, c) for d, s_, c in segs])
         add, div = (float(bound), 2.0 * float(bound)) if bound is not None else (0.0, 0.0)
-        _lib.check(_lib.lib().dwg_copy_segments(len(segs), ctypes.cast(arr, ctypes.c_void_p), add, div, _st(parts[0])), "dwg_copy_segments")
+        _lib.check(_lib.lib().dwg_copy_segments(len(segs), arr, add, div, _lib.stream(parts[0])), "dwg_copy_segments")
         ctx.bound, ctx.sizes, ctx.rows = bound, tuple(sizes), [int(t.shape[0]) for t in parts]
         return tuple(outs)
 

@@ -14,7 +14,6 @@ indices read from device memory -- no host work or sync per frame, and a capture
 Frame indices behave like the reference's list: a negative index counts from the end, an index outside [-T, T) raises IndexError.  That
 check is made on the host for Python ints; a device index tensor (GraphedAnimation's static input) is used as it is: the kernel wraps
 negative values once and clamps the rest for memory safety.  No CPU fallback: image and alpha must be fp32 CUDA tensors."""
-import ctypes
 import operator
 import os
 
@@ -24,10 +23,6 @@ import torch
 from . import _lib
 
 _STAGE_BYTES = 64 << 20          # pinned staging per upload chunk
-
-
-def _st(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _cuda(device):
@@ -198,13 +193,6 @@ class VideoBackground:
         return out[0] if image.dtype == torch.float32 else out[0].to(image.dtype)
 
 
-def _check(name, t, shape):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise RuntimeError("%s must be a float32 CUDA tensor" % name)
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-
-
 def _launch_forward(fg, alpha, background, idx, image, image_bg):
     ref = image_bg if fg is None else fg
     F, H, W = int(ref.shape[0]), int(ref.shape[1]), int(ref.shape[2])
@@ -215,7 +203,7 @@ def _launch_forward(fg, alpha, background, idx, image, image_bg):
         sf, sp, sc = _planar_strides(fg, H, W)
     rc = _lib.lib().dwg_video_composite_forward(F, H, W, _lib.ptr(fg), _lib.ptr(alpha), sf, sp, sc, _lib.ptr(store), background.frame_count,
                                                 background.frame_height, background.frame_width, _lib.ptr(idx), _lib.ptr(image),
-                                                _lib.ptr(image_bg), _st(device))
+                                                _lib.ptr(image_bg), _lib.stream(device))
     _lib.check(rc, "dwg_video_composite_forward")
 
 
@@ -246,7 +234,7 @@ class _VideoComposite(torch.autograd.Function):
             store = bg.frames(d_out.device)
             rc = _lib.lib().dwg_video_composite_backward(F, H, W, _lib.ptr(d_out), st[0], st[1], st[2], _lib.ptr(store), bg.frame_count,
                                                          bg.frame_height, bg.frame_width, _lib.ptr(idx), _lib.ptr(d_alpha),
-                                                         _st(d_out.device))
+                                                         _lib.stream(d_out.device))
             _lib.check(rc, "dwg_video_composite_backward")
         return (d_out if ctx.needs_input_grad[0] else None), d_alpha, None, None
 
@@ -260,8 +248,8 @@ def video_composite(image: torch.Tensor, alpha: torch.Tensor, background: VideoB
     if image.dim() != 4 or image.shape[3] != 3:
         raise RuntimeError("image must be [F, H, W, 3], got %s" % (tuple(image.shape),))
     F, H, W = (int(s) for s in image.shape[:3])
-    _check("image", image, (F, H, W, 3))
-    _check("alpha", alpha, (F, H, W, 1))
+    _lib.check_tensor("image", image, shape=(F, H, W, 3), contiguous=False)
+    _lib.check_tensor("alpha", alpha, shape=(F, H, W, 1), contiguous=False)
     if _planar_strides(image, H, W) is None or not _dense(image):
         image = image.contiguous()
     alpha = alpha.contiguous()

@@ -15,7 +15,6 @@ Same names, arguments and error behaviour as the reference seam; what differs, d
     `PeopleScene` (`build_people_scene`): vertices [P,V,3] over one triangle topology.  Keypoints [P,K,3] / rows [P,128,4] give one image
     for all of them, person 0 drawn first; `export_depth` / `export_normal_raw` cast against the concatenated mesh.
 There is no CPU fallback: CPU tensors raise."""
-import ctypes
 from typing import Optional
 
 import numpy as np
@@ -23,13 +22,9 @@ import torch
 
 from . import _lib
 
-N_KEYPOINTS = 128                 # body 18 + hands 2 x 21 + face 51 + 17 (smpl_condition.py:22)
-MAX_PEOPLE = 16                   # DWG_COND_MAX_PEOPLE
-DRAW_BODY, DRAW_HAND, DRAW_FACE, FLIP_LR = 1, 2, 4, 8
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+N_KEYPOINTS = _lib.CONSTANTS["DWG_COND_KEYPOINTS"]      # body 18 + hands 2 x 21 + face 51 + 17 (smpl_condition.py:22)
+MAX_PEOPLE = _lib.CONSTANTS["DWG_COND_MAX_PEOPLE"]
+DRAW_BODY, DRAW_HAND, DRAW_FACE, FLIP_LR = (_lib.CONSTANTS["DWG_COND_" + n] for n in ("DRAW_BODY", "DRAW_HAND", "DRAW_FACE", "FLIP_LR"))
 
 
 class RayCastingScene:
@@ -207,7 +202,7 @@ class SMPL2Condition:
             p(ray_casting_scene.vertices) if cull else None, int(ray_casting_scene.triangles.shape[0]) if cull else 0,
             p(ray_casting_scene.triangles) if cull else None, p(oc.groups(K, dev)) if cull else None,
             (float('inf') if oc.ignore_body_self_occlusion else oc.thres_body) if cull else 0.0, oc.thres_hand if cull else 0.0, oc.thres_face if cull else 0.0, 1 if cull else 0,
-            p(rows), _stream(dev)), "dwg_condition_keypoints")
+            p(rows), _lib.stream(dev)), "dwg_condition_keypoints")
         return rows
 
     def people_rows(self, keypoints: torch.Tensor, people_scene: Optional[PeopleScene], extrinsic: torch.Tensor,
@@ -244,7 +239,7 @@ class SMPL2Condition:
             int(people_scene.triangles.shape[0]) if cull else 0, p(people_scene.triangles) if cull else None,
             p(oc.groups(K, dev)) if cull else None, oc.thres_body if cull else 0.0, oc.thres_hand if cull else 0.0,
             oc.thres_face if cull else 0.0, 1 if (cull and oc.ignore_body_self_occlusion) else 0, 1 if cull else 0, p(rows), p(hit),
-            _stream(dev)), "dwg_condition_keypoints_people")
+            _lib.stream(dev)), "dwg_condition_keypoints_people")
         return rows, hit
 
     def draw(self, rows: torch.Tensor, height: int, width: int, out_u8: bool = True, out_chw: bool = False):
@@ -272,10 +267,10 @@ class SMPL2Condition:
         p = _lib.ptr
         if people:
             _lib.check(L.dwg_condition_draw_people(P, height, width, p(rows), flags, p(u8) if out_u8 else None, p(chw) if out_chw else None,
-                                                   p(self._ws[key]), _stream(dev)), "dwg_condition_draw_people")
+                                                   p(self._ws[key]), _lib.stream(dev)), "dwg_condition_draw_people")
         else:
             _lib.check(L.dwg_condition_draw(height, width, p(rows), flags, p(u8) if out_u8 else None, p(chw) if out_chw else None,
-                                            p(self._ws[key]), _stream(dev)), "dwg_condition_draw")
+                                            p(self._ws[key]), _lib.stream(dev)), "dwg_condition_draw")
         return u8, chw
 
     # -- the reference's methods -----------------------------------------------------------------------------------------
@@ -316,7 +311,7 @@ class SMPL2Condition:
         n = torch.empty(height, width, 3, dtype=torch.float32, device=dev) if normals else None
         p = _lib.ptr
         _lib.check(L.dwg_depthmap_cast(height, width, p(ext), p(intr), V, p(verts) if F else None, F, p(tris) if F else None, p(t), p(n),
-                                       1 if minmax else 0, p(ws), ws.numel(), _stream(dev)), "dwg_depthmap_cast")
+                                       1 if minmax else 0, p(ws), ws.numel(), _lib.stream(dev)), "dwg_depthmap_cast")
         return t, n, ws
 
     def depth_image(self, t_hit: torch.Tensor, out_u8: bool = True, out_chw: bool = False, _ws=None):
@@ -336,7 +331,7 @@ class SMPL2Condition:
         u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if out_u8 else None
         chw = torch.empty(1, 3, H, W, dtype=torch.float32, device=dev) if out_chw else None
         p = _lib.ptr
-        _lib.check(_lib.lib().dwg_depthmap_image(H, W, p(t_hit), 0 if _ws is None else 1, p(u8), p(chw), p(ws), ws.numel(), _stream(dev)),
+        _lib.check(_lib.lib().dwg_depthmap_image(H, W, p(t_hit), 0 if _ws is None else 1, p(u8), p(chw), p(ws), ws.numel(), _lib.stream(dev)),
                    "dwg_depthmap_image")
         return u8, chw
 

@@ -5,33 +5,11 @@ import torch
 
 from . import _lib
 
-F32, BF16, F16, F32X = 0, 1, 2, 3        # DWG_DTYPE_* (include/dwg_types.h); F32X tensors are int32-typed (xfmt.py)
-ACT = {None: 0, "none": 0, "relu": 1, "leaky_relu": 2, "silu": 3, "gelu": 4, "sigmoid": 5, "geglu_pair": 6}
-
-
-class GemmDesc(ctypes.Structure):
-    _fields_ = [
-        ("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-        ("residual", ctypes.c_void_p),
-        ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
-        ("a_row_stride", ctypes.c_int64), ("a_k_stride", ctypes.c_int64), ("b_row_stride", ctypes.c_int64),
-        ("b_k_stride", ctypes.c_int64), ("ldc", ctypes.c_int64), ("ldr", ctypes.c_int64),
-        ("batch1", ctypes.c_int32), ("batch2", ctypes.c_int32),
-        ("a_batch1_stride", ctypes.c_int64), ("a_batch2_stride", ctypes.c_int64), ("b_batch1_stride", ctypes.c_int64),
-        ("b_batch2_stride", ctypes.c_int64), ("c_batch1_stride", ctypes.c_int64), ("c_batch2_stride", ctypes.c_int64),
-        ("r_batch1_stride", ctypes.c_int64), ("r_batch2_stride", ctypes.c_int64),
-        ("dtype", ctypes.c_int32), ("out_dtype", ctypes.c_int32), ("residual_dtype", ctypes.c_int32),
-        ("act", ctypes.c_int32), ("alpha", ctypes.c_float), ("bias_per_row", ctypes.c_int32),
-        ("splitk", ctypes.c_int32), ("accumulate", ctypes.c_int32),
-        ("conv_enabled", ctypes.c_int32), ("conv_cin", ctypes.c_int32), ("conv_hin", ctypes.c_int32),
-        ("conv_win", ctypes.c_int32), ("conv_hout", ctypes.c_int32), ("conv_wout", ctypes.c_int32),
-        ("conv_kh", ctypes.c_int32), ("conv_kw", ctypes.c_int32), ("conv_stride", ctypes.c_int32),
-        ("conv_pad_t", ctypes.c_int32), ("conv_pad_l", ctypes.c_int32), ("conv_in_dilation", ctypes.c_int32),
-        ("conv_in_upsample", ctypes.c_int32), ("A2", ctypes.c_void_p), ("conv_cin1", ctypes.c_int32),
-        ("bias_row_div", ctypes.c_int32), ("bias_ld", ctypes.c_int64),
-        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
-        ("name", ctypes.c_char_p), ("plan_m", ctypes.c_int32),
-    ]
+_C = _lib.CONSTANTS
+F32, BF16, F16, F32X = (_C["DWG_DTYPE_" + n] for n in ("F32", "BF16", "F16", "F32X"))        # F32X tensors are int32-typed (xfmt.py)
+ACT = {n: _C["DWG_ACT_" + n.upper()] for n in ("none", "relu", "leaky_relu", "silu", "gelu", "sigmoid", "geglu_pair")}
+ACT[None] = ACT["none"]
+GemmDesc = _lib.STRUCTS["dwg_gemm_desc"]
 
 
 def _dt(t):
@@ -44,10 +22,6 @@ def _dt(t):
     if t.dtype == torch.int32:
         return F32X
     raise TypeError("dwg gemm supports float32, bfloat16, float16 and f32x (int32-typed, xfmt.py) tensors, got %s" % t.dtype)
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def gemm_raw(A, B, C, M, N, K, a_strides, b_strides, ldc, bias=None, residual=None, ldr=0, act=None, alpha=1.0,
@@ -91,7 +65,7 @@ def gemm_raw(A, B, C, M, N, K, a_strides, b_strides, ldc, bias=None, residual=No
     d.plan_m = plan_m
     if not run:
         return d
-    _lib.check(_lib.lib().dwg_gemm(ctypes.byref(d), _stream(A)), "dwg_gemm")
+    _lib.check(_lib.lib().dwg_gemm(ctypes.byref(d), _lib.stream(A)), "dwg_gemm")
     return C
 
 

@@ -59,7 +59,7 @@ class FlatGradScaler:
         return int(self._growth_tracker) if self._enabled else 0
 
     def state_ptr(self):
-        return ctypes.c_void_p(self._state.data_ptr())
+        return ctypes.cast(self._state.data_ptr(), ctypes.POINTER(_lib.ScalerStateC))        # a device address: never dereferenced here
 
     # -- the loop ------------------------------------------------------------------------------------------------------------------------
     def scale(self, loss):
@@ -91,7 +91,7 @@ class FlatGradScaler:
                 self._scale.fill_(float(new_scale))
             self._found_inf.zero_()
             return
-        st = ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+        st = _lib.stream(self._device)
         _lib.check(_lib.lib().dwg_scaler_update(self.state_ptr(), self._growth_factor, self._backoff_factor, self._growth_interval, st),
                    "dwg_scaler_update")
 

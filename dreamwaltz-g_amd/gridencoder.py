@@ -19,10 +19,6 @@ _gridtype_to_id = {'hash': 0, 'tiled': 1}
 _interp_to_id = {'linear': 0, 'smoothstep': 1}
 
 
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _need_cuda(t):
     if not t.is_cuda:
         raise RuntimeError("dreamwaltz_g_amd grid encoder runs on the GPU only (HIP kernels)")
@@ -35,7 +31,7 @@ def grid_encode_forward(inputs, embeddings, offsets, outputs, B, D, C, L, S, H, 
     p = _lib.ptr
     _lib.check(_lib.lib().dwg_grid_encode_forward(p(inputs), p(embeddings), p(offsets), p(outputs), B, D, C, L,
                                                   ctypes.c_float(S), H, p(dy_dx), gridtype, int(bool(align_corners)),
-                                                  interp, out_layout, _st(inputs)), "dwg_grid_encode_forward")
+                                                  interp, out_layout, _lib.stream(inputs)), "dwg_grid_encode_forward")
 
 
 _host_offsets = []          # [(offsets tensor kept alive, its version, ctypes array)]
@@ -116,12 +112,12 @@ def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, 
                                                              C, L, ctypes.c_float(S), H, p(dy_dx), p(grad_inputs), gridtype,
                                                              int(bool(align_corners)), interp, grad_layout,
                                                              ctypes.cast(ho, ctypes.c_void_p), p(slab_workspace), slab_workspace.numel(),
-                                                             int(bool(accumulate)), _st(inputs)), "dwg_grid_encode_backward_slabs")
+                                                             int(bool(accumulate)), _lib.stream(inputs)), "dwg_grid_encode_backward_slabs")
         return
     _lib.check(_lib.lib().dwg_grid_encode_backward(p(grad), p(inputs), p(embeddings), p(offsets), p(grad_embeddings), B, D,
                                                    C, L, ctypes.c_float(S), H, p(dy_dx), p(grad_inputs), gridtype,
                                                    int(bool(align_corners)), interp, grad_layout,
-                                                   ctypes.cast(ho, ctypes.c_void_p), _st(inputs)),
+                                                   ctypes.cast(ho, ctypes.c_void_p), _lib.stream(inputs)),
                "dwg_grid_encode_backward")
 
 

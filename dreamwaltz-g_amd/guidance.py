@@ -14,7 +14,6 @@ Attributes other code reads (basic.py:334-335,453): scheduler.scale_model_input,
 pipe.unet.config.sample_size.  Device RNG draw order per call is the reference's (checklist Q12): VAE posterior noise -> timestep ->
 latent noise.  Test-only keyword extensions: noise=, posterior_noise= (fixed draws for parity tests).
 """
-import ctypes
 import types
 from typing import Dict, List, Optional, Union
 
@@ -39,17 +38,14 @@ class SpecifyGradient(torch.autograd.Function):
         return gt_grad * grad_scale, None
 
 
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _fused_ok(*ts):
     """The one-launch forms of the latent algebra (csrc/sds.hip, include/dwg_sds.h) take fp32 CUDA tensors; CPU and non-fp32
     tensors keep the element-wise torch statements."""
     return all(t is not None and t.is_cuda and t.dtype == torch.float32 for t in ts)
 
 
-_WEIGHT_CODE = {None: 0, 'sjc': 0, 'dreamfusion': 1, 'latent-nerf': 2, 'ism': 3}
+_WEIGHT_CODE = {k: _lib.CONSTANTS["DWG_SDS_WEIGHT_" + n] for k, n in
+                {None: "NONE", 'sjc': "NONE", 'dreamfusion': "DREAMFUSION", 'latent-nerf': "LATENT_NERF", 'ism': "ISM"}.items()}
 
 
 class _PosteriorSample(torch.autograd.Function):
@@ -61,7 +57,7 @@ class _PosteriorSample(torch.autograd.Function):
         m, e = moments.contiguous(), noise.contiguous()
         V, n = m.shape[0], m[0].numel() // 2
         out = torch.empty_like(e)
-        _lib.check(_lib.lib().dwg_sds_posterior_sample(V, n, _lib.ptr(m), _lib.ptr(e), float(scale), _lib.ptr(out), _st(m)), "dwg_sds_posterior_sample")
+        _lib.check(_lib.lib().dwg_sds_posterior_sample(V, n, _lib.ptr(m), _lib.ptr(e), float(scale), _lib.ptr(out), _lib.stream(m)), "dwg_sds_posterior_sample")
         ctx.save_for_backward(m, e)
         ctx.scale = float(scale)
         return out
@@ -72,7 +68,7 @@ class _PosteriorSample(torch.autograd.Function):
         g = g.contiguous().float()
         gm = torch.empty_like(m)
         _lib.check(_lib.lib().dwg_sds_posterior_sample_backward(m.shape[0], m[0].numel() // 2, _lib.ptr(m), _lib.ptr(e), ctx.scale, _lib.ptr(g),
-                                                                _lib.ptr(gm), _st(m)), "dwg_sds_posterior_sample_backward")
+                                                                _lib.ptr(gm), _lib.stream(m)), "dwg_sds_posterior_sample_backward")
         return gm, None, None
 
 
@@ -223,7 +219,7 @@ class ControlNetScoreDistillation:
             x, e = latents.contiguous(), noise.contiguous()
             out = torch.empty_like(x)
             _lib.check(_lib.lib().dwg_sds_add_noise(x.shape[0], x[0].numel(), _lib.ptr(x), _lib.ptr(e), _lib.ptr(self.alphas_cumprod),
-                                                    int(self.alphas_cumprod.numel()), _lib.ptr(timestep.contiguous()), _lib.ptr(out), _st(x)),
+                                                    int(self.alphas_cumprod.numel()), _lib.ptr(timestep.contiguous()), _lib.ptr(out), _lib.stream(x)),
                        "dwg_sds_add_noise")
             return out
         a = self.alphas_cumprod[timestep].reshape(-1, 1, 1, 1)
@@ -390,7 +386,7 @@ class ControlNetScoreDistillation:
             _lib.check(_lib.lib().dwg_sds_gradient(noise.shape[0], noise[0].numel(), _lib.ptr(noise_pred), _lib.ptr(noise), _lib.ptr(self.alphas_cumprod),
                                                    int(self.alphas_cumprod.numel()), _lib.ptr(self.timestep.contiguous()), float(self.guidance_scale),
                                                    _WEIGHT_CODE[self.weight_type], int(bool(self.cfg.grad_latent_nan_to_num)), _lib.ptr(gradients),
-                                                   _lib.ptr(combined), _st(noise)), "dwg_sds_gradient")
+                                                   _lib.ptr(combined), _lib.stream(noise)), "dwg_sds_gradient")
             return gradients, combined, text_embeddings
         noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
         noise_pred = noise_pred_uncond + self.guidance_scale * (noise_pred_text - noise_pred_uncond)

@@ -12,22 +12,16 @@ What differs from the reference, deliberately:
   * only window_size 11 and fp32;
   * the filter and the SSIM map are accumulated in fp64; the results are fp32 scalars.
 There is no CPU fallback: CPU tensors raise."""
-import ctypes
 
 import torch
 
 from . import _lib
 
-WINDOW_SIZE = 11
-MAX_SIZE, MAX_PLANES = 32768, 65535                     # DWG_IMAGE_LOSS_MAX_SIZE, DWG_IMAGE_LOSS_MAX_PLANES
+WINDOW_SIZE, MAX_SIZE, MAX_PLANES = (_lib.CONSTANTS["DWG_IMAGE_LOSS_" + n] for n in ("WINDOW", "MAX_SIZE", "MAX_PLANES"))
 _ws = {}
 # what the forward kept for a backward: tests read it, nothing else does.  `maps_allocations` counts the derivative-map tensors ever
 # allocated, `last_maps_bytes` is the size of the one the LAST forward allocated (0: it stored none)
 stats = {"forward_calls": 0, "maps_allocations": 0, "last_maps_bytes": 0}
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _workspace(device, B, C, H, W):
@@ -60,7 +54,7 @@ class _ImageLossFn(torch.autograd.Function):
         stats["last_maps_bytes"] = 0 if maps is None else maps.numel() * 4
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_image_loss_forward(B, C, H, W, WINDOW_SIZE, float(lambda_dssim), *_image_args(x), *_image_args(y), p(scalars),
-                                                     p(per_item), p(maps), p(ws), ws.numel(), _stream(dev)), "dwg_image_loss_forward")
+                                                     p(per_item), p(maps), p(ws), ws.numel(), _lib.stream(dev)), "dwg_image_loss_forward")
         ctx.kind, ctx.lambda_dssim, ctx.keep = kind, float(lambda_dssim), keep
         if keep:
             ctx.save_for_backward(x, y, maps)
@@ -84,7 +78,7 @@ class _ImageLossFn(torch.autograd.Function):
         grad_x = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_image_loss_backward(B, C, H, W, WINDOW_SIZE, coef_ssim, coef_l1, *_image_args(x), *_image_args(y), p(maps), p(g),
-                                                      int(ctx.kind == 'ssim_batch'), p(grad_x), _stream(x.device)), "dwg_image_loss_backward")
+                                                      int(ctx.kind == 'ssim_batch'), p(grad_x), _lib.stream(x.device)), "dwg_image_loss_backward")
         return grad_x, None, None, None, None
 
 

@@ -7,15 +7,10 @@
   vertex_transform(...)                  transform_V on a vertex subset (mesh-bound Gaussians)
 csrc/lbs.hip through include/dwg_lbs.h; no CPU fallback.
 """
-import ctypes
 
 import torch
 
 from . import _lib
-
-
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 class _LbsBlend(torch.autograd.Function):
@@ -35,7 +30,7 @@ class _LbsBlend(torch.autograd.Function):
         T12 = torch.empty(N, 12, device=points.device) if grad_on else None
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_lbs_blend_forward(N, J, int(bool(normalize)), p(A), p(weights), p(points), p(quats),
-                                                    p(p_out), p(q_out), p(T12), _st(points)), "dwg_lbs_blend_forward")
+                                                    p(p_out), p(q_out), p(T12), _lib.stream(points)), "dwg_lbs_blend_forward")
         ctx.save_for_backward(T12, points, quats)
         ctx.has_q = quats is not None
         if quats is None:
@@ -54,7 +49,7 @@ class _LbsBlend(torch.autograd.Function):
             gq = torch.empty_like(quats)
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_lbs_blend_backward(N, p(T12), p(points), p(quats), p(g_p), p(g_q) if ctx.has_q else None,
-                                                     p(gp), p(gq), _st(points)), "dwg_lbs_blend_backward")
+                                                     p(gp), p(gq), _lib.stream(points)), "dwg_lbs_blend_backward")
         return None, None, gp, gq, None, None
 
 
@@ -84,7 +79,7 @@ def joint_chain(pose, joints, parents, transl=None, return_rot_mats=False, joint
     jd = None if joint_shape_dirs is None else joint_shape_dirs.contiguous().float()
     sc = None if shape_coeffs is None else shape_coeffs.reshape(-1).contiguous().float()
     _lib.check(_lib.lib().dwg_lbs_joint_chain(J, p(pose), p(joints), p(parents), p(transl), p(jd), p(sc),
-                                              0 if sc is None else sc.numel(), p(A), p(R), _st(pose)),
+                                              0 if sc is None else sc.numel(), p(A), p(R), _lib.stream(pose)),
                "dwg_lbs_joint_chain")
     return (A, R) if return_rot_mats else A
 
@@ -115,7 +110,7 @@ class _VertexTransformFn(torch.autograd.Function):
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_lbs_vertex_transform(
             Vp, J, 0 if sd is None else sd.shape[-1], 0 if pd is None else pd.shape[-1], p(x), p(A), p(w_sub), p(sd), p(sc), p(pd),
-            p(None if rot_mats is None else rot_mats.contiguous().float()), p(out), _st(x)), "dwg_lbs_vertex_transform")
+            p(None if rot_mats is None else rot_mats.contiguous().float()), p(out), _lib.stream(x)), "dwg_lbs_vertex_transform")
         ctx.save_for_backward(A, w_sub, sd, pose, parents, joint_shape_dirs)
         ctx.shape_shape = None if shape_coeffs is None else shape_coeffs.shape
         return out
@@ -136,7 +131,7 @@ class _VertexTransformFn(torch.autograd.Function):
         ws = torch.empty(int(_lib.lib().dwg_lbs_vertex_transform_backward_shape_workspace_floats(Vp)), device=A.device)     # one row of partial sums per workgroup
         _lib.check(_lib.lib().dwg_lbs_vertex_transform_backward_shape_ws(
             Vp, J, S, p(A), p(w_sub), p(sd), p(g_out.contiguous().float()), p(pose), p(parents), p(jdirs), p(scratch), p(g_shape), p(ws),
-            _st(A)), "dwg_lbs_vertex_transform_backward_shape_ws")
+            _lib.stream(A)), "dwg_lbs_vertex_transform_backward_shape_ws")
         return None, g_shape.reshape(ctx.shape_shape), None, None, None, None, None, None, None, None
 
 

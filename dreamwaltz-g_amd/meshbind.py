@@ -4,15 +4,10 @@ Mirrors MeshBindingGaussianModel.get_positions / get_scales_and_quaternions (/ro
 and compute_normal (/root/reference/core/utils/mesh.py:34-94): one forward launch produces canonical positions, observed
 positions, scales and quaternions; one backward launch produces the gradients of `_bary_coords` and `_scales`.
 """
-import ctypes
 
 import torch
 
 from . import _lib
-
-
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _need_cuda(*ts):
@@ -44,7 +39,7 @@ def vertex_normals(verts, triangles_i32, vf_offsets, vf_faces):
     vn = torch.empty(Vp, 3, device=verts.device)
     p = _lib.ptr
     _lib.check(_lib.lib().dwg_mesh_vertex_normals(Vp, Fp, p(verts), p(triangles_i32), p(vf_offsets), p(vf_faces), p(fn), p(vn),
-                                                  _st(verts)), "dwg_mesh_vertex_normals")
+                                                  _lib.stream(verts)), "dwg_mesh_vertex_normals")
     return vn
 
 
@@ -62,7 +57,7 @@ class _MeshBind(torch.autograd.Function):
         pos, scl, quat = torch.empty(M, 3, device=dev), torch.empty(M, 3, device=dev), torch.empty(M, 4, device=dev)
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_meshbind_forward(Fp, n_per_tri, p(bary_c), p(scales_c), p(vc), p(vo), p(vn), p(triangles_i32),
-                                                   p(pos_c), p(pos), p(scl), p(quat), _st(bary)), "dwg_meshbind_forward")
+                                                   p(pos_c), p(pos), p(scl), p(quat), _lib.stream(bary)), "dwg_meshbind_forward")
         ctx.save_for_backward(bary_c, scales_c, vc, vo, vn, triangles_i32)
         ctx.n_per_tri = n_per_tri
         ctx.bary_shape = bary.shape
@@ -81,7 +76,7 @@ class _MeshBind(torch.autograd.Function):
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_meshbind_backward(Fp, ctx.n_per_tri, p(bary_c), p(scales_c), p(vc), p(vo), p(vn), p(tri),
                                                     p(g_pos_c), p(cg(g_pos)), p(cg(g_scl)), p(cg(g_quat)), p(g_bary), p(g_sc),
-                                                    _st(bary_c)), "dwg_meshbind_backward")
+                                                    _lib.stream(bary_c)), "dwg_meshbind_backward")
         return g_bary.reshape(ctx.bary_shape), g_sc, None, None, None, None, None
 
 
@@ -108,7 +103,7 @@ class _MeshBindFull(torch.autograd.Function):
         pos, scl, quat = torch.empty(M, 3, device=dev), torch.empty(M, 3, device=dev), torch.empty(M, 4, device=dev)
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_meshbind_forward(Fp, n_per_tri, p(bary_c), p(scales_c), p(vc), p(vo), p(vn), p(triangles_i32),
-                                                   p(pos_c), p(pos), p(scl), p(quat), _st(bary)), "dwg_meshbind_forward")
+                                                   p(pos_c), p(pos), p(scl), p(quat), _lib.stream(bary)), "dwg_meshbind_forward")
         ctx.save_for_backward(bary_c, scales_c, vc, vo, vn, triangles_i32, vf_offsets, vf_faces)
         ctx.n_per_tri = n_per_tri
         ctx.bary_shape = bary.shape
@@ -129,7 +124,7 @@ class _MeshBindFull(torch.autograd.Function):
         want_v = ctx.needs_input_grad[3] or (vc is not None and ctx.needs_input_grad[2])
         if not want_v:
             _lib.check(L.dwg_meshbind_backward(Fp, ctx.n_per_tri, p(bary_c), p(scales_c), p(vc), p(vo), p(vn), p(tri), p(g_pos_c),
-                                               p(cg(g_pos)), p(cg(g_scl)), p(cg(g_quat)), p(g_bary), p(g_sc), _st(bary_c)),
+                                               p(cg(g_pos)), p(cg(g_scl)), p(cg(g_quat)), p(g_bary), p(g_sc), _lib.stream(bary_c)),
                        "dwg_meshbind_backward")
             return g_bary.reshape(ctx.bary_shape), g_sc, None, None, None, None, None, None
         # vertex gradients without float atomics: per-(Gaussian, corner) rows, then a per-vertex gather in incident-face order (the same bits
@@ -139,13 +134,13 @@ class _MeshBindFull(torch.autograd.Function):
         rows = torch.empty(Fp * ctx.n_per_tri * 27, device=vo.device)
         _lib.check(L.dwg_meshbind_backward_verts_gather(Vp, Fp, ctx.n_per_tri, p(bary_c), p(scales_c), p(vc), p(vo), p(vn), p(tri), p(vf_off),
                                                         p(vf_faces), p(g_pos_c), p(cg(g_pos)), p(cg(g_scl)), p(cg(g_quat)), p(g_bary), p(g_sc),
-                                                        p(rows), p(g_vc), p(g_vo), p(g_vn), _st(bary_c)), "dwg_meshbind_backward_verts_gather")
+                                                        p(rows), p(g_vc), p(g_vo), p(g_vn), _lib.stream(bary_c)), "dwg_meshbind_backward_verts_gather")
         if g_vc is None and vc is not None:
             g_vc = torch.zeros_like(vc)
         fn = torch.empty(max(Fp, 1), 3, device=vo.device)
         gs = torch.empty(Vp, 3, device=vo.device)
         _lib.check(L.dwg_mesh_vertex_normals_backward(Vp, Fp, p(vo), p(tri), p(vf_off), p(vf_faces), p(g_vn), p(fn), p(gs), p(g_vo),
-                                                      _st(bary_c)), "dwg_mesh_vertex_normals_backward")
+                                                      _lib.stream(bary_c)), "dwg_mesh_vertex_normals_backward")
         return g_bary.reshape(ctx.bary_shape), g_sc, g_vc, g_vo, None, None, None, None
 
 

@@ -20,10 +20,6 @@ from . import _lib, gemm
 PER_LAYER_BACKWARD = os.environ.get("DWG_MLP_BWD_PER_LAYER", "0") == "1"
 
 
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _inplace_allowed():
     from . import gridencoder
     return bool(gridencoder._INPLACE_OK[0]) and os.environ.get("DWG_MLP_GRAD_INPLACE", "1") != "0"
@@ -88,13 +84,13 @@ def _linear_backward(x, w, y, extra, act, dy, need_dx, zeros=None):
     colsum = torch.zeros(N, device=x.device) if zeros is None else zeros[0]
     p = _lib.ptr
     _lib.check(_lib.lib().dwg_act_backward_colsum(M, N, gemm.ACT[act], p(dy), p(y) if act else None,
-                                                  p(dz) if act else None, p(colsum), _st(x)), "dwg_act_backward_colsum")
+                                                  p(dz) if act else None, p(colsum), _lib.stream(x)), "dwg_act_backward_colsum")
     dw = torch.zeros_like(w) if zeros is None else zeros[1]
     # dW[:, :Kx] = dz^T x   (contraction over the M rows of two row-major operands)
     if N <= 64 and Kx <= 64:
         L = _lib.lib()
         ws = torch.empty(L.dwg_mlp_wgrad_workspace_floats(M), device=x.device, dtype=torch.float32)
-        _lib.check(L.dwg_mlp_wgrad(M, N, Kx, p(dz), N, p(x), Kx, p(dw), w.shape[1], p(ws), _st(x)), "dwg_mlp_wgrad")
+        _lib.check(L.dwg_mlp_wgrad(M, N, Kx, p(dz), N, p(x), Kx, p(dw), w.shape[1], p(ws), _lib.stream(x)), "dwg_mlp_wgrad")
     else:
         gemm.gemm_raw(dz, x, dw, N, Kx, M, (1, N), (1, Kx), w.shape[1], splitk=_splitk(M), name="mlp_wgrad")
     if extra is not None:
@@ -135,7 +131,7 @@ class _MlpChain(torch.autograd.Function):
         _lib.check(L.dwg_mlp_chain_forward(M, Kx, _lib.ptr(x), Kx, nl, vp(*[w.data_ptr() for w in ws]), i32(*[int(w.stride(0)) for w in ws]),
                                            vp(*[pv(b) for b in biases]), i32(*widths), i32(*[gemm.ACT[a] for a in acts]),
                                            vp(*[pv(h) for h in hidden] + [None]), _lib.ptr(out), widths[-1],
-                                           _lib.ptr(e) if e is not None else None, int(e.numel()) if e is not None else 0, _st(x)),
+                                           _lib.ptr(e) if e is not None else None, int(e.numel()) if e is not None else 0, _lib.stream(x)),
                    "dwg_mlp_chain_forward")
         ctx.acts, ctx.nl = acts, nl
         ctx.has_b = [b is not None for b in bs]
@@ -192,7 +188,7 @@ class _MlpChain(torch.autograd.Function):
                 i32(*[int(w.shape[0]) for w in ws]), i32(*[gemm.ACT[a] for a in ctx.acts]), vp(*[h.data_ptr() for h in hidden] + [None]),
                 _lib.ptr(out), int(out.shape[1]), _lib.ptr(dy), int(dy.shape[1]), _lib.ptr(dx) if need_dx else None, Kx,
                 vp(*[d.data_ptr() for d in dws]), i32(*[int(d.stride(0)) for d in dws]), vp(*dbp), i32(*acc),
-                _lib.ptr(e) if e is not None else None, int(e.numel()) if e is not None else 0, _lib.ptr(wsp), _st(x)), "dwg_mlp_chain_backward")
+                _lib.ptr(e) if e is not None else None, int(e.numel()) if e is not None else 0, _lib.ptr(wsp), _lib.stream(x)), "dwg_mlp_chain_backward")
             for l, w in enumerate(ws):
                 if wflat[l] is not None:
                     wflat[l].touch(ctx.params[l][0])        # autograd never sees this gradient: record the participation for the optimizer
@@ -274,7 +270,7 @@ class _PackRows(torch.autograd.Function):
             bc = b.contiguous().float(); keep.append(bc)
             segs.append(_lib.SegmentC(B.data_ptr() + 4 * ob, bc.data_ptr(), bc.numel())); ob += bc.numel()
         arr = (_lib.SegmentC * len(segs))(*segs)
-        _lib.check(_lib.lib().dwg_copy_segments(len(segs), ctypes.cast(arr, ctypes.c_void_p), 0.0, 0.0, _st(W)), "dwg_copy_segments")
+        _lib.check(_lib.lib().dwg_copy_segments(len(segs), arr, 0.0, 0.0, _lib.stream(W)), "dwg_copy_segments")
         ctx.pieces, ctx.n, ctx.inplace_ok = pieces, n, _inplace_allowed()
         return W, B
 
@@ -300,7 +296,7 @@ class _PackRows(torch.autograd.Function):
                 ob += cnt
         if segs:
             arr = (_lib.SegmentC * len(segs))(*segs)
-            _lib.check(_lib.lib().dwg_add_segments(len(segs), ctypes.cast(arr, ctypes.c_void_p), _st(gW if gW is not None else gB)), "dwg_add_segments")
+            _lib.check(_lib.lib().dwg_add_segments(len(segs), arr, _lib.stream(gW if gW is not None else gB)), "dwg_add_segments")
             for flat, p in touched:
                 flat.touch(p)
         return (None,) + tuple(out)

@@ -23,24 +23,7 @@ from . import _lib
 
 ACTIVATIONS = {'exp': 0, 'softplus': 1, 'scaling': 2}
 PRIORS = {'none': 0, 'gaussian': 1, 'sqrt': 2}
-MAX_LAYERS, MAX_HIDDEN, MAX_OUT, MAX_LEVELS = 4, 64, 16, 32
-
-
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _check(name, t, dtype, numel=None):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError("%s must be a tensor, got %s" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA tensor" % name)
-    if not t.is_contiguous():
-        raise RuntimeError("%s must be a contiguous tensor" % name)
-    if t.dtype != dtype:
-        raise RuntimeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if numel is not None and t.numel() != numel:
-        raise RuntimeError("%s has %d elements, expected %d" % (name, t.numel(), numel))
+MAX_LAYERS, MAX_HIDDEN, MAX_OUT, MAX_LEVELS = _lib.CONSTANTS["DWG_NERF_MAX_LAYERS"], 64, 16, 32
 
 
 def _autocast_dtype():
@@ -118,18 +101,18 @@ class FieldSpec:
         return d
 
     def check(self, x, embeddings, sigma_scale, wb):
-        _check("x", x, torch.float32)
+        _lib.check_tensor("x", x, torch.float32)
         if x.dim() != 2 or x.shape[1] != 3:
             raise RuntimeError("x must be [M, 3], got %s" % (tuple(x.shape),))
-        _check("embeddings", embeddings, torch.float32)
+        _lib.check_tensor("embeddings", embeddings, torch.float32)
         if embeddings.dim() != 2 or embeddings.shape[1] != 2:
             raise RuntimeError("embeddings must be [entries, 2] (level_dim 2), got %s" % (tuple(embeddings.shape),))
-        _check("offsets", self.offsets, torch.int32, self.L + 1)
+        _lib.check_tensor("offsets", self.offsets, torch.int32, numel=self.L + 1)
         if not 1 <= self.L <= MAX_LEVELS:
             raise RuntimeError("the fused field takes 1..%d levels, got %d" % (MAX_LEVELS, self.L))
         if int(self.host_offsets[self.L]) != embeddings.shape[0]:
             raise RuntimeError("embeddings has %d entries, offsets say %d" % (embeddings.shape[0], int(self.host_offsets[self.L])))
-        _check("sigma_scale", sigma_scale, torch.float32, 1)
+        _lib.check_tensor("sigma_scale", sigma_scale, torch.float32, numel=1)
         if not 1 <= self.num_layers <= MAX_LAYERS:
             raise RuntimeError("sigma_net must have 1..%d layers, got %d" % (MAX_LAYERS, self.num_layers))
         if self.num_layers > 1 and not 1 <= self.hidden <= MAX_HIDDEN:
@@ -139,8 +122,8 @@ class FieldSpec:
         for l in range(self.num_layers):
             k = 2 * self.L if l == 0 else self.hidden
             n = self.out_dim if l == self.num_layers - 1 else self.hidden
-            _check("sigma_net.net[%d].weight" % l, wb[2 * l], torch.float32, n * k)
-            _check("sigma_net.net[%d].bias" % l, wb[2 * l + 1], torch.float32, n)
+            _lib.check_tensor("sigma_net.net[%d].weight" % l, wb[2 * l], torch.float32, numel=n * k)
+            _lib.check_tensor("sigma_net.net[%d].bias" % l, wb[2 * l + 1], torch.float32, numel=n)
 
 
 def field_forward(spec, embeddings, sigma_scale, wb, x):
@@ -149,7 +132,7 @@ def field_forward(spec, embeddings, sigma_scale, wb, x):
     sigma = torch.empty(M, device=x.device, dtype=torch.float32)
     albedo = torch.empty(M, spec.out_dim - 1, device=x.device, dtype=torch.float16 if spec.precision else torch.float32)
     d = spec.desc(embeddings, sigma_scale, wb)
-    _lib.check(_lib.lib().dwg_nerf_field_forward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(sigma), _lib.ptr(albedo), _st(x)),
+    _lib.check(_lib.lib().dwg_nerf_field_forward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(sigma), _lib.ptr(albedo), _lib.stream(x)),
                "dwg_nerf_field_forward")
     return sigma, albedo
 
@@ -169,7 +152,7 @@ def field_backward(spec, embeddings, sigma_scale, wb, x, dsigma, dalbedo, g_emb,
     L, M = _lib.lib(), x.shape[0]
     nbytes = int(L.dwg_nerf_field_backward_workspace_bytes(ctypes.byref(d), M))
     ws = torch.empty(max(nbytes, 1), device=x.device, dtype=torch.uint8)
-    tail = (ctypes.byref(g), _lib.ptr(ws), nbytes, _st(x))
+    tail = (ctypes.byref(g), _lib.ptr(ws), nbytes, _lib.stream(x))
     if fd is None:
         _lib.check(L.dwg_nerf_field_backward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(dsigma), _lib.ptr(dalbedo), *tail), "dwg_nerf_field_backward")
     else:

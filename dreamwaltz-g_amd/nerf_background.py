@@ -21,26 +21,8 @@ from torch.autograd import Function
 from . import _lib
 from . import nerf
 
-MAX_DEGREE, MAX_LAYERS, HIDDEN, OUT_DIMS = 8, 3, (16, 32, 64), (3, 4)
-
-
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _check(name, t, shape, device=None):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError("%s must be a tensor, got %s" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA tensor" % name)
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    if not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous" % name)
-    if device is not None and t.device != device:
-        raise RuntimeError("%s is on %s, the directions on %s" % (name, t.device, device))
+MAX_DEGREE, MAX_LAYERS = _lib.CONSTANTS["DWG_NERF_BG_MAX_DEGREE"], _lib.CONSTANTS["DWG_NERF_BG_MAX_LAYERS"]
+HIDDEN, OUT_DIMS = (16, 32, 64), (3, 4)
 
 
 def _check_dirs(name, x):
@@ -48,7 +30,7 @@ def _check_dirs(name, x):
         raise RuntimeError("%s must not require grad: the frequency encoding is not differentiated (encoder_bg has no parameters)" % name)
     if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != 3:
         raise RuntimeError("%s must be a tensor [..., 3]" % name)
-    _check(name, x, None)
+    _lib.check_tensor(name, x)
     if x.numel() // 3 >= 1 << 31:
         raise RuntimeError("%s holds %d directions: fewer than 2^31" % (name, x.numel() // 3))
 
@@ -66,7 +48,7 @@ def freq_encode(x, degree=6):
     N = x.numel() // 3
     out = torch.empty(tuple(x.shape[:-1]) + (3 + 6 * degree,), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().dwg_nerf_freq_encode(N, _lib.ptr(x), degree, _lib.ptr(out), _st(x)), "dwg_nerf_freq_encode")
+        _lib.check(_lib.lib().dwg_nerf_freq_encode(N, _lib.ptr(x), degree, _lib.ptr(out), _lib.stream(x)), "dwg_nerf_freq_encode")
     return out
 
 
@@ -147,7 +129,7 @@ class _LearnedBackground(Function):
         if N:
             d = spec.desc(wb)
             with torch.cuda.device(dirs.device):
-                _lib.check(_lib.lib().dwg_nerf_bg_forward(N, _lib.ptr(dirs), ctypes.byref(d), _lib.ptr(out), _st(dirs)), "dwg_nerf_bg_forward")
+                _lib.check(_lib.lib().dwg_nerf_bg_forward(N, _lib.ptr(dirs), ctypes.byref(d), _lib.ptr(out), _lib.stream(dirs)), "dwg_nerf_bg_forward")
         ctx.spec, ctx.keep = spec, keep
         if keep:
             ctx.save_for_backward(dirs, *wb)
@@ -177,7 +159,7 @@ class _LearnedBackground(Function):
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dirs.device)
         with torch.cuda.device(dirs.device):
             _lib.check(L.dwg_nerf_bg_backward(N, _lib.ptr(dirs), _lib.ptr(d_out), ctypes.byref(d), ctypes.byref(g), _lib.ptr(ws), nbytes,
-                                              _st(dirs)), "dwg_nerf_bg_backward")
+                                              _lib.stream(dirs)), "dwg_nerf_bg_backward")
         return (None, None, None, *g_wb)
 
 
@@ -201,8 +183,8 @@ def learned_background(rays_d, encoder_bg, bg_net, sigmoid=True, precision=None)
         raise RuntimeError("learned_background does not take this background: %s" % reason)
     wb, widths = [], []
     for l, lin in enumerate(bg_net.net):
-        _check("bg_net.net[%d].weight" % l, lin.weight, (lin.out_features, lin.in_features), rays_d.device)
-        _check("bg_net.net[%d].bias" % l, lin.bias, (lin.out_features,), rays_d.device)
+        _lib.check_tensor("bg_net.net[%d].weight" % l, lin.weight, shape=(lin.out_features, lin.in_features), device=rays_d.device)
+        _lib.check_tensor("bg_net.net[%d].bias" % l, lin.bias, shape=(lin.out_features,), device=rays_d.device)
         wb += [lin.weight, lin.bias]
         widths.append((lin.out_features, lin.in_features))
     spec = _Spec(int(encoder_bg.degree), widths, sigmoid, precision)

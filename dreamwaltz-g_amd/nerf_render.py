@@ -30,8 +30,6 @@ from . import nerf
 from . import pointcloud
 from . import raymarch
 
-_st = nerf._st
-_check = pointcloud._dev_check
 
 
 SHADINGS = {'albedo': 0, 'normal': 1, 'textureless': 2, 'lambertian': 3}
@@ -57,23 +55,23 @@ def _check_render(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_s
         spec, emb, ss, wb = pointcloud.field_spec(*field)
     except ValueError as e:
         raise RuntimeError(str(e)) from None
-    _check("rays_o", rays_o, torch.float32, (None, 3))
+    _lib.check_tensor("rays_o", rays_o, torch.float32, (None, 3))
     N = rays_o.shape[0]
-    _check("rays_d", rays_d, torch.float32, (N, 3))
-    _check("nears", nears, torch.float32, (N,))
-    _check("fars", fars, torch.float32, (N,))
+    _lib.check_tensor("rays_d", rays_d, torch.float32, (N, 3))
+    _lib.check_tensor("nears", nears, torch.float32, (N,))
+    _lib.check_tensor("fars", fars, torch.float32, (N,))
     grid = _grid_shape(cascade, grid_size)
     if grid is None:
         raise RuntimeError("bad occupancy grid shape: cascade %r, grid_size %r (a power of two: a cell's Morton index must stay below "
                            "grid_size^3)" % (cascade, grid_size))
     C, H = grid
-    _check("density_bitfield", density_bitfield, torch.uint8, (C * H ** 3 // 8,))
+    _lib.check_tensor("density_bitfield", density_bitfield, torch.uint8, (C * H ** 3 // 8,))
     if int(max_steps) != max_steps or not 1 <= max_steps < 1 << 31:
         raise RuntimeError("max_steps must be an integer >= 1, got %r" % (max_steps,))
     others = []
     if SHADINGS[shading]:
         if light_d is not None:
-            _check("light_d", light_d, torch.float32, (3,))
+            _lib.check_tensor("light_d", light_d, torch.float32, (3,))
             others.append(("light_d", light_d))
         elif SHADINGS[shading] >= 2:
             raise RuntimeError("shading %r needs light_d" % shading)
@@ -122,7 +120,7 @@ def render_rays(rays_o, rays_d, nears, fars, density_bitfield, cascade, grid_siz
         head = (ctypes.byref(d), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(nears), _lib.ptr(fars), N, _lib.ptr(density_bitfield),
                 ctypes.c_float(bound), int(bool(contract)), ctypes.c_float(dt_gamma), int(max_steps), C, H, ctypes.c_float(T_thresh),
                 int(bool(binarize)))
-        tail = (_lib.ptr(weights_sum), _lib.ptr(depth), _lib.ptr(image), _lib.ptr(counts), int(max_workgroups), _st(rays_o))
+        tail = (_lib.ptr(weights_sum), _lib.ptr(depth), _lib.ptr(image), _lib.ptr(counts), int(max_workgroups), _lib.stream(rays_o))
         with torch.cuda.device(dev):
             if SHADINGS[shading]:
                 _lib.check(_lib.lib().dwg_nerf_render_shaded(*head, SHADINGS[shading], _lib.ptr(light_d), ctypes.c_float(ambient_ratio),
@@ -174,9 +172,9 @@ class _RenderRaysTrain(Function):
             if M:
                 d = spec.desc(embeddings, sigma_scale, wb)
                 _lib.check(L.dwg_nerf_field_forward_fd(ctypes.byref(d), _lib.ptr(xyzs), M, ctypes.c_float(st.eps), _lib.ptr(sigmas),
-                                                       _lib.ptr(albedo), _lib.ptr(sigma_fd), _st(rays_o)), "dwg_nerf_field_forward_fd")
+                                                       _lib.ptr(albedo), _lib.ptr(sigma_fd), _lib.stream(rays_o)), "dwg_nerf_field_forward_fd")
             rgbs = torch.empty(M, ch, dtype=torch.float32, device=dev)
-            _shade_train(L, st, sigma_fd, albedo, M, ch, rgbs, _st(rays_o))
+            _shade_train(L, st, sigma_fd, albedo, M, ch, rgbs, _lib.stream(rays_o))
         else:
             sigma_fd = None
             sigmas, albedo = nerf.field_forward(spec, embeddings, sigma_scale, wb, xyzs)
@@ -189,7 +187,7 @@ class _RenderRaysTrain(Function):
         live = torch.empty(N, dtype=torch.int32, device=dev)
         _lib.check(L.dwg_raymarch_composite_rays_train_forward_live(
             _lib.ptr(sigmas), _lib.ptr(rgbs), _lib.ptr(ts), _lib.ptr(rays), M, N, ch, ctypes.c_float(st.T_thresh), int(st.binarize),
-            _lib.ptr(weights), _lib.ptr(weights_sum), _lib.ptr(depth), _lib.ptr(image), _lib.ptr(live), _st(rays_o)),
+            _lib.ptr(weights), _lib.ptr(weights_sum), _lib.ptr(depth), _lib.ptr(image), _lib.ptr(live), _lib.stream(rays_o)),
             "dwg_raymarch_composite_rays_train_forward_live")
         del rgbs
         st.M, st.weights, st.sigmas = M, weights, sigmas if st.return_sigmas else None
@@ -202,7 +200,7 @@ class _RenderRaysTrain(Function):
         total = torch.zeros(1, dtype=torch.int32, device=dev)
         nbytes = int(L.dwg_nerf_train_workspace_bytes(N))
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _lib.check(L.dwg_nerf_train_compact_offsets(_lib.ptr(live), N, _lib.ptr(rays_live), _lib.ptr(total), _lib.ptr(ws), nbytes, _st(rays_o)),
+        _lib.check(L.dwg_nerf_train_compact_offsets(_lib.ptr(live), N, _lib.ptr(rays_live), _lib.ptr(total), _lib.ptr(ws), nbytes, _lib.stream(rays_o)),
                    "dwg_nerf_train_compact_offsets")
         M_live = int(total.item()) if N and M else 0
         st.M_live = M_live
@@ -224,10 +222,10 @@ class _RenderRaysTrain(Function):
             _lib.check(L.dwg_nerf_train_gather_live(
                 _lib.ptr(rays), _lib.ptr(rays_live), N, M, M_live, _lib.ptr(xyzs), _lib.ptr(xyzs_l), _lib.ptr(ts), _lib.ptr(ts_l),
                 _lib.ptr(sigmas), _lib.ptr(sigmas_l), _lib.ptr(albedo) if moved else None, _lib.ptr(albedo_l) if moved else None, ch,
-                int(spec.precision), _st(rays_o)), "dwg_nerf_train_gather_live")
+                int(spec.precision), _lib.stream(rays_o)), "dwg_nerf_train_gather_live")
             if st.shading:
                 _lib.check(L.dwg_nerf_train_gather_live_rows(_lib.ptr(rays), _lib.ptr(rays_live), N, M, M_live, _lib.ptr(sigma_fd),
-                                                             _lib.ptr(sigma_fd_l), 6, _st(rays_o)), "dwg_nerf_train_gather_live_rows")
+                                                             _lib.ptr(sigma_fd_l), 6, _lib.stream(rays_o)), "dwg_nerf_train_gather_live_rows")
         ctx.st = st
         if st.shading:
             ctx.save_for_backward(xyzs_l, ts_l, sigmas_l, albedo_l, rays_live, weights_sum, depth, image, embeddings, sigma_scale, *wb,
@@ -269,7 +267,7 @@ class _RenderRaysTrain(Function):
         # 1. the composite backward over the live rows; its temporaries go before the field backward allocates its workspace
         if st.shading:                                                      # the colours of the live rows again: the forward's bits
             rgbs = torch.empty(M, ch, dtype=torch.float32, device=xyzs.device)
-            _shade_train(L, st, sigma_fd, albedo, M, ch, rgbs, _st(xyzs))
+            _shade_train(L, st, sigma_fd, albedo, M, ch, rgbs, _lib.stream(xyzs))
         else:
             rgbs = albedo.float()
         grad_weights = torch.zeros(M, dtype=torch.float32, device=xyzs.device)
@@ -288,7 +286,7 @@ class _RenderRaysTrain(Function):
             _lib.check(L.dwg_nerf_train_shade_backward(
                 st.shading, _lib.ptr(sigma_fd), _lib.ptr(albedo) if st.shading == 3 else None, int(albedo.dtype == torch.float16),
                 _lib.ptr(st.light_d), ctypes.c_float(st.ratio), ctypes.c_float(st.eps), M, ch, _lib.ptr(grad_rgbs), _lib.ptr(dsigma_fd),
-                _lib.ptr(dalbedo), _st(xyzs)), "dwg_nerf_train_shade_backward")
+                _lib.ptr(dalbedo), _lib.stream(xyzs)), "dwg_nerf_train_shade_backward")
             if st.debug is not None:
                 st.debug.update(dsigma_fd_live=dsigma_fd, dalbedo_live=dalbedo)
         else:
@@ -350,10 +348,10 @@ def render_rays_train(rays_o, rays_d, nears, fars, density_bitfield, cascade, gr
     st.light_d, st.ratio, st.eps = light_d.detach() if st.shading >= 2 else None, float(ambient_ratio), float(epsilon)
     others = []
     if noises is not None:
-        _check("noises", noises, torch.float32, (N,))
+        _lib.check_tensor("noises", noises, torch.float32, (N,))
         others.append(("noises", noises))
     if counter is not None:
-        _check("counter", counter, torch.int32, (None,))
+        _lib.check_tensor("counter", counter, torch.int32, (None,))
         if counter.numel() < 1:
             raise RuntimeError("counter must hold at least one element")
         others.append(("counter", counter))

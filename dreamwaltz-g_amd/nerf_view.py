@@ -22,25 +22,8 @@ from . import _lib
 from . import nerf_background
 from . import nerf_render
 
-BG_NONE, BG_CONSTANT, BG_IMAGE = 0, 1, 2
-MAX_SIZE = 32768
-
-
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _check(name, t, shape):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError("%s must be a tensor, got %s" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA tensor" % name)
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    if not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous" % name)
+_C = _lib.CONSTANTS
+BG_NONE, BG_CONSTANT, BG_IMAGE, MAX_SIZE = _C["DWG_VIEW_BG_NONE"], _C["DWG_VIEW_BG_CONSTANT"], _C["DWG_VIEW_BG_IMAGE"], _C["DWG_VIEW_MAX_SIZE"]
 
 
 def _image_size(H, W):
@@ -67,9 +50,9 @@ def view_rays(c2w, intrinsics, H, W, aabb, min_near=0.2):
     H, W = _image_size(H, W)
     c2w = _one_camera("c2w", c2w, (4, 4))
     intrinsics = _one_camera("intrinsics", intrinsics, (3, 3))
-    _check("c2w", c2w, (4, 4))
-    _check("intrinsics", intrinsics, (3, 3))
-    _check("aabb", aabb, (6,))
+    _lib.check_tensor("c2w", c2w, shape=(4, 4))
+    _lib.check_tensor("intrinsics", intrinsics, shape=(3, 3))
+    _lib.check_tensor("aabb", aabb, shape=(6,))
     dev = c2w.device
     for name, t in (("intrinsics", intrinsics), ("aabb", aabb)):
         if t.device != dev:
@@ -82,7 +65,7 @@ def view_rays(c2w, intrinsics, H, W, aabb, min_near=0.2):
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dwg_nerf_view_rays(_lib.ptr(c2w.detach()), _lib.ptr(intrinsics.detach()), _lib.ptr(aabb.detach()), H, W,
                                                  ctypes.c_float(min_near), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(nears), _lib.ptr(fars),
-                                                 _st(c2w)), "dwg_nerf_view_rays")
+                                                 _lib.stream(c2w)), "dwg_nerf_view_rays")
     return rays_o, rays_d, nears, fars
 
 
@@ -130,7 +113,7 @@ class _ViewCompose(Function):
         with torch.cuda.device(dev):
             _lib.check(L.dwg_nerf_view_compose_forward(N, C, co, _lib.ptr(image_fg), _lib.ptr(weights_sum), _lib.ptr(bg), st.bg_mode, lam[0],
                                                        lam[1], lam[2], lam[3], _lib.ptr(image), _lib.ptr(loss) if st.sparsity is not None else None,
-                                                       _lib.ptr(ws_buf), nbytes if ws_buf is not None else 0, _st(weights_sum)),
+                                                       _lib.ptr(ws_buf), nbytes if ws_buf is not None else 0, _lib.stream(weights_sum)),
                        "dwg_nerf_view_compose_forward")
         ctx.st = st
         if st.keep:
@@ -163,7 +146,7 @@ class _ViewCompose(Function):
             _lib.check(L.dwg_nerf_view_compose_backward(N, C, st.channels_out, _lib.ptr(d_image), _lib.ptr(d_loss), _lib.ptr(weights_sum),
                                                         _lib.ptr(bg), st.bg_mode, int(st.detach_ws), lam[0], lam[1], lam[2], lam[3],
                                                         _lib.ptr(ws_buf), ws_buf.numel() * 8 if ws_buf is not None else 0, _lib.ptr(d_fg),
-                                                        _lib.ptr(d_ws), _lib.ptr(d_bg), _st(weights_sum)), "dwg_nerf_view_compose_backward")
+                                                        _lib.ptr(d_ws), _lib.ptr(d_bg), _lib.stream(weights_sum)), "dwg_nerf_view_compose_backward")
         return (None, d_fg.view(st.fg_shape) if d_fg is not None else None, d_ws.view(st.ws_shape) if ctx.needs_input_grad[2] else None,
                 d_bg.view(st.bg_shape) if d_bg is not None else None)
 
@@ -196,10 +179,10 @@ def view_compose(image_fg, weights_sum, background, H, W, *, detach_ws=False, ch
     if st.has_image and (not isinstance(image_fg, torch.Tensor) or image_fg.dim() < 1 or image_fg.shape[-1] not in (3, 4)
                          or image_fg.numel() != N * image_fg.shape[-1]):
         raise RuntimeError("image_fg must be a tensor [..., C] of H * W = %d pixels with C = 3 or 4" % N)
-    _check("weights_sum", weights_sum, weights_sum.shape)
+    _lib.check_tensor("weights_sum", weights_sum)
     dev = weights_sum.device
     if st.has_image:
-        _check("image_fg", image_fg, image_fg.shape)
+        _lib.check_tensor("image_fg", image_fg)
         C = int(image_fg.shape[-1])
         if image_fg.device != dev:
             raise RuntimeError("image_fg is on %s, weights_sum on %s" % (image_fg.device, dev))
@@ -223,7 +206,7 @@ def view_compose(image_fg, weights_sum, background, H, W, *, detach_ws=False, ch
             st.bg_mode = BG_IMAGE
         else:
             raise RuntimeError("background must be a colour [%d] or an image [..., %d] of %d pixels, got %s" % (C, C, N, tuple(background.shape)))
-        _check("background", background, background.shape)
+        _lib.check_tensor("background", background)
         if background.device != dev:
             raise RuntimeError("background is on %s, weights_sum on %s" % (background.device, dev))
         if st.bg_mode == BG_IMAGE and background.data_ptr() % 16:

@@ -1,13 +1,8 @@
 """Python bindings of include/dwg_nn.h (GroupNorm, LayerNorm, GEGLU, fused attention, row softmax)."""
-import ctypes
 
 import torch
 
 from . import _lib
-
-
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _chk(t, dtype=torch.bfloat16):
@@ -26,7 +21,7 @@ def groupnorm(x, gamma, beta, groups=32, eps=1e-5, silu=False, out=None, stats=N
     ws = torch.empty(_lib.lib().dwg_groupnorm_workspace_floats(B, groups), device=x.device, dtype=torch.float32)
     p = _lib.ptr
     _lib.check(_lib.lib().dwg_groupnorm_forward(B, HW, C, groups, p(x), p(gamma), p(beta), eps, int(silu), p(y), p(stats), p(ws),
-                                                _st(x)), "dwg_groupnorm_forward")
+                                                _lib.stream(x)), "dwg_groupnorm_forward")
     return y, stats
 
 
@@ -39,7 +34,7 @@ def groupnorm_backward(x, dy, stats, gamma, beta, groups=32, eps=1e-5, silu=Fals
     ws = torch.empty(_lib.lib().dwg_groupnorm_workspace_floats(B, groups), device=x.device, dtype=torch.float32)
     p = _lib.ptr
     _lib.check(_lib.lib().dwg_groupnorm_backward(B, HW, C, groups, p(x), p(dy), p(stats), p(gamma), p(beta), eps, int(silu), p(dx),
-                                                 p(scratch), p(ws), p(residual), _st(x)), "dwg_groupnorm_backward")
+                                                 p(scratch), p(ws), p(residual), _lib.stream(x)), "dwg_groupnorm_backward")
     return dx
 
 
@@ -49,7 +44,7 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     M = x.numel() // C
     y = torch.empty_like(x) if out is None else out
     p = _lib.ptr
-    _lib.check(_lib.lib().dwg_layernorm_forward(M, C, p(x), p(gamma), p(beta), eps, p(y), _st(x)), "dwg_layernorm_forward")
+    _lib.check(_lib.lib().dwg_layernorm_forward(M, C, p(x), p(gamma), p(beta), eps, p(y), _lib.stream(x)), "dwg_layernorm_forward")
     return y
 
 
@@ -59,7 +54,7 @@ def geglu(x, out=None):
     M = x.numel() // F2
     y = torch.empty(*x.shape[:-1], F2 // 2, device=x.device, dtype=x.dtype) if out is None else out
     p = _lib.ptr
-    _lib.check(_lib.lib().dwg_geglu_forward(M, F2 // 2, p(x), p(y), _st(x)), "dwg_geglu_forward")
+    _lib.check(_lib.lib().dwg_geglu_forward(M, F2 // 2, p(x), p(y), _lib.stream(x)), "dwg_geglu_forward")
     return y
 
 
@@ -74,7 +69,7 @@ def attention(q, k, v, heads, out=None, scale=None):
         assert t.stride(2) == 1 and t.dtype == q.dtype and t.dtype in (torch.bfloat16, torch.float16)
     p = _lib.ptr
     _lib.check(_lib.lib().dwg_attention_forward_dt(1 if q.dtype == torch.bfloat16 else 2, B, heads, Nq, Nk, d, p(q), q.stride(1), q.stride(0), p(k), k.stride(1), k.stride(0),
-                                                p(v), v.stride(1), v.stride(0), p(o), o.stride(1), o.stride(0), scale, _st(q)),
+                                                p(v), v.stride(1), v.stride(0), p(o), o.stride(1), o.stride(0), scale, _lib.stream(q)),
                "dwg_attention_forward_dt")
     return o
 
@@ -83,7 +78,7 @@ def softmax_rows(S, scale=1.0, out=None):
     rows, n = S.shape
     P = torch.empty(rows, n, device=S.device, dtype=torch.bfloat16) if out is None else out
     p = _lib.ptr
-    _lib.check(_lib.lib().dwg_softmax_rows_forward(rows, n, scale, p(S), S.stride(0), p(P), P.stride(0), _st(S)),
+    _lib.check(_lib.lib().dwg_softmax_rows_forward(rows, n, scale, p(S), S.stride(0), p(P), P.stride(0), _lib.stream(S)),
                "dwg_softmax_rows_forward")
     return P
 
@@ -93,5 +88,5 @@ def softmax_rows_backward(P, dP, scale=1.0):
     dS = torch.empty(rows, n, device=P.device, dtype=torch.bfloat16)
     p = _lib.ptr
     _lib.check(_lib.lib().dwg_softmax_rows_backward(rows, n, scale, p(P), P.stride(0), p(dP), dP.stride(0), p(dS), dS.stride(0),
-                                                    _st(P)), "dwg_softmax_rows_backward")
+                                                    _lib.stream(P)), "dwg_softmax_rows_backward")
     return dS

@@ -24,13 +24,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import nerf
 from . import pointcloud
 
 MIN_H, MAX_H, MAX_C = 4, 1024, 8
 STATS = ("mean", "min", "max", "log_min", "log_max", "thresh", "count_lo", "count_hi")
-_st = nerf._st
-_check = pointcloud._dev_check
 _axis_cache = {}
 
 
@@ -111,13 +108,13 @@ def _aligned(name, t):
 
 
 def _table_args(axis, noise, scale, half):
-    _check("axis", axis, torch.float32, (None,))
+    _lib.check_tensor("axis", axis, torch.float32, (None,))
     H = axis.numel()
-    _check("scale", scale, torch.float32, (None,))
+    _lib.check_tensor("scale", scale, torch.float32, (None,))
     C = scale.numel()
     check_limits(C, H)
-    _check("half", half, torch.float32, (C,))
-    _check("noise", noise, torch.float32, (C, H ** 3, 3))
+    _lib.check_tensor("half", half, torch.float32, (C,))
+    _lib.check_tensor("noise", noise, torch.float32, (C, H ** 3, 3))
     return C, H
 
 
@@ -125,7 +122,7 @@ def lattice_points(axis, noise, scale, half):
     """[C, H^3, 3] fp32: the jittered cell points in meshgrid order (dwg_occ_lattice_points)."""
     C, H = _table_args(axis, noise, scale, half)
     out = torch.empty((C, H ** 3, 3), dtype=torch.float32, device=axis.device)
-    _lib.check(_lib.lib().dwg_occ_lattice_points(_lib.ptr(axis), _lib.ptr(noise), _lib.ptr(scale), _lib.ptr(half), C, H, _lib.ptr(out), _st(axis)),
+    _lib.check(_lib.lib().dwg_occ_lattice_points(_lib.ptr(axis), _lib.ptr(noise), _lib.ptr(scale), _lib.ptr(half), C, H, _lib.ptr(out), _lib.stream(axis)),
                "dwg_occ_lattice_points")
     return out
 
@@ -140,10 +137,10 @@ def lattice_sigma(spec, embeddings, sigma_scale, wb, axis, noise, scale, half, r
     if out is None:
         out = torch.empty((C, H ** 3), dtype=torch.float32, device=axis.device)
     else:
-        _check("out", out, torch.float32, (C, H ** 3))
+        _lib.check_tensor("out", out, torch.float32, (C, H ** 3))
     d = spec.desc(embeddings, sigma_scale, wb)
     _lib.check(_lib.lib().dwg_occ_lattice_sigma(ctypes.byref(d), _lib.ptr(axis), _lib.ptr(noise), _lib.ptr(scale), _lib.ptr(half), C, H,
-                                                int(bool(random_sigmas)), _lib.ptr(out), _st(axis)), "dwg_occ_lattice_sigma")
+                                                int(bool(random_sigmas)), _lib.ptr(out), _lib.stream(axis)), "dwg_occ_lattice_sigma")
     return out
 
 
@@ -156,43 +153,43 @@ def update_grid(density_grid, tmp_grid, grid_size, decay, density_thresh, bitfie
     """dwg_occ_update in place on density_grid [C, H^3] and bitfield [C H^3 / 8]: the decayed maximum with tmp_grid on the valid cells,
     the statistics, min(mean, density_thresh) and the bitfield.  Returns stats [8] fp32 on the device (STATS names the entries; the last
     two hold the valid count's uint32 words as bit patterns)."""
-    _check("density_grid", density_grid, torch.float32, (None, None))
+    _lib.check_tensor("density_grid", density_grid, torch.float32, (None, None))
     C, H = check_limits(density_grid.shape[0], grid_size)
-    _check("density_grid", density_grid, torch.float32, (C, H ** 3))
-    _check("tmp_grid", tmp_grid, torch.float32, (C, H ** 3))
-    _check("bitfield", bitfield, torch.uint8, (C * H ** 3 // 8,))
+    _lib.check_tensor("density_grid", density_grid, torch.float32, (C, H ** 3))
+    _lib.check_tensor("tmp_grid", tmp_grid, torch.float32, (C, H ** 3))
+    _lib.check_tensor("bitfield", bitfield, torch.uint8, (C * H ** 3 // 8,))
     _aligned("density_grid", density_grid); _aligned("tmp_grid", tmp_grid)
     dev = density_grid.device
     if stats is None:
         stats = torch.empty(8, dtype=torch.float32, device=dev)
     else:
-        _check("stats", stats, torch.float32, (8,))
+        _lib.check_tensor("stats", stats, torch.float32, (8,))
     L = _lib.lib()
     nbytes = int(L.dwg_occ_update_workspace_bytes(C, H))
     if workspace is None:
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     else:
-        _check("workspace", workspace, torch.uint8, (None,))
+        _lib.check_tensor("workspace", workspace, torch.uint8, (None,))
         _aligned("workspace", workspace)
         if workspace.numel() < nbytes:
             raise RuntimeError("workspace has %d bytes, the update needs %d" % (workspace.numel(), nbytes))
     _lib.check(L.dwg_occ_update(_lib.ptr(density_grid), _lib.ptr(tmp_grid), C, H, ctypes.c_float(decay), ctypes.c_float(density_thresh),
-                                _lib.ptr(bitfield), _lib.ptr(stats), _lib.ptr(workspace), workspace.numel(), _st(density_grid)), "dwg_occ_update")
+                                _lib.ptr(bitfield), _lib.ptr(stats), _lib.ptr(workspace), workspace.numel(), _lib.stream(density_grid)), "dwg_occ_update")
     return stats
 
 
 def packbits_dev(grid, thresh, bitfield):
     """bitfield [N] <- bit i of byte j = grid[8 j + i] > thresh[0], the threshold a device tensor (dwg_raymarch_packbits_dev)."""
-    _check("bitfield", bitfield, torch.uint8, (None,))
+    _lib.check_tensor("bitfield", bitfield, torch.uint8, (None,))
     N = bitfield.numel()
     if not isinstance(grid, torch.Tensor) or grid.numel() != 8 * N:
         raise RuntimeError("grid must be a tensor of %d elements (8 per bitfield byte)" % (8 * N))
-    _check("grid", grid, torch.float32, tuple(grid.shape))
-    _check("thresh", thresh, torch.float32, (1,))
+    _lib.check_tensor("grid", grid, torch.float32, tuple(grid.shape))
+    _lib.check_tensor("thresh", thresh, torch.float32, (1,))
     _aligned("grid", grid)
     if N >= 1 << 32:
         raise RuntimeError("packbits_dev takes fewer than 2^32 bytes")
-    _lib.check(_lib.lib().dwg_raymarch_packbits_dev(_lib.ptr(grid), N, _lib.ptr(thresh), _lib.ptr(bitfield), _st(grid)), "dwg_raymarch_packbits_dev")
+    _lib.check(_lib.lib().dwg_raymarch_packbits_dev(_lib.ptr(grid), N, _lib.ptr(thresh), _lib.ptr(bitfield), _lib.stream(grid)), "dwg_raymarch_packbits_dev")
     return bitfield
 
 
@@ -216,8 +213,8 @@ class OccupancyGrid:
             density_grid = torch.zeros((C, H ** 3), dtype=torch.float32, device=device)
         if density_bitfield is None:
             density_bitfield = torch.zeros(C * H ** 3 // 8, dtype=torch.uint8, device=density_grid.device if isinstance(density_grid, torch.Tensor) else device)
-        _check("density_grid", density_grid, torch.float32, (C, H ** 3))
-        _check("density_bitfield", density_bitfield, torch.uint8, (C * H ** 3 // 8,))
+        _lib.check_tensor("density_grid", density_grid, torch.float32, (C, H ** 3))
+        _lib.check_tensor("density_bitfield", density_bitfield, torch.uint8, (C * H ** 3 // 8,))
         _aligned("density_grid", density_grid)
         if density_bitfield.device != density_grid.device:
             raise RuntimeError("density_grid and density_bitfield must be on the same device")

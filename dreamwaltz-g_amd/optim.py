@@ -203,7 +203,7 @@ class FlatOptimizer:
     def launch_step(self, hyper_dev: torch.Tensor, base: int):
         """DEVICE half: one fused Adam launch per group reading its scalars from row base + k of the device hyper table (capturable)."""
         b = self.buf
-        st = ctypes.c_void_p(torch.cuda.current_stream(b.flat.device).cuda_stream)
+        st = _lib.stream(b.flat.device)
         for k, pg in enumerate(self.param_groups):
             n, o = pg["end"] - pg["start"], pg["start"] * 4
             if n <= 0:
@@ -278,7 +278,7 @@ class FlatOptimizer:
                                           float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), gi))
         d = self._device_state()
         L = _lib.lib()
-        st = ctypes.c_void_p(torch.cuda.current_stream(b.flat.device).cuda_stream)
+        st = _lib.stream(b.flat.device)
         n = self.end - self.start
         _lib.check(L.dwg_grads_nonfinite(n, ctypes.c_void_p(b.grad.data_ptr() + 4 * self.start), _lib.ptr(d["slots"]), st), "dwg_grads_nonfinite")
         G = len(self.param_groups)
@@ -290,14 +290,14 @@ class FlatOptimizer:
         self._dev_ahead = True
         if groups:
             arr = (_lib.AdamGroupC * len(groups))(*groups)
-            _lib.check(L.dwg_adam_step_groups_scaled_dev(len(groups), ctypes.cast(arr, ctypes.c_void_p), _lib.ptr(d["hyper"]), st),
+            _lib.check(L.dwg_adam_step_groups_scaled_dev(len(groups), arr, _lib.ptr(d["hyper"]), st),
                        "dwg_adam_step_groups_scaled_dev")
 
     def _launch(self, pg):
         """The fused Adam launch of one group over its slice of the flat buffers (csrc/elementwise.hip k_adam)."""
         b = self.buf
         n, o = pg["end"] - pg["start"], pg["start"] * 4
-        st = ctypes.c_void_p(torch.cuda.current_stream(b.flat.device).cuda_stream)
+        st = _lib.stream(b.flat.device)
         _lib.check(_lib.lib().dwg_adam_step(n, ctypes.c_void_p(b.flat.data_ptr() + o), ctypes.c_void_p(b.grad.data_ptr() + o),
                                             ctypes.c_void_p(b.m.data_ptr() + o), ctypes.c_void_p(b.v.data_ptr() + o), float(pg["lr"]),
                                             float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), int(pg["t"]), float(self.grad_scale), st),
@@ -353,8 +353,8 @@ class FlatOptimizerDict(dict):
                 base += o.launch_step(hyper_dev, base)
             return base
         arr = (_lib.AdamGroupC * max(len(groups), 1))(*groups)
-        st = ctypes.c_void_p(torch.cuda.current_stream(b.flat.device).cuda_stream)
-        _lib.check(_lib.lib().dwg_adam_step_groups_dev(len(groups), ctypes.cast(arr, ctypes.c_void_p), ctypes.c_void_p(hyper_dev.data_ptr()), st),
+        st = _lib.stream(b.flat.device)
+        _lib.check(_lib.lib().dwg_adam_step_groups_dev(len(groups), arr, ctypes.c_void_p(hyper_dev.data_ptr()), st),
                    "dwg_adam_step_groups_dev")
         return base
 

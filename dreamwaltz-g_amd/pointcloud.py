@@ -20,8 +20,7 @@ import torch
 from . import _lib
 from . import nerf
 
-MINMAX_PAIRS = 4096                 # DWG_PC_MINMAX_PAIRS
-_st = nerf._st
+MINMAX_PAIRS = _lib.CONSTANTS["DWG_PC_MINMAX_PAIRS"]
 
 
 class BasicPointCloud:
@@ -86,19 +85,6 @@ def lattice_index(f, nx, ny, nz, split):
     return xi * sx + lx, yi * sy + ly, zi * sz + lz
 
 
-def _dev_check(name, t, dtype, shape):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError("%s must be a tensor, got %s" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA tensor" % name)
-    if t.dtype != dtype:
-        raise RuntimeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if t.dim() != len(shape) or any(s is not None and t.shape[k] != s for k, s in enumerate(shape)):
-        raise RuntimeError("%s has shape %s, expected %s" % (name, tuple(t.shape), shape))
-    if not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous" % name)
-
-
 def _lattice_args(resolution, split_size):
     if int(resolution) != resolution or int(split_size) != split_size:
         raise ValueError("resolution and split_size must be integers, got %r and %r" % (resolution, split_size))
@@ -120,7 +106,7 @@ def axis_table(resolution, device):
 def lattice_sigma(spec, embeddings, sigma_scale, wb, ax, ay, az, split):
     """(sigma [nx ny nz] fp32 in the reference's order, minmax [MINMAX_PAIRS, 2] fp32 partials) of the field at the lattice."""
     for n, t in (("ax", ax), ("ay", ay), ("az", az)):
-        _dev_check(n, t, torch.float32, (None,))
+        _lib.check_tensor(n, t, torch.float32, (None,))
     M = ax.numel() * ay.numel() * az.numel()
     if M >= 1 << 32 or split < 1:
         raise ValueError("lattice of %d points (limit 2^32 - 1) / split %d" % (M, split))
@@ -129,7 +115,7 @@ def lattice_sigma(spec, embeddings, sigma_scale, wb, ax, ay, az, split):
     d = spec.desc(embeddings, sigma_scale, wb)
     if M:
         _lib.check(_lib.lib().dwg_pc_lattice_sigma(ctypes.byref(d), _lib.ptr(ax), _lib.ptr(ay), _lib.ptr(az), ax.numel(), ay.numel(), az.numel(),
-                                                   int(split), _lib.ptr(sigma), _lib.ptr(minmax), _st(ax)), "dwg_pc_lattice_sigma")
+                                                   int(split), _lib.ptr(sigma), _lib.ptr(minmax), _lib.stream(ax)), "dwg_pc_lattice_sigma")
     return sigma, minmax
 
 
@@ -145,14 +131,14 @@ def _select(fn_name, M, args, device, capacity):
         nbytes = int(L.dwg_pc_select_workspace_bytes(M))
         ws = torch.empty(nbytes // 4, dtype=torch.int32, device=device)
         _lib.check(getattr(L, fn_name)(M, *args, _lib.ptr(idx) if idx.numel() else _lib.ptr(ws), min(M, capacity), _lib.ptr(count), _lib.ptr(ws),
-                                       nbytes, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)), fn_name)
+                                       nbytes, _lib.stream(device)), fn_name)
     return idx, count
 
 
 def select_above(values, thresh, capacity=None):
     """Indices i (ascending; int32 tensor holding uint32 bits) with values[i] > float32(thresh), and their count [1] on the device.
     With a capacity below the count only the first `capacity` indices are written; the count stays the full one."""
-    _dev_check("values", values, torch.float32, (None,))
+    _lib.check_tensor("values", values, torch.float32, (None,))
     if values.numel() >= 1 << 32:
         raise ValueError("select_above takes fewer than 2^32 values")
     return _select("dwg_pc_select_above", values.numel(), (_lib.ptr(values), float(np.float32(thresh))), values.device, capacity)
@@ -160,7 +146,7 @@ def select_above(values, thresh, capacity=None):
 
 def select_flags(flags, capacity=None):
     """The same over a uint8 mask (flags[i] != 0)."""
-    _dev_check("flags", flags, torch.uint8, (None,))
+    _lib.check_tensor("flags", flags, torch.uint8, (None,))
     if flags.numel() >= 1 << 32:
         raise ValueError("select_flags takes fewer than 2^32 flags")
     return _select("dwg_pc_select_flags", flags.numel(), (_lib.ptr(flags),), flags.device, capacity)
@@ -168,24 +154,24 @@ def select_flags(flags, capacity=None):
 
 def lattice_points(idx, ax, ay, az, split):
     """[n, 3] fp32 coordinates of the flat reference-order indices idx [n] (int32 holding uint32 bits)."""
-    _dev_check("idx", idx, torch.int32, (None,))
+    _lib.check_tensor("idx", idx, torch.int32, (None,))
     for n, t in (("ax", ax), ("ay", ay), ("az", az)):
-        _dev_check(n, t, torch.float32, (None,))
+        _lib.check_tensor(n, t, torch.float32, (None,))
     if ax.numel() * ay.numel() * az.numel() >= 1 << 32 or split < 1:
         raise ValueError("lattice of 2^32 points or more, or split < 1")
     out = torch.empty((idx.numel(), 3), dtype=torch.float32, device=idx.device)
     if idx.numel():
         _lib.check(_lib.lib().dwg_pc_lattice_points(idx.numel(), _lib.ptr(idx), _lib.ptr(ax), _lib.ptr(ay), _lib.ptr(az), ax.numel(), ay.numel(),
-                                                    az.numel(), int(split), _lib.ptr(out), _st(idx)), "dwg_pc_lattice_points")
+                                                    az.numel(), int(split), _lib.ptr(out), _lib.stream(idx)), "dwg_pc_lattice_points")
     return out
 
 
 def fd_points(points, eps, bound):
     """[6, n, 3]: clamp(points +- eps along x, y, z, -bound, bound) in the order +x, -x, +y, -y, +z, -z (nerf_model.py:149-154)."""
-    _dev_check("points", points, torch.float32, (None, 3))
+    _lib.check_tensor("points", points, torch.float32, (None, 3))
     out = torch.empty((6,) + tuple(points.shape), dtype=torch.float32, device=points.device)
     if points.shape[0]:
-        _lib.check(_lib.lib().dwg_pc_fd_points(points.shape[0], _lib.ptr(points), float(np.float32(eps)), float(bound), _lib.ptr(out), _st(points)),
+        _lib.check(_lib.lib().dwg_pc_fd_points(points.shape[0], _lib.ptr(points), float(np.float32(eps)), float(bound), _lib.ptr(out), _lib.stream(points)),
                    "dwg_pc_fd_points")
     return out
 
@@ -193,26 +179,26 @@ def fd_points(points, eps, bound):
 def finish(albedo, sig6, eps):
     """(colors [n, 3], normals [n, 3]) from albedo [n, 3 or 4] fp32 and the six shifted densities sig6 [6, n]."""
     n = albedo.shape[0] if isinstance(albedo, torch.Tensor) and albedo.dim() == 2 else 0
-    _dev_check("albedo", albedo, torch.float32, (n, None))
+    _lib.check_tensor("albedo", albedo, torch.float32, (n, None))
     if albedo.shape[1] not in (3, 4):
         raise ValueError("albedo has %d channels; latent_to_rgb takes 3 or 4" % albedo.shape[1])
-    _dev_check("sig6", sig6, torch.float32, (6, n))
+    _lib.check_tensor("sig6", sig6, torch.float32, (6, n))
     colors = torch.empty((n, 3), dtype=torch.float32, device=albedo.device)
     normals = torch.empty((n, 3), dtype=torch.float32, device=albedo.device)
     if n:
         _lib.check(_lib.lib().dwg_pc_finish(n, albedo.shape[1], _lib.ptr(albedo), _lib.ptr(sig6), float(np.float32(eps)), _lib.ptr(colors),
-                                            _lib.ptr(normals), _st(albedo)), "dwg_pc_finish")
+                                            _lib.ptr(normals), _lib.stream(albedo)), "dwg_pc_finish")
     return colors, normals
 
 
 def outside_boxes(points, boxes):
     """keep [n] uint8: 0 where points [n, 3] fp32 lies inside any of boxes [nb, 2, 3] float64 (min corner, max corner), faces included."""
-    _dev_check("points", points, torch.float32, (None, 3))
-    _dev_check("boxes", boxes, torch.float64, (None, 2, 3))
+    _lib.check_tensor("points", points, torch.float32, (None, 3))
+    _lib.check_tensor("boxes", boxes, torch.float64, (None, 2, 3))
     keep = torch.empty(points.shape[0], dtype=torch.uint8, device=points.device)
     if points.shape[0]:
         _lib.check(_lib.lib().dwg_pc_outside_boxes(points.shape[0], _lib.ptr(points), boxes.shape[0], _lib.ptr(boxes) if boxes.shape[0] else None,
-                                                   _lib.ptr(keep), _st(points)), "dwg_pc_outside_boxes")
+                                                   _lib.ptr(keep), _lib.stream(points)), "dwg_pc_outside_boxes")
     return keep
 
 
@@ -243,7 +229,7 @@ def field_spec(encoder, sigma_net, sigma_scale, bound, density_activation='exp',
 
 def field_forward(spec, embeddings, sigma_scale, wb, x):
     """(sigma [M] fp32, albedo [M, out_dim - 1]) of dwg_nerf_field_forward at x [M, 3], without autograd."""
-    _dev_check("x", x, torch.float32, (None, 3))
+    _lib.check_tensor("x", x, torch.float32, (None, 3))
     return nerf.field_forward(spec, embeddings, sigma_scale, wb, x)
 
 

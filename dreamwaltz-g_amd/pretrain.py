@@ -8,7 +8,6 @@ What differs from the reference, deliberately:
     depth picture needs max(smpl_depth) on the host, so with snapshots off the step makes no host synchronisation;
   * the loss is always fp32 (under autocast the reference's mse_loss runs in fp32 too); the gradients have the dtype of the renders.
 There is no CPU fallback: CPU renders raise."""
-import ctypes
 
 import numpy as np
 import torch
@@ -16,12 +15,8 @@ import torch
 from . import _lib
 from .condition import DepthMap
 
-_DTYPES = {torch.float32: 0, torch.float16: 2}          # DWG_DTYPE_F32, DWG_DTYPE_F16 (include/dwg_types.h)
+_DTYPES = {torch.float32: _lib.CONSTANTS["DWG_DTYPE_F32"], torch.float16: _lib.CONSTANTS["DWG_DTYPE_F16"]}
 _ws = {}
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _workspace(device, n):
@@ -40,7 +35,7 @@ class _DepthMaskLoss(torch.autograd.Function):
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_pretrain_loss_forward(_DTYPES[render_depth.dtype], n, p(render_depth), p(render_ws), p(smpl_depth), p(loss),
-                                                        p(ws), ws.numel(), _stream(dev)), "dwg_pretrain_loss_forward")
+                                                        p(ws), ws.numel(), _lib.stream(dev)), "dwg_pretrain_loss_forward")
         ctx.save_for_backward(render_depth, render_ws, smpl_depth)
         return loss.reshape(())
 
@@ -55,7 +50,7 @@ class _DepthMaskLoss(torch.autograd.Function):
             return None, None, None
         p = _lib.ptr
         _lib.check(_lib.lib().dwg_pretrain_loss_backward(_DTYPES[render_depth.dtype], n, p(render_depth), p(render_ws), p(smpl_depth), p(g),
-                                                         p(g_depth), p(g_ws), _stream(dev)), "dwg_pretrain_loss_backward")
+                                                         p(g_depth), p(g_ws), _lib.stream(dev)), "dwg_pretrain_loss_backward")
         return g_depth, g_ws, None
 
 

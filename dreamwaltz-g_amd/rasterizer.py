@@ -108,10 +108,6 @@ def _settings_struct(rs: GaussianRasterizationSettings, device, sh_coeffs: int, 
     return c
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _workspace_sizes(G, H, W, cap):
     """Bytes of one frame's (geometry, pair, image) workspaces at pair capacity `cap` (dwg_raster_workspace_sizes)."""
     gb, pb, ib = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
@@ -162,7 +158,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ws_geom = torch.empty(geom_bytes, dtype=torch.uint8, device=device)
         ws_image = torch.empty(image_bytes, dtype=torch.uint8, device=device)
         radii = torch.empty(G, dtype=torch.int32, device=device)         # k_preprocess writes every entry (0 for what it culls)
-        st = _stream(device)
+        st = _lib.stream(device)
         p = _lib.ptr
         if pair_state is not None:
             pair_state.resolve()        # the previous frame's count (long complete): keeps `cap` current, latches an overflow
@@ -250,7 +246,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                                          p(rotations), p(cov3D), p(ws_geom), p(ws_pairs), ctx.cap, p(ws_image),
                                          p(ws_grad), p(g_color), p(g_depth), p(g_alpha), p(d_means3D), p(d_means2D),
                                          p(d_sh), p(d_colors), p(d_opac), p(d_scales), p(d_rots), p(d_cov),
-                                         _stream(device)), "dwg_raster_backward")
+                                         _lib.stream(device)), "dwg_raster_backward")
         return d_means3D, d_means2D, d_sh, d_colors, d_opac, d_scales, d_rots, d_cov, None, None, None, None
 
 
@@ -275,7 +271,7 @@ class _RasterizeFrames(torch.autograd.Function):
         ws_geom = torch.empty(F * geom_bytes, dtype=torch.uint8, device=device)
         ws_image = torch.empty(F * image_bytes, dtype=torch.uint8, device=device)
         radii = torch.empty(F, G, dtype=torch.int32, device=device)          # k_preprocess writes every entry (0 for what it culls)
-        st, p = _stream(device), _lib.ptr
+        st, p = _lib.stream(device), _lib.ptr
         _lib.check(L.dwg_raster_forward_bin_frames(ctypes.byref(cfg), ctypes.byref(fr), G, p(means3D), p(shs), p(colors_precomp), p(opac),
                                                    p(scales), p(rotations), p(cov3D), p(radii), p(ws_geom), st), "dwg_raster_forward_bin_frames")
         if pair_state is not None:
@@ -348,7 +344,7 @@ class _RasterizeFrames(torch.autograd.Function):
         _lib.check(L.dwg_raster_backward_frames(ctypes.byref(cfg), ctypes.byref(fr), G, p(means3D), p(shs), p(colors_precomp), p(opac), p(scales),
                                                 p(rotations), p(cov3D), p(ws_geom), p(ws_pairs), cap, p(ws_image), p(ws_grad), p(g_color),
                                                 p(g_depth), p(g_alpha), p(d_means3D), p(d_means2D), p(d_sh), p(d_colors), p(d_opac), p(d_scales),
-                                                p(d_rots), p(d_cov), _stream(device)), "dwg_raster_backward_frames")
+                                                p(d_rots), p(d_cov), _lib.stream(device)), "dwg_raster_backward_frames")
 
         def fold(t, like):
             """[F, G, ...] gradient rows -> the input's shape: per-frame inputs take their rows, shared inputs the sum over the frames."""

@@ -17,14 +17,6 @@ from torch.autograd import Function
 from . import _lib
 
 
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _p(t):
-    return _lib.ptr(t)
-
-
 def check(name, t, dtype, numel=None, optional=False):
     if t is None:
         if optional:
@@ -62,36 +54,36 @@ _F, _I = torch.float32, torch.int32
 def near_far_from_aabb_into(rays_o, rays_d, aabb, N, min_near, nears, fars):
     check("rays_o", rays_o, _F, 3 * N); check("rays_d", rays_d, _F, 3 * N); check("aabb", aabb, _F, 6)
     check("nears", nears, _F, N); check("fars", fars, _F, N)
-    _lib.check(_lib.lib().dwg_raymarch_near_far_from_aabb(_p(rays_o), _p(rays_d), _p(aabb), N, ctypes.c_float(min_near), _p(nears), _p(fars),
-                                                          _st(rays_o)), "dwg_raymarch_near_far_from_aabb")
+    _lib.check(_lib.lib().dwg_raymarch_near_far_from_aabb(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(aabb), N, ctypes.c_float(min_near), _lib.ptr(nears), _lib.ptr(fars),
+                                                          _lib.stream(rays_o)), "dwg_raymarch_near_far_from_aabb")
 
 
 def sph_from_ray_into(rays_o, rays_d, radius, N, coords):
     check("rays_o", rays_o, _F, 3 * N); check("rays_d", rays_d, _F, 3 * N); check("coords", coords, _F, 2 * N)
-    _lib.check(_lib.lib().dwg_raymarch_sph_from_ray(_p(rays_o), _p(rays_d), ctypes.c_float(radius), N, _p(coords), _st(rays_o)),
+    _lib.check(_lib.lib().dwg_raymarch_sph_from_ray(_lib.ptr(rays_o), _lib.ptr(rays_d), ctypes.c_float(radius), N, _lib.ptr(coords), _lib.stream(rays_o)),
                "dwg_raymarch_sph_from_ray")
 
 
 def morton3D_into(coords, N, indices):
     check("coords", coords, _I, 3 * N); check("indices", indices, _I, N)
-    _lib.check(_lib.lib().dwg_raymarch_morton3d(_p(coords), N, _p(indices), _st(coords)), "dwg_raymarch_morton3d")
+    _lib.check(_lib.lib().dwg_raymarch_morton3d(_lib.ptr(coords), N, _lib.ptr(indices), _lib.stream(coords)), "dwg_raymarch_morton3d")
 
 
 def morton3D_invert_into(indices, N, coords):
     check("indices", indices, _I, N); check("coords", coords, _I, 3 * N)
-    _lib.check(_lib.lib().dwg_raymarch_morton3d_invert(_p(indices), N, _p(coords), _st(indices)), "dwg_raymarch_morton3d_invert")
+    _lib.check(_lib.lib().dwg_raymarch_morton3d_invert(_lib.ptr(indices), N, _lib.ptr(coords), _lib.stream(indices)), "dwg_raymarch_morton3d_invert")
 
 
 def packbits_into(grid, N, density_thresh, bitfield):
     check("grid", grid, _F, 8 * N); check("bitfield", bitfield, torch.uint8, N)
     if grid.data_ptr() % 16:
         grid = grid.clone()                                      # the kernel reads 2 x 16 bytes per output byte
-    _lib.check(_lib.lib().dwg_raymarch_packbits(_p(grid), N, ctypes.c_float(density_thresh), _p(bitfield), _st(grid)), "dwg_raymarch_packbits")
+    _lib.check(_lib.lib().dwg_raymarch_packbits(_lib.ptr(grid), N, ctypes.c_float(density_thresh), _lib.ptr(bitfield), _lib.stream(grid)), "dwg_raymarch_packbits")
 
 
 def flatten_rays_into(rays, N, M, res):
     check("rays", rays, _I, 2 * N); check("res", res, _I, M)
-    _lib.check(_lib.lib().dwg_raymarch_flatten_rays(_p(rays), N, M, _p(res), _st(rays)), "dwg_raymarch_flatten_rays")
+    _lib.check(_lib.lib().dwg_raymarch_flatten_rays(_lib.ptr(rays), N, M, _lib.ptr(res), _lib.stream(rays)), "dwg_raymarch_flatten_rays")
 
 
 def march_rays_train_into(rays_o, rays_d, grid, bound, contract, dt_gamma, max_steps, N, C, H, nears, fars, xyzs, dirs, ts, rays, counter,
@@ -108,9 +100,9 @@ def march_rays_train_into(rays_o, rays_d, grid, bound, contract, dt_gamma, max_s
     L = _lib.lib()
     if xyzs is None and dirs is None and ts is None:
         ws = torch.empty(max(1, L.dwg_raymarch_train_workspace_bytes(N)), dtype=torch.uint8, device=rays.device)
-        _lib.check(L.dwg_raymarch_march_rays_train(_p(rays_o), _p(rays_d), _p(grid), ctypes.c_float(bound), int(bool(contract)),
-                                                   ctypes.c_float(dt_gamma), max_steps, N, C, H, _p(nears), _p(fars), None, None, None, 0,
-                                                   _p(rays), _p(counter), _p(noises), _p(ws), ws.numel(), _st(rays)), "dwg_raymarch_march_rays_train")
+        _lib.check(L.dwg_raymarch_march_rays_train(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(grid), ctypes.c_float(bound), int(bool(contract)),
+                                                   ctypes.c_float(dt_gamma), max_steps, N, C, H, _lib.ptr(nears), _lib.ptr(fars), None, None, None, 0,
+                                                   _lib.ptr(rays), _lib.ptr(counter), _lib.ptr(noises), _lib.ptr(ws), ws.numel(), _lib.stream(rays)), "dwg_raymarch_march_rays_train")
         return
     if xyzs is None or dirs is None or ts is None:
         raise RuntimeError("xyzs, dirs and ts are either all None (count pass) or all tensors (write pass)")
@@ -118,9 +110,9 @@ def march_rays_train_into(rays_o, rays_d, grid, bound, contract, dt_gamma, max_s
     check("xyzs", xyzs, _F, 3 * M); check("dirs", dirs, _F, 3 * M); check("ts", ts, _F, 2 * M)
     if M == 0:
         return                                                   # nothing to write (an empty tensor has no address to pass)
-    _lib.check(L.dwg_raymarch_march_rays_train(_p(rays_o), _p(rays_d), _p(grid), ctypes.c_float(bound), int(bool(contract)),
-                                               ctypes.c_float(dt_gamma), max_steps, N, C, H, _p(nears), _p(fars), _p(xyzs), _p(dirs), _p(ts), M,
-                                               _p(rays), _p(counter), _p(noises), None, 0, _st(rays)), "dwg_raymarch_march_rays_train")
+    _lib.check(L.dwg_raymarch_march_rays_train(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(grid), ctypes.c_float(bound), int(bool(contract)),
+                                               ctypes.c_float(dt_gamma), max_steps, N, C, H, _lib.ptr(nears), _lib.ptr(fars), _lib.ptr(xyzs), _lib.ptr(dirs), _lib.ptr(ts), M,
+                                               _lib.ptr(rays), _lib.ptr(counter), _lib.ptr(noises), None, 0, _lib.stream(rays)), "dwg_raymarch_march_rays_train")
 
 
 def composite_rays_train_forward_into(sigmas, rgbs, ts, rays, M, N, T_thresh, binarize, weights, weights_sum, depth, image, channels):
@@ -129,8 +121,8 @@ def composite_rays_train_forward_into(sigmas, rgbs, ts, rays, M, N, T_thresh, bi
     check("weights", weights, _F, M); check("weights_sum", weights_sum, _F, N); check("depth", depth, _F, N)
     check("image", image, _F, channels * N)
     _lib.check(_lib.lib().dwg_raymarch_composite_rays_train_forward(
-        _p(sigmas), _p(rgbs), _p(ts), _p(rays), M, N, channels, ctypes.c_float(T_thresh), int(bool(binarize)), _p(weights), _p(weights_sum),
-        _p(depth), _p(image), _st(rays)), "dwg_raymarch_composite_rays_train_forward")
+        _lib.ptr(sigmas), _lib.ptr(rgbs), _lib.ptr(ts), _lib.ptr(rays), M, N, channels, ctypes.c_float(T_thresh), int(bool(binarize)), _lib.ptr(weights), _lib.ptr(weights_sum),
+        _lib.ptr(depth), _lib.ptr(image), _lib.stream(rays)), "dwg_raymarch_composite_rays_train_forward")
 
 
 def composite_rays_train_backward_into(grad_weights, grad_weights_sum, grad_depth, grad_image, sigmas, rgbs, ts, rays, weights_sum, depth,
@@ -141,8 +133,8 @@ def composite_rays_train_backward_into(grad_weights, grad_weights_sum, grad_dept
     check("ts", ts, _F, 2 * M); check("rays", rays, _I, 2 * N); check("weights_sum", weights_sum, _F, N); check("depth", depth, _F, N)
     check("image", image, _F, channels * N); check("grad_sigmas", grad_sigmas, _F, M); check("grad_rgbs", grad_rgbs, _F, channels * M)
     _lib.check(_lib.lib().dwg_raymarch_composite_rays_train_backward(
-        _p(grad_weights), _p(grad_weights_sum), _p(grad_depth), _p(grad_image), _p(sigmas), _p(rgbs), _p(ts), _p(rays), _p(weights_sum),
-        _p(depth), _p(image), M, N, channels, ctypes.c_float(T_thresh), int(bool(binarize)), _p(grad_sigmas), _p(grad_rgbs), _st(rays)),
+        _lib.ptr(grad_weights), _lib.ptr(grad_weights_sum), _lib.ptr(grad_depth), _lib.ptr(grad_image), _lib.ptr(sigmas), _lib.ptr(rgbs), _lib.ptr(ts), _lib.ptr(rays), _lib.ptr(weights_sum),
+        _lib.ptr(depth), _lib.ptr(image), M, N, channels, ctypes.c_float(T_thresh), int(bool(binarize)), _lib.ptr(grad_sigmas), _lib.ptr(grad_rgbs), _lib.stream(rays)),
         "dwg_raymarch_composite_rays_train_backward")
 
 
@@ -158,8 +150,8 @@ def march_rays_into(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, 
     if max_steps < 1 or not bound > 0:
         raise RuntimeError("max_steps must be >= 1 and bound > 0")
     _lib.check(_lib.lib().dwg_raymarch_march_rays(
-        n_alive, n_step, _p(rays_alive), _p(rays_t), _p(rays_o), _p(rays_d), ctypes.c_float(bound), int(bool(contract)), ctypes.c_float(dt_gamma),
-        max_steps, C, H, _p(grid), _p(nears), _p(fars), N, _p(xyzs), _p(dirs), _p(ts), _p(noises), _st(rays_o)), "dwg_raymarch_march_rays")
+        n_alive, n_step, _lib.ptr(rays_alive), _lib.ptr(rays_t), _lib.ptr(rays_o), _lib.ptr(rays_d), ctypes.c_float(bound), int(bool(contract)), ctypes.c_float(dt_gamma),
+        max_steps, C, H, _lib.ptr(grid), _lib.ptr(nears), _lib.ptr(fars), N, _lib.ptr(xyzs), _lib.ptr(dirs), _lib.ptr(ts), _lib.ptr(noises), _lib.stream(rays_o)), "dwg_raymarch_march_rays")
 
 
 def composite_rays_into(n_alive, n_step, T_thresh, binarize, rays_alive, rays_t, sigmas, rgbs, ts, weights_sum, depth, image, channels):
@@ -171,8 +163,8 @@ def composite_rays_into(n_alive, n_step, T_thresh, binarize, rays_alive, rays_t,
     M = n_alive * n_step
     check("sigmas", sigmas, _F, M); check("rgbs", rgbs, _F, channels * M); check("ts", ts, _F, 2 * M)
     _lib.check(_lib.lib().dwg_raymarch_composite_rays(
-        n_alive, n_step, channels, ctypes.c_float(T_thresh), int(bool(binarize)), _p(rays_alive), _p(rays_t), _p(sigmas), _p(rgbs), _p(ts), N,
-        _p(weights_sum), _p(depth), _p(image), _st(rays_t)), "dwg_raymarch_composite_rays")
+        n_alive, n_step, channels, ctypes.c_float(T_thresh), int(bool(binarize)), _lib.ptr(rays_alive), _lib.ptr(rays_t), _lib.ptr(sigmas), _lib.ptr(rgbs), _lib.ptr(ts), N,
+        _lib.ptr(weights_sum), _lib.ptr(depth), _lib.ptr(image), _lib.stream(rays_t)), "dwg_raymarch_composite_rays")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

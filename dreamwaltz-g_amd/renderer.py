@@ -128,7 +128,7 @@ class GaussianRenderer:
             p = _lib.ptr
             _lib.check(_lib.lib().dwg_raster_camera_block(p(world_view_matrix.float().contiguous()), p(projection_matrix.float().contiguous()),
                                                           p(data['c2w'][0].float().contiguous()), ctypes.c_void_p(tf.data_ptr() + 4), p(tf), p(out),
-                                                          ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                                                          _lib.stream(device)),
                        "dwg_raster_camera_block")
             viewmatrix, projmatrix, campos, tanfov_dev = out[:16].view(4, 4), out[16:32].view(4, 4), out[32:35], out[35:37]
         elif device.type == 'cuda':
@@ -136,7 +136,7 @@ class GaussianRenderer:
             p = _lib.ptr
             _lib.check(_lib.lib().dwg_raster_camera_setup(p(world_view_matrix.float().contiguous()), p(projection_matrix.float().contiguous()),
                                                           p(data['c2w'][0].float().contiguous()), p(out),
-                                                          ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                                                          _lib.stream(device)),
                        "dwg_raster_camera_setup")
             viewmatrix, projmatrix, campos = out[:16].view(4, 4), out[16:32].view(4, 4), out[32:35]
         else:

@@ -35,7 +35,7 @@ BF16 = torch.bfloat16
 #           re-split in registers.  22 significand bits end to end: eps and SDS gradients agree with the fp32 oracle like the exact "f32"
 #           plans do (tests/test_sd15_f32x_gpu.py), at 2.5-4x their speed.
 TORCH_DTYPE = {"bf16": torch.bfloat16, "f32": torch.float32, "f16": torch.float16, "f32x": xfmt.DTYPE}
-DT_CODE = {"f32": 0, "bf16": 1, "f16": 2, "f32x": 3}          # DWG_DTYPE_* (include/dwg_types.h)
+DT_CODE = {n: _lib.CONSTANTS["DWG_DTYPE_" + n.upper()] for n in ("f32", "bf16", "f16", "f32x")}
 
 
 def dtype_name(dtype) -> str:
@@ -354,7 +354,7 @@ class Plan:
         if not rows:
             return {"tensors": 0, "elements": 0, "saturated": 0, "subnormal": 0, "nonfinite": 0, "max_abs": 0.0, "worst": []}
         cnt = torch.zeros(len(rows), 5, dtype=torch.int64, device=self.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        st = _lib.stream(self.device)
         for r, (i, _) in enumerate(rows):
             t = self.keep[i]
             _lib.check(self._lib.dwg_xfmt_range_scan(t.numel(), ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(cnt[r].data_ptr()), st),
@@ -382,7 +382,7 @@ class Plan:
             src = src.float().contiguous()
         assert src.shape == dst.shape and dst.is_contiguous(), (src.shape, dst.shape)
         _lib.check(self._lib.dwg_xfmt_pack(src.numel(), ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-                                           ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "dwg_xfmt_pack")
+                                           _lib.stream(self.device)), "dwg_xfmt_pack")
 
     def load(self, t):
         """fp32 copy of a whole, contiguous activation buffer of this plan."""
@@ -390,7 +390,7 @@ class Plan:
             return t.float()
         out = torch.empty(t.shape, device=t.device, dtype=torch.float32)
         _lib.check(self._lib.dwg_xfmt_unpack(t.numel(), ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                             ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "dwg_xfmt_unpack")
+                                             _lib.stream(self.device)), "dwg_xfmt_unpack")
         return out
 
     def stage_like(self, buf):
@@ -420,7 +420,7 @@ class Plan:
         self.ops.append((self.branch, lambda s, f=f: (f(), 0)[1]))
 
     def run_eager(self):
-        self._issue(ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        self._issue(_lib.stream(self.device))
 
     def capture(self):
         """Record the whole plan into one hipGraph (launch-bound inner loop -> a single hipGraphLaunch per step).  The plan
@@ -457,7 +457,7 @@ class Plan:
 
     def run_debug(self):
         """Runs op by op and reports the first op after which any plan buffer holds a non-finite value (DWG_PLAN_ZERO=1)."""
-        s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        s = _lib.stream(self.device)
         bufs = [t for t in self.keep if torch.is_tensor(t) and t.is_floating_point()]
         for i, op in enumerate(self.ops):
             rc = 0 if op[0] == "fork" else op[1](s)
@@ -1246,14 +1246,11 @@ class VAEEncoderPlan:
         """image [B,3,H,W] fp32 in [0,1] -> moments [B,8,h,w] fp32 (NCHW view)."""
         if self._fused_io(image_nchw):
             img = image_nchw.contiguous()
-            _lib.check(self.fwd._lib.dwg_vae_image_pack(self.B, self.hw, self.hw, _lib.ptr(img), _lib.ptr(self.x), self._st()), "dwg_vae_image_pack")
+            _lib.check(self.fwd._lib.dwg_vae_image_pack(self.B, self.hw, self.hw, _lib.ptr(img), _lib.ptr(self.x), _lib.stream(self.device)), "dwg_vae_image_pack")
         else:
             self.fwd.store(self.x, (image_nchw * 2.0 - 1.0).permute(0, 2, 3, 1), self._x_stage)
         self.fwd.run()
         return self.moments.permute(0, 3, 1, 2)
-
-    def _st(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _fused_io(self, t):
         """f32x plans: the boundary conversions (2 v - 1 + NHWC + pack; max |g| + power-of-two pre-scale + NHWC + pack; unpack + NCHW + scale
@@ -1277,10 +1274,10 @@ class VAEEncoderPlan:
             inv = torch.empty(1, device=self.device, dtype=torch.float32)
             h, w_ = int(self.moments.shape[1]), int(self.moments.shape[2])
             _lib.check(self.bwd._lib.dwg_vae_grad_prescale_pack(self.B, h * w_, _lib.ptr(g), self.GRAD_TARGET,
-                                                                _lib.ptr(self.dmoments), _lib.ptr(inv), self._st()), "dwg_vae_grad_prescale_pack")
+                                                                _lib.ptr(self.dmoments), _lib.ptr(inv), _lib.stream(self.device)), "dwg_vae_grad_prescale_pack")
             self.bwd.run()
             out = torch.empty(self.B, 3, self.hw, self.hw, device=self.device, dtype=torch.float32)
-            _lib.check(self.bwd._lib.dwg_vae_dx_unpack(self.B, self.hw, self.hw, _lib.ptr(self.dx), _lib.ptr(inv), _lib.ptr(out), self._st()),
+            _lib.check(self.bwd._lib.dwg_vae_dx_unpack(self.B, self.hw, self.hw, _lib.ptr(self.dx), _lib.ptr(inv), _lib.ptr(out), _lib.stream(self.device)),
                        "dwg_vae_dx_unpack")
             return out
         inv = None

@@ -12,7 +12,6 @@ Random numbers: one torch.rand((N, 4), dtype=float64) on the device (face pick, 
 kernel is a pure function of that buffer.  The draws differ from trimesh's / numpy's, the distribution is the same.  No CPU fallback:
 every tensor is checked (CUDA, dtype, shape) and a violation raises RuntimeError before any launch.
 """
-import ctypes
 import logging
 
 import numpy as np
@@ -21,28 +20,9 @@ import torch.nn.functional as F
 
 from . import _lib
 
-REC = 16                    # DWG_SIGMA_FACE_RECORD_FLOATS
+REC = _lib.CONSTANTS["DWG_SIGMA_FACE_RECORD_FLOATS"]
 LOSS_TYPES = ('margin', 'mse', 'opacity_mse', 'opacity_ce')
 _log = logging.getLogger(__name__)
-
-
-def _st(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _check(name, t, dtype, shape=None):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError("%s must be a tensor, got %s" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA tensor" % name)
-    if t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,)):
-        raise RuntimeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if shape is not None and (t.dim() != len(shape) or any(s is not None and t.shape[k] != s for k, s in enumerate(shape))):
-        raise RuntimeError("%s has shape %s, expected %s" % (name, tuple(t.shape), shape))
-
-
-def _p(t):
-    return _lib.ptr(t)
 
 
 class PartMesh:
@@ -74,16 +54,16 @@ def _prepare(V, part):
     """Face records, fp64 area CDF and vertex normals of the part mesh at vertices V [Vn, 3] fp32 (CUDA)."""
     L = _lib.lib()
     nv, nf = part.num_vertices, part.num_faces
-    _check("V", V, torch.float32, (nv, 3))
+    _lib.check_tensor("V", V, torch.float32, (nv, 3), contiguous=False)
     V = V.contiguous()
-    dev, st = V.device, _st(V)
+    dev, st = V.device, _lib.stream(V)
     rec = torch.empty((nf, REC), dtype=torch.float32, device=dev)
     area = torch.empty(nf, dtype=torch.float64, device=dev)
     cdf = torch.empty(nf, dtype=torch.float64, device=dev)
     vn = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-    _lib.check(L.dwg_sigma_face_records(nv, _p(V), nf, _p(part.faces), _p(rec), _p(area), st), "dwg_sigma_face_records")
-    _lib.check(L.dwg_sigma_area_cdf(nf, _p(area), _p(cdf), st), "dwg_sigma_area_cdf")
-    _lib.check(L.dwg_sigma_vertex_normals(nv, _p(V), _p(part.faces), _p(part.vf_offsets), _p(part.vf_items), _p(vn), st),
+    _lib.check(L.dwg_sigma_face_records(nv, _lib.ptr(V), nf, _lib.ptr(part.faces), _lib.ptr(rec), _lib.ptr(area), st), "dwg_sigma_face_records")
+    _lib.check(L.dwg_sigma_area_cdf(nf, _lib.ptr(area), _lib.ptr(cdf), st), "dwg_sigma_area_cdf")
+    _lib.check(L.dwg_sigma_vertex_normals(nv, _lib.ptr(V), _lib.ptr(part.faces), _lib.ptr(part.vf_offsets), _lib.ptr(part.vf_items), _lib.ptr(vn), st),
                "dwg_sigma_vertex_normals")
     return rec, cdf, vn
 
@@ -91,7 +71,7 @@ def _prepare(V, part):
 def _sample(V, part, cdf, vn, draws, noise_range):
     L = _lib.lib()
     n = draws.shape[0]
-    _check("draws", draws, torch.float64, (n, 4))
+    _lib.check_tensor("draws", draws, torch.float64, (n, 4), contiguous=False)
     draws = draws.contiguous()
     dev = V.device
     pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -99,8 +79,8 @@ def _sample(V, part, cdf, vn, draws, noise_range):
     pn = torch.empty((n, 3), dtype=torch.float32, device=dev)
     noisy = torch.empty((n, 3), dtype=torch.float32, device=dev)
     if n:
-        _lib.check(L.dwg_sigma_sample(n, _p(draws), part.num_vertices, _p(V), part.num_faces, _p(part.faces), _p(cdf), _p(vn),
-                                      float(noise_range), _p(pts), _p(fid), _p(pn), _p(noisy), _st(V)), "dwg_sigma_sample")
+        _lib.check(L.dwg_sigma_sample(n, _lib.ptr(draws), part.num_vertices, _lib.ptr(V), part.num_faces, _lib.ptr(part.faces), _lib.ptr(cdf), _lib.ptr(vn),
+                                      float(noise_range), _lib.ptr(pts), _lib.ptr(fid), _lib.ptr(pn), _lib.ptr(noisy), _lib.stream(V)), "dwg_sigma_sample")
     return pts, fid, pn, noisy
 
 
@@ -115,7 +95,7 @@ def _distance(P, rec, closest_point=True):
         return d2, idx, C
     ws_bytes = L.dwg_sigma_distance_workspace_bytes(n, nf)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    _lib.check(L.dwg_sigma_point_mesh_distance(n, _p(P), nf, _p(rec), _p(d2), _p(idx), _p(C), _p(ws), ws_bytes, _st(P)),
+    _lib.check(L.dwg_sigma_point_mesh_distance(n, _lib.ptr(P), nf, _lib.ptr(rec), _lib.ptr(d2), _lib.ptr(idx), _lib.ptr(C), _lib.ptr(ws), ws_bytes, _lib.stream(P)),
                "dwg_sigma_point_mesh_distance")
     return d2, idx, C
 
@@ -127,14 +107,14 @@ def _keep_mask(d2, idx, thickness, wrist):
     kept = torch.zeros(1, dtype=torch.int32, device=d2.device)
     nf = 0 if wrist is None else wrist.numel()
     if n:
-        _lib.check(L.dwg_sigma_keep_mask(n, _p(d2), _p(idx), float(thickness), nf, _p(wrist), _p(keep), _p(kept), _st(d2)),
+        _lib.check(L.dwg_sigma_keep_mask(n, _lib.ptr(d2), _lib.ptr(idx), float(thickness), nf, _lib.ptr(wrist), _lib.ptr(keep), _lib.ptr(kept), _lib.stream(d2)),
                    "dwg_sigma_keep_mask")
     return keep, kept
 
 
 def _mesh_args(V, F_):
-    _check("V", V, torch.float32, (None, 3))
-    _check("F", F_, (torch.int32, torch.int64), (None, 3))
+    _lib.check_tensor("V", V, torch.float32, (None, 3), contiguous=False)
+    _lib.check_tensor("F", F_, (torch.int32, torch.int64), (None, 3), contiguous=False)
     if F_.shape[0] == 0:
         raise RuntimeError("F has no faces")
     faces = F_.detach().cpu().numpy()                                     # igl / trimesh API: the index range is checked on the host
@@ -145,11 +125,11 @@ def point_mesh_squared_distance(P, V, F_):
     """(sqrD [N] fp32, I [N] int64, C [N, 3] fp32): for each row of P [N, 3] fp32 the squared distance to the mesh (V [Vn, 3] fp32,
     F [Fn, 3] int), the index of the closest face (ties: the lowest index among minima equal within 5e-7 (1 + d)) and the closest
     point.  Degenerate faces count as their segments."""
-    _check("P", P, torch.float32, (None, 3))
+    _lib.check_tensor("P", P, torch.float32, (None, 3), contiguous=False)
     V, part = _mesh_args(V, F_)
     L = _lib.lib()
     rec = torch.empty((part.num_faces, REC), dtype=torch.float32, device=V.device)
-    _lib.check(L.dwg_sigma_face_records(part.num_vertices, _p(V), part.num_faces, _p(part.faces), _p(rec), None, _st(V)),
+    _lib.check(L.dwg_sigma_face_records(part.num_vertices, _lib.ptr(V), part.num_faces, _lib.ptr(part.faces), _lib.ptr(rec), None, _lib.stream(V)),
                "dwg_sigma_face_records")
     d2, idx, C = _distance(P.detach().contiguous(), rec)
     return d2, idx.long(), C

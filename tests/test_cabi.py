@@ -120,12 +120,21 @@ def _c_struct_layout(header, struct, fields, tmp_path):
     return int(out[0]), [int(v) for v in out[1:]]
 
 
+def _headers():
+    return {os.path.basename(h): open(h).read() for h in sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))}
+
+
 def test_ctypes_structures_have_the_layout_of_the_c_headers(tmp_path):
-    """The structs that cross the C-ABI by pointer: the ctypes mirrors must agree with include/*.h field for field."""
+    """The structs that cross the C-ABI by pointer: the ctypes mirrors must agree with include/*.h field for field, for every struct the
+    headers define."""
     from dreamwaltz_g_amd import gemm
-    for header, struct, mirror in (("dwg_raster.h", "dwg_raster_settings", _lib.RasterSettingsC), ("dwg_raster.h", "dwg_raster_frames", _lib.RasterFramesC),
-                                   ("dwg_gemm.h", "dwg_gemm_desc", gemm.GemmDesc), ("dwg_gaussian.h", "dwg_segment", _lib.SegmentC),
-                                   ("dwg_elementwise.h", "dwg_adam_group", _lib.AdamGroupC)):
+    found = [(h, m) for h, src in _headers().items() for m in re.findall(r"typedef\s+struct\s+(\w+)", src)]
+    assert {"dwg_nerf_field_desc", "dwg_nerf_field_grads", "dwg_scaler_state", "dwg_nerf_bg_desc", "dwg_gemm_desc"} <= {s for _, s in found}
+    assert sorted(s for _, s in found) == sorted(_lib.STRUCTS)
+    assert (_lib.RasterSettingsC, _lib.NerfFieldDescC, gemm.GemmDesc) == tuple(
+        _lib.STRUCTS[n] for n in ("dwg_raster_settings", "dwg_nerf_field_desc", "dwg_gemm_desc"))
+    for header, struct in found:
+        mirror = _lib.STRUCTS[struct]
         names = [f[0] for f in mirror._fields_]
         size, offsets = _c_struct_layout(header, struct, names, tmp_path)        # a field the header lacks fails to compile
         assert size == ctypes.sizeof(mirror), (struct, size, ctypes.sizeof(mirror))
@@ -133,6 +142,52 @@ def test_ctypes_structures_have_the_layout_of_the_c_headers(tmp_path):
         # and the header has no field the mirror lacks: the last mirrored field ends where the struct (padding aside) ends
         last = mirror._fields_[-1]
         assert offsets[-1] + ctypes.sizeof(last[1]) + 8 > size, struct
+
+
+def test_signatures_follow_the_headers_type_for_type():
+    """Hand-written expectations for prototypes that between them use every mapping rule of the binding."""
+    c, S = ctypes, _lib.SIGNATURES
+    i32, i64, u64, f32, f64, vp = c.c_int32, c.c_int64, c.c_uint64, c.c_float, c.c_double, c.c_void_p
+    assert S["dwg_image_loss_backward"] == (c.c_int, [i32] * 5 + [f64] * 2 + [vp, i64, i64, i64, i64] * 2 + [vp, vp, i32, vp, vp])
+    assert S["dwg_scaler_update"] == (c.c_int, [c.POINTER(_lib.ScalerStateC), f64, f64, i32, vp])
+    assert S["dwg_pc_select_above"] == (c.c_int, [u64, vp, f32, vp, u64, vp, vp, c.c_size_t, vp])
+    assert S["dwg_prof_query"] == (c.c_int, [c.c_char_p, vp, vp])
+    assert S["dwg_prof_dump"] == (i64, [vp, i64])                                   # a buffer the library writes: a data pointer
+    assert S["dwg_grads_nonfinite_slots"] == (i32, [i64])
+    assert S["dwg_gemm_workspace_bytes"] == (c.c_size_t, [c.POINTER(_lib.STRUCTS["dwg_gemm_desc"])])
+    assert S["dwg_raster_num_pairs_ptr"] == (vp, [vp])                              # an int restype would truncate the address
+    assert S["dwg_nerf_field_backward"] == (c.c_int, [c.POINTER(_lib.NerfFieldDescC), vp, u64, vp, vp, c.POINTER(_lib.NerfFieldGradsC), vp,
+                                                      c.c_size_t, vp])
+    assert S["dwg_grid_encode_forward"][1][4:10] == [c.c_uint32] * 4 + [f32, c.c_uint32]
+    assert S["dwg_graph_end_capture"] == (c.c_int, [vp, vp])                        # dwg_stream_t, dwg_graph_t*
+    assert len(S) == len(_declared_symbols())
+
+
+def test_constants_are_the_integer_defines_of_the_headers():
+    src = re.sub(r"/\*.*?\*/", "", "\n".join(_headers().values()), flags=re.S)
+    defines = dict(re.findall(r"^#define[ \t]+(DWG_\w+)[ \t]*(.*?)[ \t]*$", src, flags=re.M))
+    integers = {n: int(v.strip("()uU")) for n, v in defines.items() if re.fullmatch(r"\(?-?\d+[uU]?\)?", v)}
+    guards = {n for n, v in defines.items() if not v}
+    assert len(integers) >= 40 and len(guards) == len(_headers())
+    assert _lib.CONSTANTS == integers and not guards & set(_lib.CONSTANTS)
+    assert (_lib.CONSTANTS["DWG_E_ARG"], _lib.CONSTANTS["DWG_VIEW_BG_IMAGE"], _lib.CONSTANTS["DWG_ADAM_MAX_GROUPS"]) == (-1, 2, 16)
+    from dreamwaltz_g_amd import condition, gemm, pointcloud
+    assert (_lib.ADAM_MAX_GROUPS, condition.MAX_PEOPLE, pointcloud.MINMAX_PAIRS, gemm.F32X, gemm.ACT["geglu_pair"]) == (16, 16, 4096, 3, 6)
+
+
+def test_a_declaration_the_binding_cannot_read_raises_with_its_text():
+    import pytest
+    for text, decl in (("int dwg_new_entry(int32_t n, half* x, dwg_stream_t stream);", "int dwg_new_entry(int32_t n, half* x, dwg_stream_t stream)"),
+                       ("typedef struct dwg_new { int32_t n; long double v; } dwg_new;", "long double v"),
+                       ("typedef struct dwg_new { int32_t n; complex_t v[2]; } dwg_new;", "complex_t v[2]"),
+                       ("int dwg_new_entry(float x[3]);", "int dwg_new_entry(float x[3])")):
+        with pytest.raises(ValueError, match=re.escape(decl)) as e:
+            _lib.parse_headers({"dwg_types.h": _headers()["dwg_types.h"], "dwg_new.h": text})
+        assert "dwg_new.h" in str(e.value)
+    sigs, structs, consts = _lib.parse_headers({"dwg_new.h": "#define DWG_NEW_N 2\ntypedef struct dwg_new { float v[DWG_NEW_N]; } dwg_new;\n"
+                                                             "void dwg_new_entry(const dwg_new* d, const char* name);"})
+    assert sigs == {"dwg_new_entry": (None, [ctypes.POINTER(structs["dwg_new"]), ctypes.c_char_p])} and consts == {"DWG_NEW_N": 2}
+    assert ctypes.sizeof(structs["dwg_new"]) == 8
 
 
 def test_every_header_compiles_standalone_as_c_and_cxx(tmp_path):

@@ -156,7 +156,7 @@ def test_learned_background_refuses_bad_arguments_before_the_library(monkeypatch
     with pytest.raises(RuntimeError, match="degree"):
         nb.freq_encode(d, degree=0)
     # the fake device tensor passes the device checks: what is left to refuse is the shape of the network
-    monkeypatch.setattr(nb, "_check", lambda *a, **k: None)
+    monkeypatch.setattr(_lib, "check_tensor", lambda *a, **k: None)
     for kw, word in ((dict(layers=4), "layers"), (dict(hidden=48), "hidden width"), (dict(hidden=128), "hidden width"), (dict(C=5), "output width"),
                      (dict(C=2), "output width")):
         e, b = bc.make_bg(**kw)
