@@ -13,12 +13,23 @@ indices read from device memory -- no host work or sync per frame, and a capture
 
 Frame indices behave like the reference's list: a negative index counts from the end, an index outside [-T, T) raises IndexError.  That
 check is made on the host for Python ints; a device index tensor (GraphedAnimation's static input) is used as it is: the kernel wraps
-negative values once and clamps the rest for memory safety.  No CPU fallback: image and alpha must be fp32 CUDA tensors."""
+negative values once and clamps the rest for memory safety.  No CPU fallback: image and alpha must be fp32 CUDA tensors.
+
+The learned MLP background of stage II (boundary B23: the reference's MLPBackground, core/system/background.py:55-89, composited by
+core/system/scene.py:161-164) is here too:
+
+  MLPBackground()                                       encoder_bg = FreqEncoder(3, 4), bg_net = MLP(27, 3, 16, 2); forward(data, skip_bg) ->
+                                                        [B, H, W, 3]; get_optimizer(cfg) -> optim.FlatAdan with the reference's values;
+                                                        from_reference(ref_bg)
+  background_dirs(c2w, intrinsics, H, W)                the unit view direction of every pixel of F cameras, one launch
+  mlp_composite(image, alpha, image_bg)                 image + image_bg * (1 - alpha): autograd over one launch each way, gradients to
+                                                        image, alpha and image_bg"""
 import operator
 import os
 
 import numpy as np
 import torch
+import torch.nn as nn
 
 from . import _lib
 
@@ -255,3 +266,144 @@ def video_composite(image: torch.Tensor, alpha: torch.Tensor, background: VideoB
     alpha = alpha.contiguous()
     idx = background.index_tensor(frame_index, image.device, count=F)
     return _VideoComposite.apply(image, alpha, background, idx)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# The learned (MLP) background of stage II (boundary B23: the reference's MLPBackground, core/system/background.py:55-89, and its
+# compositing in Scene.forward, core/system/scene.py:161-164)
+# --------------------------------------------------------------------------------------------------------------------------------------
+CAMERA_FLOATS = _lib.CONSTANTS["DWG_BACKGROUND_CAMERA_FLOATS"]
+
+
+def pack_cameras(c2w: torch.Tensor, intrinsics: torch.Tensor) -> torch.Tensor:
+    """c2w [F, 4, 4] (or [F, 3, 4]) and intrinsics [F, 3, 3] -> the kernel's camera rows [F, 16] fp32: rows 0..2 of c2w, then fx, fy, cx,
+    cy.  Device tensors stay on the device (no host read)."""
+    if c2w.dim() != 3 or c2w.shape[1] < 3 or c2w.shape[2] != 4 or intrinsics.dim() != 3 or tuple(intrinsics.shape[1:]) != (3, 3):
+        raise RuntimeError("c2w must be [F, 4, 4] and intrinsics [F, 3, 3], got %s and %s" % (tuple(c2w.shape), tuple(intrinsics.shape)))
+    if intrinsics.shape[0] != c2w.shape[0]:
+        raise RuntimeError("%d cameras and %d intrinsics" % (c2w.shape[0], intrinsics.shape[0]))
+    K = intrinsics.to(device=c2w.device, dtype=torch.float32)
+    return torch.cat([c2w[:, :3, :].to(torch.float32).reshape(-1, 12), K[:, 0, 0:1], K[:, 1, 1:2], K[:, 0, 2:3], K[:, 1, 2:3]], dim=1).contiguous()
+
+
+def background_dirs(c2w: torch.Tensor, intrinsics: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """The unit view direction of every pixel of F cameras -> [F * H * W, 3] fp32 (one launch, csrc/background.hip k_background_dirs):
+    get_rays' rays_d with N = -1 (core/nerf/nerf_utils.py:124-129) divided by its norm (background.py:78).  No gradients."""
+    H, W = int(H), int(W)
+    cams = pack_cameras(c2w.detach(), intrinsics.detach())
+    _lib.check_tensor("c2w", cams)
+    F = int(cams.shape[0])
+    if F < 1 or H < 1 or W < 1:
+        raise RuntimeError("background_dirs needs at least one camera and one pixel, got F=%d H=%d W=%d" % (F, H, W))
+    dirs = torch.empty((F * H * W, 3), dtype=torch.float32, device=cams.device)
+    with torch.cuda.device(cams.device):
+        _lib.check(_lib.lib().dwg_background_dirs(F, _lib.ptr(cams), H, W, _lib.ptr(dirs), _lib.stream(cams.device)), "dwg_background_dirs")
+    return dirs
+
+
+class MLPBackground(nn.Module):
+    """The reference's MLPBackground: a degree-4 frequency encoding of the pixel's view direction (27 columns), MLP(27, 3, 16, 2) and a
+    sigmoid, on the fused kernels of nerf_background (B22) at that shape.  Checkpoint keys are the reference's: bg_net.net.{0,1}.{weight,
+    bias} (under `background.` in a Scene)."""
+
+    def __init__(self) -> None:
+        super().__init__()
+        from . import nerf_background, nerf_model
+        self.encoder_bg = nerf_background.FreqEncoder(3, 4)
+        self.bg_net = nerf_model.MLP(self.encoder_bg.output_dim, 3, 16, 2)
+        self._optimizer = None
+
+    @classmethod
+    def from_reference(cls, ref_bg):
+        """Adopt the reference's MLPBackground: its bg_net's weights and biases (the frequency encoder has none)."""
+        self = cls()
+        ref = [p for lin in ref_bg.bg_net.net for p in (lin.weight, lin.bias)]
+        own = [p for lin in self.bg_net.net for p in (lin.weight, lin.bias)]
+        if [tuple(p.shape) for p in ref] != [tuple(p.shape) for p in own]:
+            raise RuntimeError("from_reference: bg_net has shapes %s, expected %s" % ([tuple(p.shape) for p in ref], [tuple(p.shape) for p in own]))
+        with torch.no_grad():
+            for p, q in zip(own, ref):
+                p.copy_(q.detach().to(p.dtype))
+        self.reference = [ref_bg]            # kept alive, not registered as a submodule
+        return self
+
+    def directions(self, data) -> torch.Tensor:
+        if 'c2w' not in data or 'intrinsics' not in data:
+            raise KeyError("MLPBackground reads data['c2w'] [B, 4, 4] and data['intrinsics'] [B, 3, 3] (core/system/background.py:69-70)")
+        return background_dirs(data['c2w'], data['intrinsics'], data['image_height'], data['image_width'])
+
+    def forward(self, data, skip_bg=False):
+        """data: c2w [B, 4, 4], intrinsics [B, 3, 3], image_height, image_width -> image [B, H, W, 3] (zeros under skip_bg).  Two launches:
+        the directions, then encoding + network + sigmoid."""
+        from . import nerf_background
+        c2w = data['c2w']
+        B, H, W = int(c2w.shape[0]), int(data['image_height']), int(data['image_width'])
+        if skip_bg:
+            return torch.zeros(B, H, W, 3, device=c2w.device)
+        image = nerf_background.learned_background(self.directions(data), self.encoder_bg, self.bg_net, sigmoid=True, precision=0)
+        return image.view(B, H, W, 3)
+
+    def get_optimizer(self, cfg=None):
+        """The reference's Adan(lr=1e-3, eps=1e-8, weight_decay=2e-5, max_grad_norm=5.0) over this module's parameters as an
+        optim.FlatAdan (built once: it re-homes the parameters into its flat buffers)."""
+        from . import optim
+        if self._optimizer is None:
+            params = list(self.parameters())
+            spec = optim.AdanSpec([{'params': params}], lr=0.001, eps=1e-8, weight_decay=2e-5, max_grad_norm=5.0)
+            self._optimizer = optim.FlatAdan(spec, params[0].device, name="background")
+        return self._optimizer
+
+
+class _MLPComposite(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, alpha, image_bg):
+        F, H, W = (int(s) for s in image.shape[:3])
+        out = torch.empty_strided(image.shape, image.stride(), dtype=torch.float32, device=image.device)
+        sf, sp, sc = _planar_strides(image, H, W)
+        with torch.cuda.device(image.device):
+            rc = _lib.lib().dwg_mlp_composite_forward(F, H, W, _lib.ptr(image), _lib.ptr(alpha), sf, sp, sc, _lib.ptr(image_bg),
+                                                      0 if image_bg.shape[0] == 1 and F > 1 else H * W * 3, _lib.ptr(out), _lib.stream(image.device))
+        _lib.check(rc, "dwg_mlp_composite_forward")
+        ctx.save_for_backward(alpha, image_bg)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        alpha, image_bg = ctx.saved_tensors
+        need_fg, need_alpha, need_bg = ctx.needs_input_grad
+        d_alpha = d_bg = None
+        if need_alpha or need_bg:
+            F, H, W = (int(s) for s in d_out.shape[:3])
+            if image_bg.shape[0] != F:
+                raise RuntimeError("mlp_composite: no backward through a background shared by several frames")
+            st = _planar_strides(d_out, H, W)
+            if st is None or d_out.dtype != torch.float32 or not _dense(d_out):
+                d_out = d_out.float().contiguous()
+                st = _planar_strides(d_out, H, W)
+            if need_alpha:
+                d_alpha = torch.empty((F, H, W, 1), dtype=torch.float32, device=d_out.device)
+            if need_bg:
+                d_bg = torch.empty((F, H, W, 3), dtype=torch.float32, device=d_out.device)
+            with torch.cuda.device(d_out.device):
+                rc = _lib.lib().dwg_mlp_composite_backward(F, H, W, _lib.ptr(d_out), st[0], st[1], st[2], _lib.ptr(alpha), _lib.ptr(image_bg),
+                                                           _lib.ptr(d_alpha), _lib.ptr(d_bg), _lib.stream(d_out.device))
+            _lib.check(rc, "dwg_mlp_composite_backward")
+        return (d_out if need_fg else None), d_alpha, d_bg
+
+
+def mlp_composite(image: torch.Tensor, alpha: torch.Tensor, image_bg: torch.Tensor) -> torch.Tensor:
+    """image [F, H, W, 3] fp32 (any strides whose H, W merge: the renderer's planar view included), alpha [F, H, W, 1] fp32, image_bg
+    [F, H, W, 3] fp32 -- or [1, H, W, 3], one background under all F frames (no gradients then) -- -> image + image_bg * (1 - alpha) at
+    image's strides, one launch.  Differentiable in image (d = d_out), alpha (d = -sum_c d_out_c * bg_c) and image_bg
+    (d = d_out * (1 - alpha)): one launch for the last two."""
+    if image.dim() != 4 or image.shape[3] != 3:
+        raise RuntimeError("image must be [F, H, W, 3], got %s" % (tuple(image.shape),))
+    F, H, W = (int(s) for s in image.shape[:3])
+    _lib.check_tensor("image", image, shape=(F, H, W, 3), contiguous=False)
+    _lib.check_tensor("alpha", alpha, shape=(F, H, W, 1), contiguous=False, device=image.device)
+    _lib.check_tensor("image_bg", image_bg, shape=(None, H, W, 3), contiguous=False, device=image.device)
+    if image_bg.shape[0] != F and not (image_bg.shape[0] == 1 and not (torch.is_grad_enabled() and image_bg.requires_grad)):
+        raise RuntimeError("image_bg holds %d frames for %d images" % (image_bg.shape[0], F))
+    if _planar_strides(image, H, W) is None or not _dense(image):
+        image = image.contiguous()
+    return _MLPComposite.apply(image, alpha.contiguous(), image_bg.contiguous())

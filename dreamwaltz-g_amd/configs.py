@@ -53,6 +53,7 @@ class RenderConfig:
     use_fixed_n_gaussians: Optional[int] = None
     avatar_transl: Optional[str] = None
     avatar_scale: Optional[str] = None
+    use_mlp_background: bool = False                 # the learned MLP background (scene.py:227-228; background.MLPBackground, boundary B23)
     use_video_background: Optional[str] = None       # a video file (or "motionx_reenact,<name>" through the reference): scene.py:229-230
     use_densifier: bool = False                      # configs/__init__.py:159-171 (off in every shipped recipe)
     densify_from_iter: Optional[int] = None

@@ -2,6 +2,9 @@
 // source pixel fetched from a device-resident uint8 BGR frame store, resampled with OpenCV's 8-bit INTER_LINEAR rule when the sizes
 // differ, divided by 255 and composited as `fg + bg * (1 - alpha)`.
 //
+// Also here (boundary B23, the stage-II learned MLP background): the view directions of every pixel of F cameras, and the composite of a
+// background image read from memory with its backward to alpha and to that image -- the same `Layout` and the same statements.
+//
 // Traffic per 512^2 frame: 12 B fg + 4 B alpha read, 12 B image + 12 B image_bg written per pixel (~10.5 MB) plus the source bytes;
 // a few microseconds at HBM rates.  fg / image / d_image take the caller's strides: the renderer's image is a channel-planar view
 // ([F, 3, H, W] permuted), and the composite keeps that layout as torch's elementwise ops would.  The backward recomputes the
@@ -9,6 +12,7 @@
 #include "dwg_common.h"
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_background.h"
+#include "view_math.h"
 
 #include <math.h>
 
@@ -128,6 +132,65 @@ __global__ __launch_bounds__(kBlock) void k_video_composite_bwd(int W, int HW, c
     d_alpha[px] = -acc;
 }
 
+// ---- the learned (MLP) background of stage II (boundary B23) -----------------------------------------------------------------------
+// One lane per pixel of F cameras: get_rays' direction (view_math.h view_ray: pixel centre, safe_normalize, rotation), then the
+// reference's second normalisation d / ||d|| as a plain division (core/system/background.py:78).
+__global__ __launch_bounds__(kBlock) void k_background_dirs(int W, int HW, const float* __restrict__ cameras, float* __restrict__ dirs) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= HW) return;
+    const int f = blockIdx.y;
+    const float* cam = cameras + (size_t)f * DWG_BACKGROUND_CAMERA_FLOATS;
+    const float K[9] = {cam[12], 0.f, cam[14], 0.f, cam[13], cam[15], 0.f, 0.f, 1.f};
+    const int row = p / W, col = p - row * W;
+    float d[3];
+    view_ray(cam, K, (uint32_t)row, (uint32_t)col, d);
+    const float s = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+    const float len = sqrtf(s);
+    float* o = dirs + ((size_t)f * HW + p) * 3;
+    o[0] = d[0] / len; o[1] = d[1] / len; o[2] = d[2] / len;
+}
+
+// image = fg + bg * (1 - alpha): the statements of k_video_composite with the background read from memory (bg_sf: its frame stride in
+// elements, 0 when all frames share one background).
+__global__ __launch_bounds__(kBlock) void k_mlp_composite(int HW, const float* __restrict__ fg, const float* __restrict__ alpha, Layout L,
+                                                          const float* __restrict__ bg, int64_t bg_sf, float* __restrict__ image) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= HW) return;
+    const int f = blockIdx.y;
+    const size_t px = (size_t)f * HW + p;
+    const float* b = bg + (int64_t)f * bg_sf + (int64_t)p * 3;
+    const float om = 1.0f - alpha[px];
+    const int64_t q = (int64_t)f * L.sf + (int64_t)p * L.sp;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float t = b[c] * om;
+        image[q + c * L.sc] = fg[q + c * L.sc] + t;
+    }
+}
+
+// d_alpha = -((d_r bg_r + d_g bg_g) + d_b bg_b), d_bg = d * (1 - alpha); either output may be NULL.
+__global__ __launch_bounds__(kBlock) void k_mlp_composite_bwd(int HW, const float* __restrict__ d_image, Layout L, const float* __restrict__ alpha,
+                                                              const float* __restrict__ bg, float* __restrict__ d_alpha,
+                                                              float* __restrict__ d_bg) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= HW) return;
+    const int f = blockIdx.y;
+    const size_t px = (size_t)f * HW + p;
+    const float* g = d_image + (int64_t)f * L.sf + (int64_t)p * L.sp;
+    const float g0 = g[0], g1 = g[L.sc], g2 = g[2 * L.sc];
+    if (d_alpha) {
+        const float* b = bg + px * 3;
+        float acc = g0 * b[0];
+        acc = acc + g1 * b[1];
+        acc = acc + g2 * b[2];
+        d_alpha[px] = -acc;
+    }
+    if (d_bg) {
+        const float om = 1.0f - alpha[px];
+        d_bg[px * 3] = g0 * om; d_bg[px * 3 + 1] = g1 * om; d_bg[px * 3 + 2] = g2 * om;
+    }
+}
+
 inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
 // the resample mode and scales of cv2.resize(frame, (W, H)) for an (h, w) frame; false on sizes the kernels do not take
@@ -182,6 +245,44 @@ int dwg_video_composite_backward(int32_t F, int32_t H, int32_t W, const float* d
     const int HW = H * W;
     DWG_LAUNCH("video_composite_bwd", k_video_composite_bwd, dim3(dwg_cdiv(HW, kBlock), F), dim3(kBlock), 0, (hipStream_t)stream_, W, HW,
                d_image, L, s, d_alpha);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+static bool image_dims(int32_t F, int32_t H, int32_t W) {
+    return F > 0 && H > 0 && W > 0 && F <= 65535 && (int64_t)H * W <= (int64_t)0x7fffffff - kBlock;
+}
+
+int dwg_background_dirs(int32_t F, const float* cameras, int32_t H, int32_t W, float* dirs, dwg_stream_t stream_) {
+    if (!image_dims(F, H, W) || !cameras || !dirs || !aligned4(cameras) || !aligned4(dirs)) return DWG_E_ARG;
+    const int HW = H * W;
+    DWG_LAUNCH("background_dirs", k_background_dirs, dim3(dwg_cdiv(HW, kBlock), F), dim3(kBlock), 0, (hipStream_t)stream_, W, HW, cameras, dirs);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_mlp_composite_forward(int32_t F, int32_t H, int32_t W, const float* fg, const float* alpha, int64_t sf, int64_t sp, int64_t sc,
+                              const float* bg, int64_t bg_frame_stride, float* image, dwg_stream_t stream_) {
+    if (!image_dims(F, H, W) || !fg || !alpha || !bg || !image) return DWG_E_ARG;
+    if (!aligned4(fg) || !aligned4(alpha) || !aligned4(bg) || !aligned4(image) || sf < 0 || sp < 0 || sc < 0) return DWG_E_ARG;
+    const int HW = H * W;
+    if (bg_frame_stride != 0 && bg_frame_stride != (int64_t)HW * 3) return DWG_E_ARG;
+    const Layout L{sf, sp, sc};
+    DWG_LAUNCH("mlp_composite", k_mlp_composite, dim3(dwg_cdiv(HW, kBlock), F), dim3(kBlock), 0, (hipStream_t)stream_, HW, fg, alpha, L, bg,
+               bg_frame_stride, image);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_mlp_composite_backward(int32_t F, int32_t H, int32_t W, const float* d_image, int64_t sf, int64_t sp, int64_t sc, const float* alpha,
+                               const float* bg, float* d_alpha, float* d_bg, dwg_stream_t stream_) {
+    if (!image_dims(F, H, W) || !d_image || !aligned4(d_image) || sf < 0 || sp < 0 || sc < 0) return DWG_E_ARG;
+    if ((!d_alpha && !d_bg) || (d_alpha && !bg) || (d_bg && !alpha)) return DWG_E_ARG;
+    if (!aligned4(alpha) || !aligned4(bg) || !aligned4(d_alpha) || !aligned4(d_bg)) return DWG_E_ARG;
+    const Layout L{sf, sp, sc};
+    const int HW = H * W;
+    DWG_LAUNCH("mlp_composite_bwd", k_mlp_composite_bwd, dim3(dwg_cdiv(HW, kBlock), F), dim3(kBlock), 0, (hipStream_t)stream_, HW, d_image, L,
+               alpha, bg, d_alpha, d_bg);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

@@ -11,6 +11,10 @@ and the trainer loops `optimizer.zero_grad()`, `optimizer.update_learning_rate(.
 them (core/trainer.py:861-890).  Here every one of those objects is a VIEW of one flat fp32 parameter buffer with flat gradient /
 first-moment / second-moment buffers next to it: the multi-view step all-reduces ONE tensor over RCCL, and each view's `step()` is
 a fused Adam launch per learning-rate group (csrc/elementwise.hip k_adam through include/dwg_elementwise.h).
+
+The stage-II learned MLP background brings its own optimizer, `MLPBackground.get_optimizer()` (core/system/background.py:86-89): Adan
+(core/optim/adan.py).  Here that is FlatAdan (boundary B23): flat buffers of its own and three launches a step (csrc/adan.hip through
+include/dwg_adan.h), with the clipping factor and the step counts kept on the device.
 """
 import ctypes
 import math
@@ -447,3 +451,159 @@ def resize_flat_params(opts: FlatOptimizerDict, new_values: Dict[torch.nn.Parame
         o.start = min(r[0] for r in ranges)
         o.end = max(r[1] for r in ranges)
     return renamed
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------
+# Adan (boundary B23): the optimizer of the stage-II learned MLP background, fused on flat buffers of its own
+# ----------------------------------------------------------------------------------------------------------------------------------------
+class AdanSpec:
+    """What the reference's Adan (core/optim/adan.py:47-78) is made of: param groups (each may override lr, betas, eps, weight_decay and
+    no_prox) and the optimizer-wide max_grad_norm (0: no clipping)."""
+
+    def __init__(self, groups: List[dict], lr=1e-3, betas=(0.98, 0.92, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0, no_prox=False):
+        if not 0.0 <= max_grad_norm:
+            raise ValueError('Invalid Max grad norm: {}'.format(max_grad_norm))
+        if not 0.0 <= lr:
+            raise ValueError('Invalid learning rate: {}'.format(lr))
+        if not 0.0 <= eps:
+            raise ValueError('Invalid epsilon value: {}'.format(eps))
+        for i in range(3):
+            if not 0.0 <= betas[i] < 1.0:
+                raise ValueError('Invalid beta parameter at index {}: {}'.format(i, betas[i]))
+        self.groups, self.lr, self.betas, self.eps, self.weight_decay = groups, lr, tuple(betas), eps, weight_decay
+        self.max_grad_norm, self.no_prox = float(max_grad_norm), bool(no_prox)
+
+
+class FlatAdan:
+    """The reference's Adan on flat fp32 buffers it OWNS: parameters, gradient (FlatBuffers: 16-byte aligned slices, the Parameters re-homed
+    so that `.data` / `.grad` are views, a post-accumulate hook recording participation) and the four state buffers exp_avg, exp_avg_sq,
+    exp_avg_diff and neg_pre_grad (minus the previous clipped gradient, the reference's sign).  A step is three launches
+    (include/dwg_adan.h) and no host read: the sum of squares of the whole gradient, the one-workgroup preparation (clipping factor over
+    ALL groups, every group's step count + 1 on the device, the groups' scalars), the update of the participating groups.  The surface is
+    what the trainer and a disabled GradScaler use on the reference's object: param_groups, zero_grad, step, state_dict /
+    load_state_dict, grad_scale.  The gradient buffer stays as autograd wrote it (the reference scales it in place by the clipping
+    factor; nothing reads it before the next zero_grad)."""
+    owns_buffers = True          # not a view of a FlatOptimizerDict's buffers: FlatOptimizerDict.zero_grad() does not reach it
+
+    def __init__(self, spec: AdanSpec, device, name: str = "adan"):
+        if not spec.groups or len(spec.groups) > _lib.CONSTANTS["DWG_ADAN_MAX_GROUPS"]:
+            raise RuntimeError("FlatAdan takes 1..%d param groups, got %d" % (_lib.CONSTANTS["DWG_ADAN_MAX_GROUPS"], len(spec.groups)))
+        self.name, self.spec = name, spec
+        for g in spec.groups:
+            g['params'] = list(g['params'])
+        params = [p for g in spec.groups for p in g['params']]
+        if any(p.dtype != torch.float32 for p in params):
+            raise RuntimeError("FlatAdan steps fp32 parameters")
+        self.buf = FlatBuffers(params, device)
+        self.exp_avg_diff = torch.zeros(self.buf.total, device=device)
+        self.neg_pre_grad = torch.zeros(self.buf.total, device=device)
+        self.max_grad_norm = float(spec.max_grad_norm)
+        self.param_groups = []
+        for g, (start, end) in zip(spec.groups, _group_ranges({name: spec}, self.buf)[name]):
+            pg = dict(g)
+            pg.update(lr=g.get('lr', spec.lr), betas=tuple(g.get('betas', spec.betas)), eps=g.get('eps', spec.eps),
+                      weight_decay=g.get('weight_decay', spec.weight_decay), no_prox=bool(g.get('no_prox', spec.no_prox)),
+                      max_grad_norm=self.max_grad_norm, start=start, end=end, step=0, has_prev=False)
+            self.param_groups.append(pg)
+        G = len(self.param_groups)
+        self.grad_scale = 1.0
+        self._steps = torch.zeros(G, dtype=torch.int32, device=device)                        # the groups' step counts: authoritative
+        self._rows = torch.zeros(G, _lib.CONSTANTS["DWG_ADAN_ROW"], device=device)
+        self._partials = torch.zeros(_lib.CONSTANTS["DWG_ADAN_MAX_SLOTS"], dtype=torch.float64, device=device)
+
+    # FlatBuffers' two moment buffers under the reference's names (exp_avg_diff and neg_pre_grad are this object's own)
+    exp_avg = property(lambda self: self.buf.m)
+    exp_avg_sq = property(lambda self: self.buf.v)
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.buf.grad.zero_()
+        self.buf.tracking = False
+        for pg in self.param_groups:
+            for p in pg['params']:
+                p._dwg_touched = False
+
+    def participating(self, participation=None):
+        """Indices of the groups this step updates, as FlatOptimizer.step decides it: an empty group never; `participation` (one bool per
+        group) when the caller decides; else, once some backward recorded participation, the groups with a touched parameter; else all."""
+        out = []
+        for gi, pg in enumerate(self.param_groups):
+            if pg["end"] <= pg["start"]:
+                continue
+            if participation is not None:
+                if not participation[gi]:
+                    continue
+            elif self.buf.tracking and not any(getattr(p, "_dwg_touched", False) for p in pg['params']):
+                continue
+            out.append(gi)
+        return out
+
+    def step(self, participation=None):
+        """One Adan step.  Every group ages (the reference counts a group's step whether or not any of its parameters had a gradient,
+        adan.py:143-146); a group none of whose parameters took part is otherwise untouched."""
+        took_part = self.participating(participation)
+        PARAM_EPOCH[0] += 1
+        b = self.buf
+        if b.total == 0:
+            return
+        L = _lib.lib()
+        st = _lib.stream(b.flat.device)
+        nslots = 0
+        if self.max_grad_norm > 0:
+            nslots = int(L.dwg_adan_sumsq_slots(b.total))
+            _lib.check(L.dwg_adan_sumsq(b.total, _lib.ptr(b.grad), _lib.ptr(self._partials), st), "dwg_adan_sumsq")
+        G = len(self.param_groups)
+        hyper = (_lib.STRUCTS["dwg_adan_hyper"] * G)()
+        first_mask = 0
+        for gi, pg in enumerate(self.param_groups):
+            h = hyper[gi]
+            h.lr, h.eps, h.weight_decay, h.no_prox = float(pg["lr"]), float(pg["eps"]), float(pg["weight_decay"]), int(bool(pg["no_prox"]))
+            h.beta1, h.beta2, h.beta3 = (float(x) for x in pg["betas"])
+            if not pg["has_prev"]:
+                first_mask |= 1 << gi
+        _lib.check(L.dwg_adan_prepare(nslots, _lib.ptr(self._partials) if nslots else None, G, hyper, first_mask, self.max_grad_norm,
+                                      float(self.grad_scale), _lib.ptr(self._steps), _lib.ptr(self._rows), st), "dwg_adan_prepare")
+        if not took_part:
+            return
+        groups = (_lib.STRUCTS["dwg_adan_group"] * len(took_part))()
+        for k, gi in enumerate(took_part):
+            pg = self.param_groups[gi]
+            n, off = pg["end"] - pg["start"], pg["start"] * 4
+            a = groups[k]
+            a.param, a.grad, a.exp_avg, a.exp_avg_sq = b.flat.data_ptr() + off, b.grad.data_ptr() + off, b.m.data_ptr() + off, b.v.data_ptr() + off
+            a.exp_avg_diff, a.neg_pre_grad = self.exp_avg_diff.data_ptr() + off, self.neg_pre_grad.data_ptr() + off
+            a.n, a.hyper_row = n, gi
+            pg["has_prev"] = True
+        _lib.check(L.dwg_adan_step_groups_dev(len(took_part), groups, _lib.ptr(self._rows), st), "dwg_adan_step_groups_dev")
+
+    def step_scaled(self, scaler, participation=None):
+        raise NotImplementedError("FlatAdan.step_scaled: the Adan step under a loss scaler is not built (stage II never runs under optim.fp16)")
+
+    def device_step_counts(self):
+        """The per-group step counts (a host read)."""
+        return [int(t) for t in self._steps.tolist()]
+
+    def state_dict(self):
+        """The reference's state, flat: per group its hyper-parameters and `step` (read back from the device here: checkpoint time), and
+        the four state buffers under the reference's keys."""
+        for pg, t in zip(self.param_groups, self.device_step_counts()):
+            pg["step"] = t
+        b = self.buf
+        return {"max_grad_norm": self.max_grad_norm,
+                "param_groups": [{k: v for k, v in pg.items() if k != 'params'} for pg in self.param_groups],
+                "exp_avg": b.m.clone(), "exp_avg_sq": b.v.clone(), "exp_avg_diff": self.exp_avg_diff.clone(), "neg_pre_grad": self.neg_pre_grad.clone()}
+
+    def load_state_dict(self, sd):
+        if len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError("FlatAdan.load_state_dict: %d param groups in the state, %d here" % (len(sd["param_groups"]), len(self.param_groups)))
+        self.max_grad_norm = float(sd.get("max_grad_norm", self.max_grad_norm))
+        for pg, s in zip(self.param_groups, sd["param_groups"]):
+            for k in ("lr", "betas", "eps", "weight_decay", "no_prox"):
+                if k in s:
+                    pg[k] = tuple(s[k]) if k == "betas" else s[k]
+            pg["step"] = int(s.get("step", 0))
+            pg["has_prev"] = bool(s.get("has_prev", pg["step"] > 0))
+            pg["max_grad_norm"] = self.max_grad_norm
+        b = self.buf
+        for dst, key in ((b.m, "exp_avg"), (b.v, "exp_avg_sq"), (self.exp_avg_diff, "exp_avg_diff"), (self.neg_pre_grad, "neg_pre_grad")):
+            dst.copy_(sd[key])
+        self._steps.copy_(torch.tensor([pg["step"] for pg in self.param_groups], dtype=torch.int32))

@@ -1,8 +1,11 @@
 """Mirror of Scene (/root/reference/core/system/scene.py:15-168; SURVEY.md section 8a row R7, boundary B5): avatar_forward
 (optional per-avatar scale / translation), multi-avatar merge, the debug overrides, GaussianRenderer.render, and the background
-compositing `image + bg (1 - alpha)` for bg_mode in {black, white, gray} and for a video background (background.VideoBackground:
-the frames on the device, one launch per frame chain).  Learned (MLP) and Gaussian backgrounds are outside the hot path
-(scene.py:123-132,162-165) and are rejected."""
+compositing `image + bg (1 - alpha)` for bg_mode in {black, white, gray}, for a video background (background.VideoBackground:
+the frames on the device, one launch per frame chain) and for the learned MLP background (boundary B23, background.MLPBackground:
+directions, the fused encoding + network + sigmoid, and the composite -- three launches forward; gradients to alpha and to the
+background's weights).  Precedence as the reference's (scene.py:153-166): a pure-colour bg_mode, then video, then MLP.  The Gaussian
+(.ply) background (scene.py:123-132) is outside the hot path and is rejected, and so is every object that is not one of the package's
+own two background classes."""
 from typing import Iterable, Optional
 
 import contextlib
@@ -11,7 +14,8 @@ import torch
 import torch.nn as nn
 
 from .avatar import DreamWaltzG, GaussianOutput, merge_gaussians
-from .background import VideoBackground, video_composite
+from . import optim as _optim
+from .background import MLPBackground, VideoBackground, mlp_composite, video_composite
 from .renderer import GaussianRenderer
 
 
@@ -39,9 +43,10 @@ def downsample_gaussians(gaussians: GaussianOutput, n: int) -> GaussianOutput:
 class Scene(nn.Module):
     def __init__(self, cfg, avatar, background=None, async_pair_count=False) -> None:
         super().__init__()
-        if background is not None and not isinstance(background, VideoBackground):
-            raise NotImplementedError("learned (MLP) and Gaussian backgrounds are outside the SDS hot path (scene.py:123-132,162-165); "
-                                      "a video background is a background.VideoBackground")
+        if background is not None and not isinstance(background, VideoBackground) and type(background) is not MLPBackground:
+            raise NotImplementedError("Gaussian backgrounds are outside the SDS hot path (scene.py:123-132); a video background is a "
+                                      "background.VideoBackground and a learned one a background.MLPBackground, got %s.%s"
+                                      % (type(background).__module__, type(background).__name__))
         self.device = torch.device(cfg.device)
         if isinstance(avatar, DreamWaltzG):
             self.avatar, self.avatars = avatar, None
@@ -103,6 +108,28 @@ class Scene(nn.Module):
             raise ValueError("a video background needs one frame index per frame: frame_indices= or data['frame_index']")
         return idx
 
+    @property
+    def mlp_background(self):
+        """The learned background, or None."""
+        return self.background if type(self.background) is MLPBackground else None
+
+    def _mlp_frames_background(self, data, F):
+        """image_bg of F playback frames from ONE directions launch and ONE network launch: [F, H, W, 3] for a list of F camera dicts,
+        [1, H, W, 3] for one shared camera (computed once)."""
+        if isinstance(data, (list, tuple)):
+            if len(data) != F:
+                raise ValueError("%d camera dicts for %d frames" % (len(data), F))
+            H, W = int(data[0]['image_height']), int(data[0]['image_width'])
+            if any((int(d['image_height']), int(d['image_width'])) != (H, W) for d in data):
+                raise ValueError("the frames of one forward_frames call share one image size")
+            data = {'c2w': torch.cat([d['c2w'][:1] for d in data]), 'intrinsics': torch.cat([d['intrinsics'][:1] for d in data]),
+                    'image_height': H, 'image_width': W}
+        else:
+            data = {'c2w': data['c2w'][:1], 'intrinsics': data['intrinsics'][:1], 'image_height': data['image_height'],
+                    'image_width': data['image_width']}
+        with torch.no_grad():
+            return self.background(data)
+
     def forward_frames(self, data: dict, poses, bg_mode: Optional[str] = None, frozen_avatar: bool = False, frame_indices=None) -> dict:
         """Playback of F pose frames under one camera (`data`: the loader's dict) or each under its own (`data`: a list of F dicts, as the
         reference's evaluation loader yields them): `animate` per pose, then ONE rasterizer launch chain for all of them
@@ -143,11 +170,17 @@ class Scene(nn.Module):
             outputs['image_bg'] = self.pure_colors.get_background_like(bg_mode, outputs['image'])
             outputs['image_fg'] = outputs['image']
             outputs['image'] = outputs['image'] + outputs['image_bg'] * (1 - outputs['alpha'])
-        elif self.background is not None:
+        elif isinstance(self.background, VideoBackground):
             image, outputs['image_bg'] = video_composite(outputs['image'], outputs['alpha'], self.background,
                                                          self._video_indices(data, frame_indices))
             outputs['image_fg'] = outputs['image']
             outputs['image'] = image
+        elif self.mlp_background is not None:
+            with torch.no_grad():
+                bg = self._mlp_frames_background(data, len(frames))
+                outputs['image_fg'] = outputs['image']
+                outputs['image'] = mlp_composite(outputs['image'], outputs['alpha'], bg)
+                outputs['image_bg'] = bg if bg.shape[0] == len(frames) else bg.expand(len(frames), -1, -1, -1)
         else:
             outputs['image_fg'] = outputs['image']
         return outputs
@@ -160,6 +193,9 @@ class Scene(nn.Module):
         and so do the gradients it sends back.  Single avatar.  -> a list of V output dicts ([1, H, W, C] tensors)."""
         if self.avatars is not None:
             raise NotImplementedError("forward_views renders one avatar per view")
+        if self.mlp_background is not None:
+            raise NotImplementedError("forward_views with an MLP background: a step with the learned background is single view "
+                                      "(Scene.forward); the batched multi-view render does not composite it")
         main = torch.cuda.current_stream(self.avatar.device) if streams else None
         frames = []
         for v, pose in enumerate(poses):
@@ -184,7 +220,7 @@ class Scene(nn.Module):
             for side in streams[:len(frames)]:
                 main.wait_stream(side)
         out = self.renderer.render_frames(data=list(datas), frames=frames)
-        video = bg_mode not in self.pure_colors and self.background is not None
+        video = bg_mode not in self.pure_colors and isinstance(self.background, VideoBackground)
         if video:                                          # all V views in one launch; view v's pixels are those of forward()
             composite, bg = video_composite(out['image'], out['alpha'], self.background, self._video_indices(list(datas), None))
         views = []
@@ -222,12 +258,17 @@ class Scene(nn.Module):
             outputs['image_bg'] = self.pure_colors.get_background_like(bg_mode, outputs['image'])
             outputs['image_fg'] = outputs['image']
             outputs['image'] = outputs['image'] + outputs['image_bg'] * (1 - outputs['alpha'])
-        elif self.background is not None:
+        elif isinstance(self.background, VideoBackground):
             # scene.py:157-160: image_bg is the [H, W, 3] frame of data['frame_index'] (an int, or an int32 CUDA tensor of one index)
             image, image_bg = video_composite(outputs['image'], outputs['alpha'], self.background, data['frame_index'])
             outputs['image_bg'] = image_bg[0]
             outputs['image_fg'] = outputs['image']
             outputs['image'] = image
+        elif self.mlp_background is not None:
+            # scene.py:161-164: image_bg [B, H, W, 3] from the network; the composite sends gradients to alpha and to image_bg
+            outputs['image_bg'] = self.background(data)
+            outputs['image_fg'] = outputs['image']
+            outputs['image'] = mlp_composite(outputs['image'], outputs['alpha'], outputs['image_bg'])
         else:
             outputs['image_fg'] = outputs['image']
         return outputs
@@ -270,6 +311,8 @@ class Scene(nn.Module):
             self.avatar._nerf_bound_host = float(state_dict['avatar.nerf_bound'])
         for a in ([self.avatar] if self.avatars is None else list(self.avatars)):
             a.invalidate_caches()
+        if any(k.startswith('background.') for k in filtered):
+            _optim.PARAM_EPOCH[0] += 1          # the background's weights were written behind the parameter-derived caches' back
         unexpected = [k for k in state_dict.keys() if k not in own]
         if strict and (res.missing_keys or unexpected):
             raise RuntimeError("Scene.load_state_dict: missing %s unexpected %s" % (res.missing_keys, unexpected))

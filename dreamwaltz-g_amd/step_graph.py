@@ -42,6 +42,9 @@ class GraphedTrainStep:
         scalars 'radius' / 'tanfov' (the learning-rate schedule's spatial scale, trainer.py:713): the captured step then renders whatever
         camera `step(pose, camera)` was given (`warmup_cameras` / `capture_camera` pair with the warm-up / capture poses)."""
         self.trainer, self.grow = trainer, float(grow)
+        if getattr(trainer.model, "mlp_background", None) is not None:
+            raise NotImplementedError("GraphedTrainStep with an MLP background: the captured step replays the avatar's optimizers only; "
+                                      "the learned background's Adan step is not part of it")
         self.device = next(iter(example_pose.values())).device
         if self.device.type != "cuda":
             raise RuntimeError("dreamwaltz_g_amd.step_graph runs on the GPU only (HIP kernels)")

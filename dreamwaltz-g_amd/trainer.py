@@ -36,6 +36,10 @@ class SDSTrainer:
         self._unit = None
         self._cache_generation = getattr(getattr(model, "avatar", None), "cache_generation", None)
         self.past_checkpoints = []
+        if world > 1 and self._mlp_background() is not None:
+            # before sync_replicas() broadcasts anything: the background's Adan is not part of the replicas' exchange
+            raise NotImplementedError("SDSTrainer with an MLP background is single rank (ranks: %d): its parameters and gradient buffer "
+                                      "are not part of the multi-rank broadcast and reduce" % world)
         self.set_views(world)                       # one view per rank unless the caller says otherwise: mean of the summed gradients,
                                                     # folded into the Adam kernel
         # SURVEY 8e replica-consistency guard (nothing in the reference to mirror: it is single-GPU).  Replicas start from rank 0's
@@ -240,8 +244,8 @@ class SDSTrainer:
         if flat:
             self.optimizers.zero_grad()
         for optimizer in self.optimizers.values():
-            if not flat:
-                optimizer.zero_grad()
+            if not flat or getattr(optimizer, "owns_buffers", False):       # (the one fill does not reach an entry that owns its buffers:
+                optimizer.zero_grad()                                       # the background's optim.FlatAdan)
             if hasattr(optimizer, 'update_learning_rate'):
                 optimizer.update_learning_rate(iteration=self.train_step_index, spatial_scale=spatial_scale)
 
@@ -277,10 +281,28 @@ class SDSTrainer:
         renderer = getattr(self.model, "renderer", None)
         while renderer is not None and renderer.consume_overflow():
             self.redone_frames += 1
+            # the truncated frame sent zeros to the avatar, but the composite's backward has already written the learned background's
+            # gradient: it must not be counted twice (single view per step with that background: nothing else is in its buffer)
+            self._zero_background_grad()
             if seed is not None:
                 self._view_rng.manual_seed(int(seed))
             out = self._forward_backward(data, **forced)
         return out
+
+    def _mlp_background(self):
+        """The scene's learned background (background.MLPBackground), or None."""
+        return getattr(self.model, "mlp_background", None)
+
+    def _zero_background_grad(self):
+        optimizer = self.optimizers.get('background') if self._mlp_background() is not None and self.optimizers is not None else None
+        if optimizer is not None:
+            optimizer.zero_grad()
+
+    def _check_mlp_background(self, n_views, what):
+        """With the learned MLP background a step is the reference's: single view, single rank, not captured.  Refused BEFORE any launch."""
+        if self._mlp_background() is not None and (n_views != 1 or self.world != 1 or self.total_views != 1):
+            raise NotImplementedError("%s with an MLP background is single view and single rank (views this rank: %d, ranks: %d, views per "
+                                      "step: %d): its gradient buffer is not part of the multi-view reduce" % (what, n_views, self.world, self.total_views))
 
     def train_step(self, data, **forced):
         """One optimizer step.  `data`: the loader's dict for the reference's single-view step, or a LIST of such dicts -- the views THIS
@@ -289,6 +311,7 @@ class SDSTrainer:
         fused Adam with 1 / V folded in (the mean over ALL views of the step, `set_views`)."""
         views = list(data) if isinstance(data, (list, tuple)) else [data]
         self._check_densifier(len(views))
+        self._check_mlp_background(len(views), "train_step")
         self._check_caches()
         self.train_step_index += 1
         self._begin_step(self.get_spatial_scale(views[0]))
@@ -329,6 +352,9 @@ class SDSTrainer:
         if self.world != 1 or self.total_views != 1:
             raise NotImplementedError("the nerf2gs step is the reference's single-view, single-GPU loop (ranks: %d, views per step: %d)"
                                       % (self.world, self.total_views))
+        if self._mlp_background() is not None:
+            raise NotImplementedError("nerf2gs_step with an MLP background: the fit to the NeRF's renders compares foregrounds "
+                                      "(trainer.py:1304-1332); build the scene without the learned background for it")
         self._check_caches()
         self.nerf_guidance = nerf_guidance
         self.train_step_index += 1

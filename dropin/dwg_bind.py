@@ -84,6 +84,10 @@ Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's fie
                                                      mix and the planar image in one launch each; a network built with bg_mode 'nerf' -- it
                                                      has a bg_net and an encoder_bg -- also gets its learned background from one launch, B22:
                                                      dreamwaltz_g_amd.nerf_background); unset or any other value: render() is the reference's
+             DWG_BIND_MLP_BACKGROUND = 1              also bind `--render.use_mlp_background` (B23): the reference's own MLPBackground is built
+                                                     and adopted by dreamwaltz_g_amd.background.MLPBackground.from_reference, and its
+                                                     get_optimizer() is the fused Adan (optim.FlatAdan); unset or any other value: the bound
+                                                     build_scene refuses that flag as before
              DWG_BIND_INIT = 0                        leave the avatar constructor's geometry (B11) on the reference path (igl + pytorch3d)
              DWG_BIND_POINTCLOUD = 0                  leave the NeRF-to-Gaussian point-cloud export (B12) on the reference path
              DWG_BIND_SIGMA = 0                       leave Trainer.calc_sigma_loss (B8) on the reference path (trimesh + igl)
@@ -483,10 +487,17 @@ def _patch_scene_module(mod):
         from dreamwaltz_g_amd.scene import Scene
         import torch
         r = cfg.render
-        if r.use_mlp_background or r.use_gs_background:
-            raise NotImplementedError("learned / Gaussian backgrounds are outside the bound hot path (scene.py:226-237)")
+        mlp = bool(r.use_mlp_background) and os.environ.get("DWG_BIND_MLP_BACKGROUND") == "1"
+        if (r.use_mlp_background and not mlp) or r.use_gs_background:
+            raise NotImplementedError("learned / Gaussian backgrounds are outside the bound hot path (scene.py:226-237); "
+                                      "DWG_BIND_MLP_BACKGROUND=1 binds the learned MLP background (B23)")
         background = None
-        if r.use_video_background:
+        if mlp:
+            # the reference's OWN MLPBackground is built (its initial weights are the reference's draw) and adopted: the scene's
+            # background.get_optimizer() -- what init_gaussian_solvers puts under 'background' (trainer.py:594-598) -- is the fused Adan
+            from dreamwaltz_g_amd.background import MLPBackground
+            background = MLPBackground.from_reference(mod.MLPBackground())
+        elif r.use_video_background:
             # the reference's OWN VideoBackground (resolved at call time like its build_scene does: scene.py:229-230) decodes the video,
             # with its motionx temp-file extraction; the adopted device store keeps it alive (its __del__ removes that file)
             from dreamwaltz_g_amd.background import VideoBackground

@@ -54,6 +54,36 @@ int dwg_video_composite_backward(int32_t F, int32_t H, int32_t W, const float* d
                                  const uint8_t* frames, int32_t T, int32_t h, int32_t w, const int32_t* frame_index, float* d_alpha,
                                  dwg_stream_t stream);
 
+/*
+ * The learned (MLP) background of stage II (boundary B23, the reference's MLPBackground: core/system/background.py:55-89 and
+ * core/system/scene.py:161-164).  The network itself is include/dwg_nerf_background.h's, unchanged; here are the two steps around it.
+ *
+ *   dwg_background_dirs           the unit view direction of every pixel of F cameras
+ *   dwg_mlp_composite_forward     image = fg + bg * (1 - alpha), bg read from memory
+ *   dwg_mlp_composite_backward    d_alpha = -((d_r bg_r + d_g bg_g) + d_b bg_b) and d_bg = d_image * (1 - alpha);
+ *                                 d_fg = d_image: the caller uses d_image itself.
+ * Every float operation is rounded on its own; no atomics.
+ */
+#define DWG_BACKGROUND_CAMERA_FLOATS 16
+
+/* cameras [F][DWG_BACKGROUND_CAMERA_FLOATS] fp32: rows 0..2 of c2w (12 floats, row-major; the translation column is not read), then fx,
+ * fy, cx, cy -> dirs [F * H * W, 3] fp32, pixel (row, col) of camera f at f * H * W + row * W + col.  Per pixel, in fp32: get_rays'
+ * direction with N = -1 (core/nerf/nerf_utils.py:124-129) -- ((col + 0.5 - cx) / fx, (row + 0.5 - cy) / fy, 1), safe_normalize with its
+ * clamp at 1e-20, times c2w[:3, :3]^T -- then d / sqrt((d_x^2 + d_y^2) + d_z^2), a plain division (background.py:78).  No origins. */
+int dwg_background_dirs(int32_t F, const float* cameras, int32_t H, int32_t W, float* dirs, dwg_stream_t stream);
+
+/* fg [F, H, W, 3] fp32 at element strides (sf, sp, sc) as in dwg_video_composite_forward, alpha [F, H, W, 1] fp32 contiguous, bg
+ * [F, H, W, 3] fp32 contiguous (bg_frame_stride = H * W * 3) or one [H, W, 3] background shared by all frames (bg_frame_stride = 0)
+ * -> image [F, H, W, 3] fp32 at fg's strides. */
+int dwg_mlp_composite_forward(int32_t F, int32_t H, int32_t W, const float* fg, const float* alpha, int64_t sf, int64_t sp, int64_t sc,
+                              const float* bg, int64_t bg_frame_stride, float* image, dwg_stream_t stream);
+
+/* d_image [F, H, W, 3] fp32 at element strides (sf, sp, sc), alpha [F, H, W, 1] and bg [F, H, W, 3] fp32 contiguous -> d_alpha
+ * [F, H, W, 1] and d_bg [F, H, W, 3] fp32 contiguous.  Either output may be NULL (not wanted; alpha is read for d_bg only, bg for
+ * d_alpha only), not both. */
+int dwg_mlp_composite_backward(int32_t F, int32_t H, int32_t W, const float* d_image, int64_t sf, int64_t sp, int64_t sc, const float* alpha,
+                               const float* bg, float* d_alpha, float* d_bg, dwg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
