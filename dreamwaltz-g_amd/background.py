@@ -23,7 +23,15 @@ core/system/scene.py:161-164) is here too:
                                                         from_reference(ref_bg)
   background_dirs(c2w, intrinsics, H, W)                the unit view direction of every pixel of F cameras, one launch
   mlp_composite(image, alpha, image_bg)                 image + image_bg * (1 - alpha): autograd over one launch each way, gradients to
-                                                        image, alpha and image_bg"""
+                                                        image, alpha and image_bg
+
+The static 3D-Gaussian scene of `--render.use_gs_background PATH` (boundary B24: the reference's GaussianModel as a background,
+core/system/scene.py:123-132) is here as well:
+
+  load_gaussian_ply(path)                               the six tensors of GaussianModel.load_ply, read with numpy (no plyfile)
+  GaussianBackground.from_ply / from_tensors / from_reference   frozen parameters under the reference's names; .gaussians(camera_positions)
+                                                        -> the activated block (cached: one launch per parameter change)
+  scene_merge(avatar_parts, background, camera_positions)   merge_gaussians(avatars..., background) in one launch per frame"""
 import operator
 import os
 
@@ -407,3 +415,336 @@ def mlp_composite(image: torch.Tensor, alpha: torch.Tensor, image_bg: torch.Tens
     if _planar_strides(image, H, W) is None or not _dense(image):
         image = image.contiguous()
     return _MLPComposite.apply(image, alpha.contiguous(), image_bg.contiguous())
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# The static 3D-Gaussian scene (boundary B24: the reference's `--render.use_gs_background PATH`, a GaussianModel loaded from a .ply --
+# core/gaussian/gaussian_model.py:97-171 -- and merged into every frame, core/system/scene.py:123-132)
+# --------------------------------------------------------------------------------------------------------------------------------------
+SCENE_MAX_PARTS, SCENE_SH_REST = _lib.CONSTANTS["DWG_SCENE_MAX_PARTS"], _lib.CONSTANTS["DWG_SCENE_SH_REST"]
+ScenePartC = _lib.STRUCTS["dwg_scene_part"]
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _ply_first_element(path):
+    """(element name, {property: float64-castable array [count]}) of the FIRST element of a .ply (the reference reads `elements[0]`)."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.find(b"end_header")
+    if not raw.startswith(b"ply") or end < 0:
+        raise ValueError("%s: not a PLY file (no `ply` ... `end_header`)" % path)
+    nl = raw.find(b"\n", end)
+    body = raw[nl + 1:] if nl >= 0 else b""
+    fmt, elements = None, []
+    for line in raw[:end].decode("ascii", "replace").splitlines()[1:]:
+        words = line.split()
+        if not words or words[0] in ("comment", "obj_info"):
+            continue
+        if words[0] == "format":
+            fmt = words[1] if len(words) > 1 else None
+        elif words[0] == "element" and len(words) == 3:
+            elements.append((words[1], int(words[2]), []))
+        elif words[0] == "property" and elements:
+            if len(elements) > 1:
+                continue                                       # data behind the first element is never read
+            if words[1] == "list":
+                raise ValueError("%s: list property `%s` in element `%s`: a Gaussian scene has scalar properties only"
+                                 % (path, words[-1], elements[0][0]))
+            if len(words) != 3 or words[1] not in _PLY_TYPES:
+                raise ValueError("%s: cannot read the property declaration `%s`" % (path, line.strip()))
+            elements[0][2].append((words[2], _PLY_TYPES[words[1]]))
+        else:
+            raise ValueError("%s: cannot read the header line `%s`" % (path, line.strip()))
+    if fmt not in ("binary_little_endian", "binary_big_endian", "ascii"):
+        raise ValueError("%s: unknown PLY format `%s`" % (path, fmt))
+    if not elements:
+        raise ValueError("%s: no element in the header" % path)
+    name, count, props = elements[0]
+    if len({p for p, _ in props}) != len(props):
+        raise ValueError("%s: a property of element `%s` is declared twice" % (path, name))
+    if fmt == "ascii":
+        tokens = body.split()
+        if len(tokens) < count * len(props):
+            raise ValueError("%s: %d values for %d x %d properties of element `%s`" % (path, len(tokens), count, len(props), name))
+        table = np.array(tokens[:count * len(props)], dtype=np.float64).reshape(count, len(props))
+        return name, {p: table[:, i].astype(t) for i, (p, t) in enumerate(props)}
+    dtype = np.dtype([(p, ("<" if fmt == "binary_little_endian" else ">") + t) for p, t in props])
+    if len(body) < count * dtype.itemsize:
+        raise ValueError("%s: %d bytes of data for %d rows of %d bytes of element `%s`" % (path, len(body), count, dtype.itemsize, name))
+    rec = np.frombuffer(body, dtype=dtype, count=count)
+    return name, {p: rec[p] for p, _ in props}
+
+
+def load_gaussian_ply(path, max_sh_degree: int = 3):
+    """The six tensors of the reference's GaussianModel.load_ply (gaussian_model.py:97-147) from a 3DGS .ply, read with numpy alone:
+    {'positions' [N, 3], 'sh_features_dc' [N, 1, 3], 'sh_features_rest' [N, (max_sh_degree + 1)^2 - 1, 3], 'opacities' [N, 1] (logits),
+    'scales' [N, 3] (log), 'quaternions' [N, 4] (raw)}, fp32 on the CPU.  `f_rest_*` sorted by numeric suffix, reshaped (N, 3, 15), then
+    transposed, as the reference does.  binary_little_endian, binary_big_endian and ascii; the first element; properties in any order;
+    other properties (nx, ny, nz, ...) ignored; any scalar type (float and double are what such files carry).  ValueError for a wrong
+    `f_rest_*` count, a missing property or a list property (the reference asserts there)."""
+    name, cols = _ply_first_element(path)
+
+    def numbered(prefix):
+        try:
+            return sorted((c for c in cols if c.startswith(prefix)), key=lambda c: int(c.split("_")[-1]))
+        except ValueError:
+            raise ValueError("%s: a `%s*` property without a numeric suffix" % (path, prefix)) from None
+
+    def table(names):
+        n = len(next(iter(cols.values()))) if cols else 0
+        out = np.zeros((n, len(names)), dtype=np.float64)
+        for i, c in enumerate(names):
+            if c not in cols:
+                raise ValueError("%s: element `%s` has no property `%s`" % (path, name, c))
+            out[:, i] = cols[c]
+        return out
+    rest, scales, rots = numbered("f_rest_"), numbered("scale_"), numbered("rot")
+    want = 3 * (max_sh_degree + 1) ** 2 - 3
+    if len(rest) != want:
+        raise ValueError("%s: %d `f_rest_*` properties, expected %d for max_sh_degree %d" % (path, len(rest), want, max_sh_degree))
+    for names, n, what in ((scales, 3, "scale_0..2"), (rots, 4, "rot_0..3")):
+        if len(names) != n:
+            raise ValueError("%s: element `%s` has the properties %s, expected `%s`" % (path, name, names, what))
+    xyz, opac, dc = table(["x", "y", "z"]), table(["opacity"]), table(["f_dc_0", "f_dc_1", "f_dc_2"])
+    extra = table(rest).reshape(xyz.shape[0], 3, (max_sh_degree + 1) ** 2 - 1)
+    f32 = lambda a: torch.tensor(a, dtype=torch.float32)       # noqa: E731
+    return {'positions': f32(xyz), 'sh_features_dc': f32(dc[:, :, None]).transpose(1, 2).contiguous(),
+            'sh_features_rest': f32(extra).transpose(1, 2).contiguous(), 'opacities': f32(opac), 'scales': f32(table(scales)),
+            'quaternions': f32(table(rots))}
+
+
+def _camera_words(camera_positions):
+    """(tensor, element stride) of a camera position on the device: data['c2w'][:, :3, 3] is read in place (stride 4)."""
+    cam = camera_positions
+    while cam.dim() > 1:
+        if cam.shape[0] != 1:
+            raise ValueError("one camera position per frame, got %s" % (tuple(camera_positions.shape),))
+        cam = cam[0]
+    if cam.numel() != 3:
+        raise ValueError("camera_positions must hold 3 values, got %s" % (tuple(camera_positions.shape),))
+    if cam.dtype != torch.float32 or cam.stride(0) < 1:
+        cam = cam.float().contiguous()
+    return cam, int(cam.stride(0))
+
+
+class GaussianBackground(nn.Module):
+    """A static scene of N Gaussians behind the avatars.  Parameters carry the reference's names (GaussianModel: `_positions` [N, 3],
+    `_sh_features_dc` [N, 1, 3], `_sh_features_rest` [N, 15, 3], `_opacities` [N, 1] logits, `_scales` [N, 3] log, `_quaternions` [N, 4]
+    raw), so that a Scene's state_dict has the reference's `background.*` keys.  They are frozen: the reference has no optimizer for this
+    background.  `sh_levels` 1 (the reference's hard-coded view-independent colour max(C0 dc + 0.5, 0)) .. 4 (view-dependent colour from
+    the file's higher bands, renderer.compute_colors' semantics).  The activated block -- sigmoid, exp, F.normalize, DC colour: one launch
+    -- is kept until optim.PARAM_EPOCH, a parameter's address or version counter, or invalidate_caches() says otherwise."""
+    NAMES = ('_positions', '_sh_features_dc', '_sh_features_rest', '_opacities', '_scales', '_quaternions')
+
+    def __init__(self, positions, sh_features_dc, sh_features_rest, opacities, scales, quaternions, sh_levels: int = 1):
+        super().__init__()
+        n = int(positions.shape[0])
+        opacities = opacities.reshape(n, 1) if opacities.dim() == 1 else opacities
+        given = dict(zip(self.NAMES, (positions, sh_features_dc, sh_features_rest, opacities, scales, quaternions)))
+        tails = {'_positions': (3,), '_sh_features_dc': (1, 3), '_sh_features_rest': (None, 3), '_opacities': (1,), '_scales': (3,),
+                 '_quaternions': (4,)}
+        for k, t in given.items():
+            if t.dim() != 1 + len(tails[k]) or t.shape[0] != n or any(w is not None and t.shape[1 + i] != w for i, w in enumerate(tails[k])):
+                raise ValueError("GaussianBackground: %s has shape %s, expected [%d, %s]" % (k, tuple(t.shape), n, ", ".join(map(str, tails[k]))))
+            setattr(self, k, nn.Parameter(t.detach().to(torch.float32).contiguous(), requires_grad=False))
+        self.sh_levels = int(sh_levels)
+        if not 1 <= self.sh_levels <= 4:
+            raise ValueError("sh_levels must be 1..4, got %r" % (sh_levels,))
+        if self.sh_levels > 1 and self._sh_features_rest.shape[1] != SCENE_SH_REST:
+            raise ValueError("sh_levels %d reads the higher bands of a degree-3 file: _sh_features_rest must be [N, %d, 3], got %s"
+                             % (self.sh_levels, SCENE_SH_REST, tuple(self._sh_features_rest.shape)))
+        self.reference = None
+        self.activation_launches = 0            # how often the activation kernel ran (the cache's counter)
+        self._generation, self._cache, self._block = 0, None, None
+
+    @classmethod
+    def from_tensors(cls, positions, sh_features_dc, sh_features_rest, opacities, scales, quaternions, sh_levels: int = 1):
+        return cls(positions, sh_features_dc, sh_features_rest, opacities, scales, quaternions, sh_levels=sh_levels)
+
+    @classmethod
+    def from_ply(cls, path, device=None, sh_levels: int = 1, max_sh_degree: int = 3):
+        self = cls(**load_gaussian_ply(path, max_sh_degree=max_sh_degree), sh_levels=sh_levels)
+        return self if device is None else self.to(device)
+
+    @classmethod
+    def from_reference(cls, ref_gaussian_model, sh_levels: int = 1):
+        """Adopt a loaded reference GaussianModel (load_ply_and_initialize): its six parameters' storage, frozen here."""
+        missing = [k for k in cls.NAMES if getattr(ref_gaussian_model, k, None) is None]
+        if missing:
+            raise ValueError("from_reference: the Gaussian model has no %s (load_ply_and_initialize first)" % ", ".join(missing))
+        self = cls(*(getattr(ref_gaussian_model, k) for k in cls.NAMES), sh_levels=sh_levels)
+        self.reference = [ref_gaussian_model]                  # kept alive, not registered as a submodule
+        return self
+
+    @property
+    def n_points(self) -> int:
+        return int(self._positions.shape[0])
+
+    def invalidate_caches(self):
+        self._generation += 1
+        self._cache = None
+
+    def reset_by_state_dict(self, state_dict):
+        """GaussianModel.reset_by_state_dict (gaussian_model.py:58-85): resize the parameters to the checkpoint's Gaussian count."""
+        for k in self.NAMES:
+            v, cur = state_dict.get(k), getattr(self, k)
+            if v is not None and v.dim() and cur.shape[0] != v.shape[0]:
+                setattr(self, k, nn.Parameter(torch.empty(v.shape[0], *cur.shape[1:], dtype=cur.dtype, device=cur.device), requires_grad=False))
+        self.invalidate_caches()
+
+    def _cache_key(self):
+        from . import optim
+        ps = (self._opacities, self._scales, self._quaternions, self._sh_features_dc)
+        return (optim.PARAM_EPOCH[0], self._generation,
+                tuple((p.data_ptr(), 0 if p.is_inference() else p._version, tuple(p.shape)) for p in ps))
+
+    def activated(self) -> dict:
+        """{'opacities' [N, 1], 'scales' [N, 3], 'quaternions' [N, 4], 'colors' [N, 3] (the DC colour)}: cached, one launch when stale.
+        A stale block is recomputed into the SAME tensors while the Gaussian count and the device stay: a graph captured earlier
+        (player.GraphedAnimation) has their addresses baked in and must never find them freed.  The graph does not contain the activation,
+        so after the scene's parameters change a replay shows the new values only once activated() has run again outside the graph."""
+        key = self._cache_key()
+        if self._cache is not None and self._cache[0] == key:
+            return self._cache[1]
+        n, dev = self.n_points, self._positions.device
+        for k in self.NAMES:
+            _lib.check_tensor(k, getattr(self, k), device=dev)
+        capturing = torch.cuda.is_current_stream_capturing()
+        block = None if capturing else self._block
+        if block is None or block['opacities'].shape[0] != n or block['opacities'].device != dev:
+            block = {'opacities': torch.empty((n, 1), dtype=torch.float32, device=dev), 'scales': torch.empty((n, 3), dtype=torch.float32, device=dev),
+                     'quaternions': torch.empty((n, 4), dtype=torch.float32, device=dev), 'colors': torch.empty((n, 3), dtype=torch.float32, device=dev)}
+        with torch.cuda.device(dev):
+            rc = _lib.lib().dwg_scene_gaussians_activate(n, _lib.ptr(self._opacities), _lib.ptr(self._scales), _lib.ptr(self._quaternions),
+                                                         _lib.ptr(self._sh_features_dc), _lib.ptr(block['opacities']), _lib.ptr(block['scales']),
+                                                         _lib.ptr(block['quaternions']), _lib.ptr(block['colors']), _lib.stream(dev))
+        _lib.check(rc, "dwg_scene_gaussians_activate")
+        self.activation_launches += 1
+        if not capturing:                                      # a block allocated inside a capture belongs to that graph's pool
+            self._cache, self._block = (key, block), block
+        return block
+
+    def view_colors(self, camera_positions) -> torch.Tensor:
+        """[N, 3]: the colour seen from `camera_positions` ([1, 3] or [3], a device tensor read in place) at this background's sh_levels."""
+        if self.sh_levels == 1:
+            return self.activated()['colors']
+        if camera_positions is None:
+            raise ValueError("sh_levels %d is view dependent: gaussians(camera_positions=) needs the camera position" % self.sh_levels)
+        n, dev = self.n_points, self._positions.device
+        cam, stride = _camera_words(camera_positions.to(dev))
+        colors = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().dwg_scene_gaussians_colors(n, _lib.ptr(self._positions), _lib.ptr(self._sh_features_dc), _lib.ptr(self._sh_features_rest),
+                                                       self.sh_levels, _lib.ptr(cam), stride, _lib.ptr(colors), _lib.stream(dev))
+        _lib.check(rc, "dwg_scene_gaussians_colors")
+        return colors
+
+    def gaussians(self, camera_positions=None):
+        """The activated scene as a GaussianOutput (positions: the parameter itself; sh_features None): what the reference's
+        `background.forward()` + `compute_colors(..., sh_levels=1)` (scene.py:124-131) hands to merge_gaussians."""
+        from .avatar import GaussianOutput
+        block = self.activated()
+        return GaussianOutput(positions=self._positions.detach(), opacities=block['opacities'], colors=self.view_colors(camera_positions),
+                              scales=block['scales'], quaternions=block['quaternions'], sh_features=None)
+
+    def forward(self, camera_positions=None):
+        return self.gaussians(camera_positions)
+
+    def get_optimizer(self, cfg=None):
+        raise NotImplementedError("GaussianBackground is frozen: the reference has no optimizer for a Gaussian scene background either "
+                                  "(its init_gaussian_solvers fails at background.get_optimizer)")
+
+
+_MERGE_ATTRS = (("positions", 3), ("opacities", 1), ("colors", 3), ("scales", 3), ("quaternions", 4))
+
+
+def _merge_launch(part_tensors, counts, background, camera_positions, out):
+    """part_tensors: 5 dense fp32 tensors per avatar part, flat; the background's block goes last -> rows [0, sum) of the 5 `out` tensors."""
+    dev = out[0].device
+    block = background.activated()
+    n_bg, levels = background.n_points, background.sh_levels
+    if len(counts) + 1 > SCENE_MAX_PARTS:
+        raise ValueError("a frame merges at most %d avatars with the scene, got %d" % (SCENE_MAX_PARTS - 1, len(counts)))
+    parts = (ScenePartC * SCENE_MAX_PARTS)()
+    for i, n in enumerate(counts):
+        p = parts[i]
+        p.positions, p.opacities, p.colors, p.scales, p.quaternions = (t.data_ptr() for t in part_tensors[5 * i:5 * i + 5])
+        p.count = n
+    p = parts[len(counts)]
+    p.positions, p.opacities, p.scales, p.quaternions = (background._positions.data_ptr(), block['opacities'].data_ptr(),
+                                                         block['scales'].data_ptr(), block['quaternions'].data_ptr())
+    p.colors = block['colors'].data_ptr() if levels == 1 else None
+    p.count = n_bg
+    cam, stride = (None, 1)
+    if levels > 1:
+        if camera_positions is None:
+            raise ValueError("sh_levels %d is view dependent: the merge needs the camera position" % levels)
+        cam, stride = _camera_words(camera_positions.to(dev))
+    total = sum(counts) + n_bg
+    if any(int(o.shape[0]) != total for o in out):
+        raise RuntimeError("scene_merge: %d rows for buffers of %s rows" % (total, [int(o.shape[0]) for o in out]))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().dwg_scene_merge(len(counts) + 1, parts, levels, _lib.ptr(background._sh_features_dc), _lib.ptr(background._sh_features_rest),
+                                        _lib.ptr(cam), stride, total, *(_lib.ptr(o) for o in out), _lib.stream(dev))
+    _lib.check(rc, "dwg_scene_merge")
+
+
+class _SceneMerge(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, background, camera_positions, counts, shapes, *tensors):
+        dev, total = tensors[0].device, sum(counts) + background.n_points
+        out = tuple(torch.empty((total, w), dtype=torch.float32, device=dev) for _, w in _MERGE_ATTRS)
+        _merge_launch([t.detach().reshape(-1, w).contiguous() for t, (_, w) in zip(tensors, _MERGE_ATTRS * len(counts))], counts, background,
+                      camera_positions, out)
+        ctx.counts, ctx.shapes = counts, shapes
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        # the avatar parts get their row slices of the incoming gradients (what torch.cat's backward hands out); the scene gets none
+        out, row = [], 0
+        for i, n in enumerate(ctx.counts):
+            for a in range(5):
+                g = grads[a]
+                k = 5 * i + a
+                out.append(g[row:row + n].reshape(ctx.shapes[k]) if g is not None and ctx.needs_input_grad[4 + k] else None)
+            row += n
+        return (None, None, None, None) + tuple(out)
+
+
+def scene_merge(avatar_parts, background: GaussianBackground, camera_positions=None, out=None):
+    """merge_gaussians(*avatar_parts, background.gaussians(camera_positions)) (scene.py:107-132) in ONE launch: the five attributes of every
+    part into rows [0, sum N) -- of `out` (five [sum N, .] fp32 tensors: rows of the stacked buffers a frames chain reads; no gradients) or of
+    fresh tensors.  With gradients enabled and an avatar part that requires them the merge is an autograd function whose backward slices
+    the incoming gradients per part.  -> GaussianOutput (sh_features None)."""
+    from .avatar import GaussianOutput
+    if not isinstance(background, GaussianBackground):
+        raise TypeError("scene_merge needs a GaussianBackground, got %s" % type(background).__name__)
+    tensors, counts = [], []
+    dev = background._positions.device
+    for i, g in enumerate(avatar_parts):
+        if g.colors is None:
+            raise NotImplementedError("scene_merge: avatar part %d has no precomputed `colors` (sh_features only): the merge with a Gaussian "
+                                      "scene takes precomputed colours, as the reference's scene.py:123-132 produces for the scene" % i)
+        n = int(g.positions.shape[0])
+        for name, w in _MERGE_ATTRS:
+            t = g[name]
+            _lib.check_tensor("part %d %s" % (i, name), t, contiguous=False, device=dev)
+            if t.numel() != n * w:
+                raise RuntimeError("part %d: %s has shape %s, expected [%d, %d]" % (i, name, tuple(t.shape), n, w))
+            tensors.append(t)
+        counts.append(n)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        if out is not None:
+            raise RuntimeError("scene_merge: no gradients through preallocated rows (out=)")
+        res = _SceneMerge.apply(background, camera_positions, tuple(counts), tuple(tuple(t.shape) for t in tensors), *tensors)
+    else:
+        total = sum(counts) + background.n_points
+        res = out if out is not None else tuple(torch.empty((total, w), dtype=torch.float32, device=dev) for _, w in _MERGE_ATTRS)
+        for o, (name, w) in zip(res, _MERGE_ATTRS):
+            _lib.check_tensor("out " + name, o, shape=(total, w), device=dev)
+        _merge_launch([t.detach().reshape(-1, w).contiguous() for t, (_, w) in zip(tensors, _MERGE_ATTRS * len(counts))], counts, background,
+                      camera_positions, res)
+    return GaussianOutput(**{name: t for (name, _), t in zip(_MERGE_ATTRS, res)}, sh_features=None)

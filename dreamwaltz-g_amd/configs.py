@@ -55,6 +55,7 @@ class RenderConfig:
     avatar_scale: Optional[str] = None
     use_mlp_background: bool = False                 # the learned MLP background (scene.py:227-228; background.MLPBackground, boundary B23)
     use_video_background: Optional[str] = None       # a video file (or "motionx_reenact,<name>" through the reference): scene.py:229-230
+    use_gs_background: Optional[str] = None          # a 3DGS .ply scene behind the avatars: scene.py:233-235 (background.GaussianBackground, B24)
     use_densifier: bool = False                      # configs/__init__.py:159-171 (off in every shipped recipe)
     densify_from_iter: Optional[int] = None
     densify_until_iter: Optional[int] = None

@@ -12,7 +12,13 @@ tolerate a truncated frame call check() per frame -- that still skips all the pe
 
 A scene with a video background (background.VideoBackground, bg_mode not a pure colour) gets the frame index as one more static input:
 an int32 device word the captured composite reads, set per `replay(pose, frame_index=i)` by a device-to-device copy from the
-background's index table -- one capture replays a whole clip with no host sync."""
+background's index table -- one capture replays a whole clip with no host sync.
+
+A scene with a Gaussian scene background (background.GaussianBackground) is captured with the scene's activated block as it was cached
+before the capture: the graph merges those tensors and does not contain the activation.  The block keeps its addresses when it is
+recomputed (a replay never reads freed memory), but after the scene's parameters change -- an in-place edit, load_state_dict,
+invalidate_caches() -- a replay shows the new values only once something has run the activation again eagerly
+(`scene.background.activated()`); a changed Gaussian count needs `recapture()`."""
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -31,7 +37,9 @@ class GraphedAnimation:
             raise ValueError("GraphedAnimation needs a renderer with async_pair_count=True (no host read-back inside the frame)")
         self.pose = {k: v.clone() for k, v in example_pose.items()} if example_pose is not None else None      # static inputs of the graph
         self.frame_index = None
-        if getattr(scene, "background", None) is not None and bg_mode not in scene.pure_colors:
+        # (a Gaussian scene background has no frame index: its rows are merged into the captured frame, camera read from device memory)
+        if (getattr(scene, "background", None) is not None and getattr(scene, "gaussian_background", None) is None
+                and bg_mode not in scene.pure_colors):
             self.frame_index = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.set_frame_index(frame_index if frame_index is not None else data.get('frame_index', 0))
             self.data = dict(data, frame_index=self.frame_index)

@@ -183,14 +183,27 @@ class GaussianRenderer:
             sh_levels = self.sh_levels
         return get_colors(sh_features=sh_features, directions=directions, sh_levels=sh_levels)
 
-    def render_frames(self, data: dict, frames) -> dict:
+    def render_frames(self, data: dict, frames, stacked: Optional[dict] = None) -> dict:
         """F posed sets of Gaussians seen by ONE camera (or each by its own), rasterized by ONE launch chain (rasterizer.rasterize_frames):
         the playback path under inference mode (trainer.py:1019-1150 renders a pose sequence frame by frame), and -- differentiable since
         round 6, the backward on (work, F) grids too -- the V views of a batched multi-view training step.  Frame f of the result is
         bit-identical to `render(data, frames[f])`; what changes is the cost: the rasterizer's seven dependent launches are paid once per
         batch and each runs over F times the work (per frame, 300 k Gaussians at 1024^2: 0.44 ms alone, 0.25 ms at F = 4).
+        `stacked` (with `frames` None): the frames' attributes ALREADY stacked -- {'positions' [F, G, 3], 'opacities' [F, G, 1], 'colors'
+        [F, G, 3], 'scales' [F, G, 3], 'quaternions' [F, G, 4]}, precomputed colours -- read in place: a caller that wrote its frames into
+        such buffers (Scene.forward_frames with a Gaussian scene) pays no torch.stack copy.  No gradients through them.
         -> {'image': [F, H, W, 3], 'depth': [F, H, W, 1], 'alpha': [F, H, W, 1]}."""
         from .rasterizer import rasterize_frames
+        if stacked is not None:
+            from .avatar import GaussianOutput
+            if frames is not None:
+                raise ValueError("render_frames: either frames or stacked attributes")
+            missing = [k for k in ("positions", "opacities", "colors", "scales", "quaternions") if stacked.get(k) is None]
+            if missing or stacked["positions"].dim() != 3:
+                raise ValueError("render_frames: stacked attributes need [F, G, .] positions, opacities, colors, scales and quaternions"
+                                 " (missing: %s)" % missing)
+            frames = [GaussianOutput(**{k: stacked[k][f] for k in ("positions", "opacities", "colors", "scales", "quaternions")})
+                      for f in range(int(stacked["positions"].shape[0]))]           # views, for the per-frame statements below
         # one camera for the batch (`data`: the loader's dict), or one per frame (`data`: a list of F such dicts -- the reference's evaluation
         # loader hands a camera with every pose; image size and field of view must agree across the batch)
         datas = list(data) if isinstance(data, (list, tuple)) else [data]
@@ -216,7 +229,8 @@ class GaussianRenderer:
         if use_cov:
             for g in frames:
                 g.cov3D = self.compute_3d_covariance(scales=g.scales, quaternions=g.quaternions)
-        st = lambda name: torch.stack([getattr(g, name) for g in frames])          # noqa: E731
+        st = lambda name: (stacked[name].detach() if stacked is not None and name in stacked else      # noqa: E731
+                           torch.stack([getattr(g, name) for g in frames]))
         # the pair workspace is sized exactly: ONE read-back of the F pair counts between binning and compositing (per frame before)
         color, radii, depth, alpha, info = rasterize_frames(
             st("positions"), st("opacities"), colors_precomp=st("colors") if use_colors else None,

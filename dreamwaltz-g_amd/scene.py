@@ -4,8 +4,9 @@ compositing `image + bg (1 - alpha)` for bg_mode in {black, white, gray}, for a 
 the frames on the device, one launch per frame chain) and for the learned MLP background (boundary B23, background.MLPBackground:
 directions, the fused encoding + network + sigmoid, and the composite -- three launches forward; gradients to alpha and to the
 background's weights).  Precedence as the reference's (scene.py:153-166): a pure-colour bg_mode, then video, then MLP.  The Gaussian
-(.ply) background (scene.py:123-132) is outside the hot path and is rejected, and so is every object that is not one of the package's
-own two background classes."""
+(.ply) scene background (scene.py:123-132, boundary B24) is a background.GaussianBackground: its activated block is merged with the avatars'
+Gaussians in one launch per frame, whatever bg_mode says, before the debug overrides and the rasterizer -- playback and evaluation only,
+its parameters are frozen.  Every object that is not one of the package's own three background classes is rejected."""
 from typing import Iterable, Optional
 
 import contextlib
@@ -15,7 +16,7 @@ import torch.nn as nn
 
 from .avatar import DreamWaltzG, GaussianOutput, merge_gaussians
 from . import optim as _optim
-from .background import MLPBackground, VideoBackground, mlp_composite, video_composite
+from .background import GaussianBackground, MLPBackground, VideoBackground, mlp_composite, scene_merge, video_composite
 from .renderer import GaussianRenderer
 
 
@@ -43,9 +44,11 @@ def downsample_gaussians(gaussians: GaussianOutput, n: int) -> GaussianOutput:
 class Scene(nn.Module):
     def __init__(self, cfg, avatar, background=None, async_pair_count=False) -> None:
         super().__init__()
-        if background is not None and not isinstance(background, VideoBackground) and type(background) is not MLPBackground:
+        if (background is not None and not isinstance(background, VideoBackground) and type(background) is not MLPBackground
+                and type(background) is not GaussianBackground):
             raise NotImplementedError("Gaussian backgrounds are outside the SDS hot path (scene.py:123-132); a video background is a "
-                                      "background.VideoBackground and a learned one a background.MLPBackground, got %s.%s"
+                                      "background.VideoBackground, a learned one a background.MLPBackground and a Gaussian scene for "
+                                      "playback a background.GaussianBackground, got %s.%s"
                                       % (type(background).__module__, type(background).__name__))
         self.device = torch.device(cfg.device)
         if isinstance(avatar, DreamWaltzG):
@@ -84,14 +87,62 @@ class Scene(nn.Module):
             gaussians.positions = gaussians.positions + t.unsqueeze(0)
         return gaussians
 
-    def _avatars_forward(self, smpl_observed_inputs: dict) -> GaussianOutput:
-        """scene.py:107-121: avatar i animated with slice i of the [A, ...] inputs (and its scale / translation), the outputs merged."""
+    def _avatar_parts(self, smpl_observed_inputs) -> list:
+        """The avatars' outputs of one frame, unmerged: [avatar_forward(pose)] or, with several avatars, avatar i animated with slice i of
+        the [A, ...] inputs (scene.py:107-121)."""
+        if self.avatars is None:
+            return [self.avatar_forward(smpl_observed_inputs=smpl_observed_inputs)]
         parts = []
         batch_size = smpl_observed_inputs['body_pose'].size(0)
         assert batch_size <= len(self.avatars), f'Assert num_smplx_inputs: {batch_size} <= num_avatars: {len(self.avatars)}'
         for i, avatar in enumerate(self.avatars):
             parts.append(self.avatar_forward({k: v[i:i + 1, ...] for k, v in smpl_observed_inputs.items()}, avatar=avatar, avatar_index=i))
-        return merge_gaussians(*parts)
+        return parts
+
+    def _avatars_forward(self, smpl_observed_inputs: dict) -> GaussianOutput:
+        """scene.py:107-121: avatar i animated with slice i of the [A, ...] inputs (and its scale / translation), the outputs merged."""
+        return merge_gaussians(*self._avatar_parts(smpl_observed_inputs))
+
+    @property
+    def gaussian_background(self):
+        """The static Gaussian scene behind the avatars (background.GaussianBackground), or None."""
+        return self.background if type(self.background) is GaussianBackground else None
+
+    def _frames_with_scene(self, data, poses):
+        """forward_frames with a Gaussian scene: per frame the avatars' rows and the scene's rows go straight into the stacked [F, N, .]
+        buffers the frames chain reads (ONE merge launch per frame, no torch.cat and no torch.stack of the scene), then the debug overrides
+        on the merged set (scene.py:134-145).  -> the kwargs of renderer.render_frames."""
+        bg = self.background
+        datas = list(data) if isinstance(data, (list, tuple)) else None
+        bufs, total, F = None, None, len(poses)
+        if datas is not None and len(datas) not in (1, F):
+            raise ValueError("%d camera dicts for %d frames" % (len(datas), F))
+        for f, pose in enumerate(poses):
+            parts = self._avatar_parts(pose)
+            n = sum(int(g.positions.shape[0]) for g in parts) + bg.n_points
+            if bufs is None:
+                total = n
+                dev = parts[0].positions.device
+                bufs = tuple(torch.empty((F, n, w), dtype=torch.float32, device=dev) for w in (3, 1, 3, 3, 4))
+            elif n != total:
+                raise ValueError("the frames of one forward_frames call share one Gaussian count: frame %d has %d, frame 0 %d" % (f, n, total))
+            d = data if datas is None else datas[f if len(datas) > 1 else 0]
+            scene_merge(parts, bg, d['c2w'][:, :3, 3], out=tuple(b[f] for b in bufs))
+        positions, opacities, colors, scales, quaternions = bufs
+        # the stacked buffers are this call's own: the overrides change them in place (the same values as forward()'s `scales * 0.1` and
+        # expanded constants, without a second [F, N, .] tensor)
+        if self.use_zero_scales:
+            scales.mul_(0.1)
+        if self.use_constant_colors:
+            colors.copy_(self.constant_colors.to(colors.dtype).expand(F, total, -1))
+        if self.use_constant_opacities:
+            opacities.copy_(self.constant_opacities.to(opacities.dtype).expand(F, total, -1))
+        if self.use_fixed_n_gaussians:                         # a random subset per frame, as forward() draws it: frames of their own
+            frames = [downsample_gaussians(GaussianOutput(positions=positions[f], opacities=opacities[f], colors=colors[f], scales=scales[f],
+                                                          quaternions=quaternions[f]), self.fixed_n_gaussians) for f in range(F)]
+            return {'frames': frames}
+        return {'frames': None, 'stacked': {'positions': positions, 'opacities': opacities, 'colors': colors, 'scales': scales,
+                                            'quaternions': quaternions}}
 
     def _video_indices(self, data, frame_indices):
         if frame_indices is not None:
@@ -147,7 +198,12 @@ class Scene(nn.Module):
         avatars = [self.avatar] if self.avatars is None else list(self.avatars)
         for avatar in avatars:
             avatar.frozen_playback = bool(frozen_avatar)
+        scene_frames = None
         try:
+            if self.gaussian_background is not None:
+                with torch.no_grad():                           # playback: the rows are written into preallocated buffers
+                    scene_frames = self._frames_with_scene(data, list(poses))
+                poses = []
             for pose in poses:
                 if self.avatars is None:
                     g = self.avatar_forward(smpl_observed_inputs=pose)
@@ -165,7 +221,7 @@ class Scene(nn.Module):
         finally:
             for avatar in avatars:
                 avatar.frozen_playback = False
-        outputs = self.renderer.render_frames(data=data, frames=frames)
+        outputs = self.renderer.render_frames(data=data, frames=frames) if scene_frames is None else self.renderer.render_frames(data=data, **scene_frames)
         if bg_mode in self.pure_colors:
             outputs['image_bg'] = self.pure_colors.get_background_like(bg_mode, outputs['image'])
             outputs['image_fg'] = outputs['image']
@@ -191,6 +247,9 @@ class Scene(nn.Module):
         small launches -- then ONE differentiable rasterizer launch chain for all of them (renderer.render_frames: forward AND backward on
         (work, V) grids).  View v of the result equals `forward(datas[v], poses[v], use_densifier=False, bg_mode=bg_mode)` bit for bit,
         and so do the gradients it sends back.  Single avatar.  -> a list of V output dicts ([1, H, W, C] tensors)."""
+        if self.gaussian_background is not None:
+            raise NotImplementedError("forward_views with a GaussianBackground: the Gaussian scene is for playback and evaluation "
+                                      "(Scene.forward / forward_frames); the batched multi-view training render does not merge it")
         if self.avatars is not None:
             raise NotImplementedError("forward_views renders one avatar per view")
         if self.mlp_background is not None:
@@ -241,7 +300,10 @@ class Scene(nn.Module):
 
     def forward(self, data: dict, smpl_observed_inputs: Optional[dict] = None, use_densifier: bool = True, bg_mode: Optional[str] = None,
                 **kwargs):
-        if self.avatars is None:
+        if self.gaussian_background is not None:
+            # scene.py:123-132, whatever bg_mode says: the avatars' rows, then the scene's, in one launch (no torch.cat per attribute)
+            gaussians = scene_merge(self._avatar_parts(smpl_observed_inputs), self.background, data['c2w'][:, :3, 3])
+        elif self.avatars is None:
             gaussians = self.avatar_forward(smpl_observed_inputs=smpl_observed_inputs)
         else:
             gaussians = self._avatars_forward(smpl_observed_inputs)
@@ -304,6 +366,8 @@ class Scene(nn.Module):
         by_module = self.organize_state_dict(state_dict)
         if 'avatar' in by_module:
             self.avatar.reset_by_state_dict(by_module['avatar'])
+        if 'background' in by_module and self.gaussian_background is not None:
+            self.background.reset_by_state_dict(by_module['background'])
         own = set(super().state_dict().keys())
         filtered = {k: v for k, v in state_dict.items() if k in own}
         res = super().load_state_dict(filtered, strict=False)

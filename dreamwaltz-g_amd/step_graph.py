@@ -45,6 +45,9 @@ class GraphedTrainStep:
         if getattr(trainer.model, "mlp_background", None) is not None:
             raise NotImplementedError("GraphedTrainStep with an MLP background: the captured step replays the avatar's optimizers only; "
                                       "the learned background's Adan step is not part of it")
+        if getattr(trainer.model, "gaussian_background", None) is not None:
+            raise NotImplementedError("GraphedTrainStep with a GaussianBackground: the Gaussian scene background is for playback and "
+                                      "evaluation; no training step renders it")
         self.device = next(iter(example_pose.values())).device
         if self.device.type != "cuda":
             raise RuntimeError("dreamwaltz_g_amd.step_graph runs on the GPU only (HIP kernels)")

@@ -36,6 +36,7 @@ class SDSTrainer:
         self._unit = None
         self._cache_generation = getattr(getattr(model, "avatar", None), "cache_generation", None)
         self.past_checkpoints = []
+        self._check_gaussian_background("SDSTrainer")
         if world > 1 and self._mlp_background() is not None:
             # before sync_replicas() broadcasts anything: the background's Adan is not part of the replicas' exchange
             raise NotImplementedError("SDSTrainer with an MLP background is single rank (ranks: %d): its parameters and gradient buffer "
@@ -304,6 +305,12 @@ class SDSTrainer:
             raise NotImplementedError("%s with an MLP background is single view and single rank (views this rank: %d, ranks: %d, views per "
                                       "step: %d): its gradient buffer is not part of the multi-view reduce" % (what, n_views, self.world, self.total_views))
 
+    def _check_gaussian_background(self, what):
+        """The Gaussian scene background (background.GaussianBackground) is frozen, for playback and evaluation.  Refused BEFORE any launch."""
+        if getattr(self.model, "gaussian_background", None) is not None:
+            raise NotImplementedError("%s with a GaussianBackground: the Gaussian scene background is frozen and for playback and evaluation "
+                                      "(Scene.forward / forward_frames); no training step renders it" % what)
+
     def train_step(self, data, **forced):
         """One optimizer step.  `data`: the loader's dict for the reference's single-view step, or a LIST of such dicts -- the views THIS
         rank renders in a multi-view step (view v of V goes to rank v mod world; identical parameters everywhere).
@@ -312,6 +319,7 @@ class SDSTrainer:
         views = list(data) if isinstance(data, (list, tuple)) else [data]
         self._check_densifier(len(views))
         self._check_mlp_background(len(views), "train_step")
+        self._check_gaussian_background("train_step")
         self._check_caches()
         self.train_step_index += 1
         self._begin_step(self.get_spatial_scale(views[0]))
@@ -352,6 +360,7 @@ class SDSTrainer:
         if self.world != 1 or self.total_views != 1:
             raise NotImplementedError("the nerf2gs step is the reference's single-view, single-GPU loop (ranks: %d, views per step: %d)"
                                       % (self.world, self.total_views))
+        self._check_gaussian_background("nerf2gs_step")
         if self._mlp_background() is not None:
             raise NotImplementedError("nerf2gs_step with an MLP background: the fit to the NeRF's renders compares foregrounds "
                                       "(trainer.py:1304-1332); build the scene without the learned background for it")

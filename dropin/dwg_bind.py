@@ -488,9 +488,13 @@ def _patch_scene_module(mod):
         import torch
         r = cfg.render
         mlp = bool(r.use_mlp_background) and os.environ.get("DWG_BIND_MLP_BACKGROUND") == "1"
-        if (r.use_mlp_background and not mlp) or r.use_gs_background:
+        # the reference's precedence (scene.py:227-235): MLP, then video, then the Gaussian scene
+        gs_bound = os.environ.get("DWG_BIND_GS_BACKGROUND") == "1"
+        gs = bool(r.use_gs_background) and gs_bound and not r.use_mlp_background and not r.use_video_background
+        if (r.use_mlp_background and not mlp) or (r.use_gs_background and not gs_bound):
             raise NotImplementedError("learned / Gaussian backgrounds are outside the bound hot path (scene.py:226-237); "
-                                      "DWG_BIND_MLP_BACKGROUND=1 binds the learned MLP background (B23)")
+                                      "DWG_BIND_MLP_BACKGROUND=1 binds the learned MLP background (B23), DWG_BIND_GS_BACKGROUND=1 the "
+                                      "Gaussian scene background for playback (B24)")
         background = None
         if mlp:
             # the reference's OWN MLPBackground is built (its initial weights are the reference's draw) and adopted: the scene's
@@ -502,6 +506,11 @@ def _patch_scene_module(mod):
             # with its motionx temp-file extraction; the adopted device store keeps it alive (its __del__ removes that file)
             from dreamwaltz_g_amd.background import VideoBackground
             background = VideoBackground.from_reference(mod.VideoBackground(r.use_video_background))
+        elif gs:
+            # the .ply is read by the package's own reader (the reference's load_ply needs plyfile); the parameters go to cfg.device with
+            # the scene, frozen
+            from dreamwaltz_g_amd.background import GaussianBackground
+            background = GaussianBackground.from_ply(r.use_gs_background)
         # exact pair sizing through the 16-byte read-back per frame, like the reference's CUDA extension: the reference's loop body does
         # not know about re-rendering a truncated frame
         return Scene(cfg, avatar, background=background, async_pair_count=False).to(torch.device(cfg.device))
