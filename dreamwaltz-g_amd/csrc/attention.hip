@@ -318,6 +318,7 @@ int DWG_ATTN_PAIRS_FN(DWG_ATTN_PAIRS_ARGS, dwg_stream_t stream_) {
     if (R <= 0 || Bq <= 0 || H <= 0 || (long long)R * Bq * H > 65535) return DWG_E_ARG;          // one grid row per (image, head)
     const int B = R * Bq;
     if (Nq <= 0 || Nk <= 0 || d <= 0 || d % 8 || d > 160 || !Q || !K || !V || !O) return DWG_E_ARG;
+    if (!(scale > 0.f) || !__builtin_isfinite(scale)) return DWG_E_ARG;      // the kernels fold the scale into the exponent and take the tile maximum BEFORE scaling
     if ((ldq | ldk | ldv | ldo | bq | bk | bv | bo | oq | ok | ov | oo) % 8) return DWG_E_ARG;   // 16-byte aligned rows
     if (R > 1 && (ok == 0 || ov == 0 || oo == 0)) return DWG_E_ARG;          // only the queries may be shared by the outer entries
     if (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) % 16) return DWG_E_ARG;

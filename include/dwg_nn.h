@@ -68,7 +68,10 @@ int dwg_layernorm_forward_dt(int32_t dtype, int32_t M, int32_t C, const void* x,
                              void* y, dwg_stream_t stream);
 int dwg_geglu_forward_dt(int32_t dtype, int64_t M, int32_t F, const void* x, void* out, dwg_stream_t stream);
 /* fused attention: DWG_DTYPE_BF16, DWG_DTYPE_F16 or DWG_DTYPE_F32X (split-precision operands, csrc/attention_x.hip: three 16-bit MFMAs per
- * product, fp32-grade scores / probabilities / outputs); the exact-fp32 plans run attention as QK^T -> row softmax -> PV on dwg_gemm */
+ * product, fp32-grade scores / probabilities / outputs); the exact-fp32 plans run attention as QK^T -> row softmax -> PV on dwg_gemm.
+ * `scale` must be positive and finite -- the kernels fold it into the exponent and take each tile's maximum before scaling: every fused
+ * attention entry point (this one, _ws, _pairs_dt, _pairs_ws and the un-suffixed bf16 one) returns DWG_E_ARG for scale <= 0, NaN or inf, on
+ * the host, before any device call. */
 int dwg_attention_forward_dt(int32_t dtype, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d, const void* Q, int64_t ldq,
                              int64_t bq, const void* K, int64_t ldk, int64_t bk, const void* V, int64_t ldv, int64_t bv, void* O,
                              int64_t ldo, int64_t bo, float scale, dwg_stream_t stream);

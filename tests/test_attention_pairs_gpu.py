@@ -132,15 +132,27 @@ def test_pair_arguments_are_checked_on_the_host():
     ld = H * d
 
     def call(dt=F32X, Rr=R, Bq=BQ, Hh=H, dd=d, Q=fake, K=fake, V=fake, O=fake, oq=0, ok=BQ * Nk * ld, ov=BQ * Nk * ld, oo=BQ * Nq * ld, bq=Nq * ld,
-             ldq=ld, ws=False):
-        args = (dt, Rr, Bq, Hh, Nq, Nk, dd, Q, ldq, bq, oq, K, ld, Nk * ld, ok, V, ld, Nk * ld, ov, O, ld, Nq * ld, oo, float(dd) ** -0.5)
+             ldq=ld, ws=False, scale=None):
+        args = (dt, Rr, Bq, Hh, Nq, Nk, dd, Q, ldq, bq, oq, K, ld, Nk * ld, ok, V, ld, Nk * ld, ov, O, ld, Nq * ld, oo,
+                float(dd) ** -0.5 if scale is None else scale)
         return L.dwg_attention_forward_pairs_ws(*args, None, 0, None) if ws else L.dwg_attention_forward_pairs_dt(*args, None)
+
+    def plain(dt, ws, scale):
+        """The one-level entry points: dwg_attention_forward_dt / _ws over B = R Bq images."""
+        args = (dt, R * BQ, H, Nq, Nk, d, fake, ld, Nq * ld, fake, ld, Nk * ld, fake, ld, Nk * ld, fake, ld, Nq * ld, scale)
+        return L.dwg_attention_forward_ws(*args, None, 0, None) if ws else L.dwg_attention_forward_dt(*args, None)
     for dt in (F32X, F16, BF16):
         for ws in (False, True):
             for bad in (dict(Q=None), dict(K=None), dict(V=None), dict(O=None), dict(Q=odd), dict(O=odd), dict(ok=0), dict(ov=0), dict(oo=0),
                         dict(oq=4), dict(ok=BQ * Nk * ld + 4), dict(ov=12), dict(oo=BQ * Nq * ld + 2), dict(bq=Nq * ld + 4), dict(ldq=ld + 1),
                         dict(Rr=0), dict(Bq=0), dict(Rr=-1), dict(Hh=0), dict(dd=44), dict(dd=168), dict(Rr=300, Bq=300)):
                 assert call(dt=dt, ws=ws, **bad) == E_ARG, (dt, ws, bad)
+            # the scale is folded into the exponent as a positive factor: 0, negative, NaN and inf are argument errors, on every entry point
+            for scale in (0.0, -0.0, -0.158, float("nan"), float("inf"), -float("inf")):
+                assert call(dt=dt, ws=ws, scale=scale) == E_ARG, (dt, ws, scale)
+                assert plain(dt, ws, scale) == E_ARG, (dt, ws, scale)
+    for scale in (0.0, -0.158, float("nan"), float("inf")):
+        assert L.dwg_attention_forward(R * BQ, H, Nq, Nk, d, fake, ld, Nq * ld, fake, ld, Nk * ld, fake, ld, Nk * ld, fake, ld, Nq * ld, scale, None) == E_ARG
     assert call(dt=F32) == E_ARG and call(dt=7, ws=True) == E_ARG          # the exact-f32 plans run attention on dwg_gemm
     fn = L.dwg_concat_channels_bcast
     assert fn(0, 70, 320, 320, fake, fake, fake, None) == 0
