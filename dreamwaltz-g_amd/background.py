@@ -31,7 +31,10 @@ core/system/scene.py:123-132) is here as well:
   load_gaussian_ply(path)                               the six tensors of GaussianModel.load_ply, read with numpy (no plyfile)
   GaussianBackground.from_ply / from_tensors / from_reference   frozen parameters under the reference's names; .gaussians(camera_positions)
                                                         -> the activated block (cached: one launch per parameter change)
-  scene_merge(avatar_parts, background, camera_positions)   merge_gaussians(avatars..., background) in one launch per frame"""
+  scene_merge(avatar_parts, background, camera_positions)   merge_gaussians(avatars..., background) in one launch per frame
+  GaussianBackground.culled(cameras, H, W)              boundary B25: the scene Gaussians that may reach the image under the cameras, compacted
+                                                        in index order into a CulledScene that scene_merge takes in place of the background
+                                                        (cached per cameras and image size: csrc/scene_cull.hip, csrc/cull_math.h)"""
 import operator
 import os
 
@@ -423,6 +426,8 @@ def mlp_composite(image: torch.Tensor, alpha: torch.Tensor, image_bg: torch.Tens
 # --------------------------------------------------------------------------------------------------------------------------------------
 SCENE_MAX_PARTS, SCENE_SH_REST = _lib.CONSTANTS["DWG_SCENE_MAX_PARTS"], _lib.CONSTANTS["DWG_SCENE_SH_REST"]
 ScenePartC = _lib.STRUCTS["dwg_scene_part"]
+CULL_MAX_CAMERAS, CULL_CAMERA_FLOATS = _lib.CONSTANTS["DWG_SCENE_CULL_MAX_CAMERAS"], _lib.CONSTANTS["DWG_SCENE_CULL_CAMERA_FLOATS"]
+CULL_MAX_ROWS, CullRowsC = _lib.CONSTANTS["DWG_SCENE_CULL_MAX_ROWS"], _lib.STRUCTS["dwg_scene_cull_rows"]
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
@@ -529,6 +534,79 @@ def _camera_words(camera_positions):
     return cam, int(cam.stride(0))
 
 
+CULL_CACHE_BLOCKS = 4            # culled blocks a GaussianBackground keeps
+_CULL_CAMERA_KEYS = ('extrinsic', 'projection', 'c2w', 'tanfov', 'tanfov_x')
+
+
+def _cull_camera_dicts(cameras):
+    dicts = list(cameras) if isinstance(cameras, (list, tuple)) else [cameras]
+    if not dicts or not all(isinstance(d, dict) for d in dicts):
+        raise TypeError("cameras: one camera dict, a list of them, or a [C, %d] fp32 device tensor of camera blocks" % CULL_CAMERA_FLOATS)
+    return dicts
+
+
+def _cull_camera_tensors(cameras):
+    """The tensors a culled block's cameras are read from, in a fixed order (what the cache key identifies)."""
+    if isinstance(cameras, torch.Tensor):
+        return (cameras,)
+    out = []
+    for d in _cull_camera_dicts(cameras):
+        if d.get('tanfov_dev') is not None:
+            raise ValueError("culling under a camera whose field of view lives in device memory (data['tanfov_dev']) is not supported: the "
+                             "cull reads data['tanfov'] on the host and would not follow the device value")
+        for k in _CULL_CAMERA_KEYS:
+            t = d.get(k)
+            if t is None and k != 'tanfov_x':
+                raise KeyError("a camera dict needs '%s'" % k)
+            if t is not None:
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError("camera dict: '%s' must be a tensor, got %s" % (k, type(t).__name__))
+                out.append(t)
+    return tuple(out)
+
+
+def _cull_camera_blocks(cameras, dev):
+    """[C, 37] fp32 on `dev`: per camera the 35 floats the renderer's own camera launch writes (dwg_raster_camera_setup: the very view and
+    projection matrices the rasterizer reads), then tanfovx, tanfovy as the renderer passes them."""
+    if isinstance(cameras, torch.Tensor):
+        return cameras
+    dicts = _cull_camera_dicts(cameras)
+    blocks = torch.empty((len(dicts), CULL_CAMERA_FLOATS), dtype=torch.float32, device=dev)
+    tanfov = []
+    with torch.cuda.device(dev):
+        for i, d in enumerate(dicts):
+            mats = [d[k][0].to(dev).float().contiguous() for k in ('extrinsic', 'projection', 'c2w')]
+            _lib.check(_lib.lib().dwg_raster_camera_setup(*(_lib.ptr(m) for m in mats), _lib.ptr(blocks[i]), _lib.stream(dev)),
+                       "dwg_raster_camera_setup")
+            ty = float(d['tanfov'][0])
+            tanfov.append([float(d['tanfov_x'][0]) if d.get('tanfov_x') is not None else ty, ty])
+    blocks[:, 35:] = torch.tensor(tanfov, dtype=torch.float32).to(dev)
+    return blocks
+
+
+class CulledScene:
+    """The part of a GaussianBackground that may reach the image under a set of cameras (GaussianBackground.culled): what scene_merge
+    reads of a background -- n_points (the kept count), activated(), _positions, _sh_features_dc / _sh_features_rest (sh_levels > 1 only,
+    else None: the merge does not read them) and sh_levels -- over the kept rows in their original order, plus `index` (int32 [n_points],
+    ascending: row k is scene Gaussian index[k]) and `n_total` (the scene's Gaussian count).  A copy: it does not follow later changes
+    of the scene; `key` is the GaussianBackground.cull_key() it was computed under, and `camera_tensors` are the tensors that key
+    identifies by address and version counter -- held here, so that no other tensor can get their addresses while the block is cached."""
+
+    def __init__(self, key, n_total, sh_levels, index, rows, camera_tensors=()):
+        self.key, self.n_total, self.sh_levels, self.index = key, int(n_total), int(sh_levels), index
+        self.camera_tensors = tuple(camera_tensors)
+        self._positions = rows['positions']
+        self._sh_features_dc, self._sh_features_rest = rows.get('sh_features_dc'), rows.get('sh_features_rest')
+        self._block = {k: rows[k] for k in ('opacities', 'scales', 'quaternions', 'colors')}
+
+    @property
+    def n_points(self) -> int:
+        return int(self.index.shape[0])
+
+    def activated(self) -> dict:
+        return self._block
+
+
 class GaussianBackground(nn.Module):
     """A static scene of N Gaussians behind the avatars.  Parameters carry the reference's names (GaussianModel: `_positions` [N, 3],
     `_sh_features_dc` [N, 1, 3], `_sh_features_rest` [N, 15, 3], `_opacities` [N, 1] logits, `_scales` [N, 3] log, `_quaternions` [N, 4]
@@ -558,6 +636,8 @@ class GaussianBackground(nn.Module):
         self.reference = None
         self.activation_launches = 0            # how often the activation kernel ran (the cache's counter)
         self._generation, self._cache, self._block = 0, None, None
+        self.cull_launches = 0                  # how often culled() ran its kernels (the culled blocks' cache counter)
+        self._cull_cache = {}                   # cull_key() -> CulledScene, least recently used first
 
     @classmethod
     def from_tensors(cls, positions, sh_features_dc, sh_features_rest, opacities, scales, quaternions, sh_levels: int = 1):
@@ -585,6 +665,7 @@ class GaussianBackground(nn.Module):
     def invalidate_caches(self):
         self._generation += 1
         self._cache = None
+        self._cull_cache = {}
 
     def reset_by_state_dict(self, state_dict):
         """GaussianModel.reset_by_state_dict (gaussian_model.py:58-85): resize the parameters to the checkpoint's Gaussian count."""
@@ -656,6 +737,75 @@ class GaussianBackground(nn.Module):
         raise NotImplementedError("GaussianBackground is frozen: the reference has no optimizer for a Gaussian scene background either "
                                   "(its init_gaussian_solvers fails at background.get_optimizer)")
 
+    # -- the per-camera cull (boundary B25, csrc/scene_cull.hip) --------------------------------------------------------------------------
+    def cull_key(self, cameras, image_height, image_width):
+        """What a culled block depends on: the activated block's key, the positions (and, at sh_levels > 1, the SH tables the compact
+        block copies), `(data_ptr, _version, shape)` of every camera tensor, and the image size.  No launch, no host read."""
+        ident = lambda t: (t.data_ptr(), 0 if t.is_inference() else t._version, tuple(t.shape))      # noqa: E731
+        own = (self._positions,) + ((self._sh_features_dc, self._sh_features_rest) if self.sh_levels > 1 else ())
+        return (self._cache_key(), tuple(ident(p) for p in own), tuple(ident(t) for t in _cull_camera_tensors(cameras)),
+                int(image_height), int(image_width))
+
+    def culled(self, cameras, image_height, image_width) -> "CulledScene":
+        """The scene Gaussians that MAY reach an image_height x image_width image under any of `cameras` (one camera dict of the loader, a
+        list of them -- the union: one block for all frames of a forward_frames call -- or a [C, 37] fp32 device tensor of camera blocks as
+        dwg_raster_camera_block writes them), compacted in index order into a block that scene_merge takes in place of this background.
+        The test (csrc/cull_math.h) never drops a Gaussian the rasterizer would give radius > 0, and the kept rows keep their relative
+        order, so a frame merged from the culled block is the frame merged from the whole scene, bit for bit.  Cached like the activated
+        block, under cull_key(): a hit launches nothing and reads nothing back; a miss runs flags, compaction and gather
+        (`cull_launches` += 1) and reads the kept count back ONCE, to size the block.  The last CULL_CACHE_BLOCKS blocks are kept
+        (a second camera does not evict the first), each with its camera tensors: a key identifies them by address, and a held tensor's
+        address cannot pass to another camera's tensor.  Never inside a graph capture."""
+        key = self.cull_key(cameras, image_height, image_width)
+        hit = self._cull_cache.pop(key, None)
+        if hit is not None:
+            self._cull_cache[key] = hit                        # most recently used last
+            return hit
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("GaussianBackground.culled: the culled block is not cached for these cameras and cannot be computed inside a "
+                               "graph capture (its size is read back from the device): call culled() before the capture")
+        n, dev, H, W = self.n_points, self._positions.device, int(image_height), int(image_width)
+        if n > 0x7fffffff:
+            raise ValueError("GaussianBackground.culled: %d Gaussians, the kept indices are int32" % n)
+        block = self.activated()
+        cams = _cull_camera_blocks(cameras, dev)
+        _lib.check_tensor("camera blocks", cams, shape=(None, CULL_CAMERA_FLOATS), device=dev)
+        C = int(cams.shape[0])
+        if not 1 <= C <= CULL_MAX_CAMERAS:
+            raise ValueError("GaussianBackground.culled: %d cameras, expected 1..%d" % (C, CULL_MAX_CAMERAS))
+        _lib.check_tensor("_positions", self._positions, shape=(n, 3), device=dev)
+        L = _lib.lib()
+        index = torch.empty((n,), dtype=torch.int32, device=dev)
+        count = torch.zeros((1,), dtype=torch.int32, device=dev)
+        if n:
+            flags = torch.empty((n,), dtype=torch.uint8, device=dev)
+            work = torch.empty((max(int(L.dwg_scene_cull_workspace_bytes(n)), 4),), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(L.dwg_scene_cull_flags(n, _lib.ptr(self._positions), _lib.ptr(block['scales']), C, _lib.ptr(cams), CULL_CAMERA_FLOATS,
+                                                  H, W, _lib.ptr(flags), _lib.stream(dev)), "dwg_scene_cull_flags")
+                _lib.check(L.dwg_scene_cull_compact(n, _lib.ptr(flags), _lib.ptr(index), _lib.ptr(count), _lib.ptr(work), _lib.stream(dev)),
+                           "dwg_scene_cull_compact")
+        kept = int(count.item())                               # the one host read of a cull: sizes the block and the chain's G
+        index = index[:kept].clone()                           # the scene-sized scratch goes back to the allocator
+        src = {'positions': self._positions.detach(), 'opacities': block['opacities'], 'scales': block['scales'],
+               'quaternions': block['quaternions'], 'colors': block['colors']}
+        if self.sh_levels > 1:
+            src['sh_features_dc'], src['sh_features_rest'] = self._sh_features_dc.detach(), self._sh_features_rest.detach()
+        out = {k: torch.empty((kept,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for k, t in src.items()}
+        if kept:
+            for k, t in src.items():
+                _lib.check_tensor(k, t, device=dev)
+            tables = (CullRowsC * CULL_MAX_ROWS)()
+            for row, (k, t) in zip(tables, src.items()):
+                row.src, row.dst, row.width = t.data_ptr(), out[k].data_ptr(), t[0].numel()
+            with torch.cuda.device(dev):
+                _lib.check(L.dwg_scene_cull_gather(kept, _lib.ptr(index), n, len(src), tables, _lib.stream(dev)), "dwg_scene_cull_gather")
+        self.cull_launches += 1
+        culled = self._cull_cache[key] = CulledScene(key, n, self.sh_levels, index, out, _cull_camera_tensors(cameras))
+        while len(self._cull_cache) > CULL_CACHE_BLOCKS:
+            del self._cull_cache[next(iter(self._cull_cache))]
+        return culled
+
 
 _MERGE_ATTRS = (("positions", 3), ("opacities", 1), ("colors", 3), ("scales", 3), ("quaternions", 4))
 
@@ -717,10 +867,10 @@ class _SceneMerge(torch.autograd.Function):
 def scene_merge(avatar_parts, background: GaussianBackground, camera_positions=None, out=None):
     """merge_gaussians(*avatar_parts, background.gaussians(camera_positions)) (scene.py:107-132) in ONE launch: the five attributes of every
     part into rows [0, sum N) -- of `out` (five [sum N, .] fp32 tensors: rows of the stacked buffers a frames chain reads; no gradients) or of
-    fresh tensors.  With gradients enabled and an avatar part that requires them the merge is an autograd function whose backward slices
+    fresh tensors.  `background` may be a CulledScene (GaussianBackground.culled): only its kept rows are merged.  With gradients enabled and an avatar part that requires them the merge is an autograd function whose backward slices
     the incoming gradients per part.  -> GaussianOutput (sh_features None)."""
     from .avatar import GaussianOutput
-    if not isinstance(background, GaussianBackground):
+    if not isinstance(background, (GaussianBackground, CulledScene)):
         raise TypeError("scene_merge needs a GaussianBackground, got %s" % type(background).__name__)
     tensors, counts = [], []
     dev = background._positions.device

@@ -64,6 +64,8 @@ class _ChainCounts:
 
 
 class GaussianRenderer:
+    SCALE_MODIFIER = 1.          # gaussian_renderer.py:62: the reference fixes it; the scene cull's bound (csrc/cull_math.h) is stated for 1
+
     def __init__(self, sh_levels=4, bg_color=(0.0, 0.0, 0.0), compute_color_in_rasterizer=True,
                  compute_covariance_in_rasterizer=True, async_pair_count=False, reorder_every: int = 0) -> None:
         self.sh_levels = sh_levels
@@ -154,7 +156,7 @@ class GaussianRenderer:
         for key, value in raster_settings.items():
             if isinstance(value, torch.Tensor):
                 raster_settings[key] = value.to(device)
-        settings = GaussianRasterizationSettings(**raster_settings, scale_modifier=1., prefiltered=False, debug=False)
+        settings = GaussianRasterizationSettings(**raster_settings, scale_modifier=self.SCALE_MODIFIER, prefiltered=False, debug=False)
         return GaussianRasterizer(raster_settings=settings, pair_state=self.pair_state(device, image_height, image_width))
 
     def _visit_order_for(self, positions: torch.Tensor) -> torch.Tensor:

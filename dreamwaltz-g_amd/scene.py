@@ -6,7 +6,8 @@ directions, the fused encoding + network + sigmoid, and the composite -- three l
 background's weights).  Precedence as the reference's (scene.py:153-166): a pure-colour bg_mode, then video, then MLP.  The Gaussian
 (.ply) scene background (scene.py:123-132, boundary B24) is a background.GaussianBackground: its activated block is merged with the avatars'
 Gaussians in one launch per frame, whatever bg_mode says, before the debug overrides and the rasterizer -- playback and evaluation only,
-its parameters are frozen.  Every object that is not one of the package's own three background classes is rejected."""
+its parameters are frozen.  With `cull_scene` (boundary B25, off by default) forward_frames merges only the scene Gaussians that may reach
+the image under the call's cameras (background.GaussianBackground.culled): the same frames bit for bit.  Every object that is not one of the package's own three background classes is rejected."""
 from typing import Iterable, Optional
 
 import contextlib
@@ -16,7 +17,7 @@ import torch.nn as nn
 
 from .avatar import DreamWaltzG, GaussianOutput, merge_gaussians
 from . import optim as _optim
-from .background import GaussianBackground, MLPBackground, VideoBackground, mlp_composite, scene_merge, video_composite
+from .background import CULL_MAX_CAMERAS, GaussianBackground, MLPBackground, VideoBackground, mlp_composite, scene_merge, video_composite
 from .renderer import GaussianRenderer
 
 
@@ -42,7 +43,10 @@ def downsample_gaussians(gaussians: GaussianOutput, n: int) -> GaussianOutput:
 
 
 class Scene(nn.Module):
-    def __init__(self, cfg, avatar, background=None, async_pair_count=False) -> None:
+    def __init__(self, cfg, avatar, background=None, async_pair_count=False, cull_scene=False) -> None:
+        """`cull_scene`: forward_frames merges, per call, only the Gaussians of a Gaussian scene background that may reach the image under
+        the call's cameras (background.GaussianBackground.culled, boundary B25) -- the same frames bit for bit, fewer rows through the merge
+        and the rasterizer.  Off by default; forward_frames(cull_scene=) overrides it per call."""
         super().__init__()
         if (background is not None and not isinstance(background, VideoBackground) and type(background) is not MLPBackground
                 and type(background) is not GaussianBackground):
@@ -57,6 +61,9 @@ class Scene(nn.Module):
             self.avatars = nn.ModuleList(avatar)
             self.avatar = self.avatars[0]
         self.background = background
+        self.cull_scene = bool(cull_scene)
+        if self.cull_scene and type(background) is not GaussianBackground:
+            raise ValueError("cull_scene=True culls a Gaussian scene background (background.GaussianBackground): this scene has none")
         self.pure_colors = PureColorBackground()
         self.renderer = GaussianRenderer(sh_levels=cfg.render.sh_levels, bg_color=cfg.render.bg_color, async_pair_count=async_pair_count)
         r = cfg.render
@@ -108,11 +115,28 @@ class Scene(nn.Module):
         """The static Gaussian scene behind the avatars (background.GaussianBackground), or None."""
         return self.background if type(self.background) is GaussianBackground else None
 
-    def _frames_with_scene(self, data, poses):
+    def _culled_background(self, cameras):
+        """The scene background culled for `cameras` (one camera dict or a list: the union), or the refusal of what culling cannot serve."""
+        if self.gaussian_background is None:
+            raise ValueError("cull_scene=True culls a Gaussian scene background (background.GaussianBackground): this scene has none")
+        if self.use_fixed_n_gaussians:
+            raise ValueError("cull_scene with use_fixed_n_gaussians: the random subset would be drawn from the culled set, not from the "
+                             "merged set the unculled frame draws it from -- switch one of them off")
+        if self.renderer.SCALE_MODIFIER != 1.0:                # the bound of csrc/cull_math.h is stated for the scale modifier the renderer fixes
+            raise ValueError("cull_scene needs the renderer's scale_modifier to be 1, got %r" % (self.renderer.SCALE_MODIFIER,))
+        many = isinstance(cameras, (list, tuple))
+        if many and len(cameras) > CULL_MAX_CAMERAS:
+            raise ValueError("cull_scene takes the union over at most %d per-frame cameras, got %d: split the forward_frames call"
+                             % (CULL_MAX_CAMERAS, len(cameras)))
+        first = cameras[0] if many else cameras
+        return self.background.culled(cameras, first['image_height'], first['image_width'])
+
+    def _frames_with_scene(self, data, poses, cull_scene=False):
         """forward_frames with a Gaussian scene: per frame the avatars' rows and the scene's rows go straight into the stacked [F, N, .]
         buffers the frames chain reads (ONE merge launch per frame, no torch.cat and no torch.stack of the scene), then the debug overrides
-        on the merged set (scene.py:134-145).  -> the kwargs of renderer.render_frames."""
-        bg = self.background
+        on the merged set (scene.py:134-145).  `cull_scene`: the scene's rows are those of the block culled for the call's cameras (their
+        union; cached per cameras).  -> the kwargs of renderer.render_frames."""
+        bg = self._culled_background(data) if cull_scene else self.background
         datas = list(data) if isinstance(data, (list, tuple)) else None
         bufs, total, F = None, None, len(poses)
         if datas is not None and len(datas) not in (1, F):
@@ -181,7 +205,8 @@ class Scene(nn.Module):
         with torch.no_grad():
             return self.background(data)
 
-    def forward_frames(self, data: dict, poses, bg_mode: Optional[str] = None, frozen_avatar: bool = False, frame_indices=None) -> dict:
+    def forward_frames(self, data: dict, poses, bg_mode: Optional[str] = None, frozen_avatar: bool = False, frame_indices=None,
+                       cull_scene: Optional[bool] = None) -> dict:
         """Playback of F pose frames under one camera (`data`: the loader's dict) or each under its own (`data`: a list of F dicts, as the
         reference's evaluation loader yields them): `animate` per pose, then ONE rasterizer launch chain for all of them
         (renderer.render_frames).  Frame f equals `forward(data, poses[f], use_densifier=False, bg_mode=bg_mode)` bit for bit -- the
@@ -192,9 +217,15 @@ class Scene(nn.Module):
         pose-independent part of `animate` -- canonical positions, grid encoding, colour / opacity network -- is computed once and kept until
         a parameter changes (avatar.DreamWaltzG.frozen_playback; same bits, 0.3 ms less per 300 k-Gaussian frame).  A video background
         takes one frame index per frame (`frame_indices`: ints or an int32 CUDA tensor; else each data dict's 'frame_index', or a
-        single dict's list / tensor of F) and composites all F frames in one launch after the rasterizer chain.
+        single dict's list / tensor of F) and composites all F frames in one launch after the rasterizer chain.  `cull_scene` (default:
+        the scene's own switch): merge only the Gaussians of a Gaussian scene background that may reach the image under this call's
+        cameras (their union: at most 64 per-frame cameras a call) -- the same frames bit for bit; refused together with
+        use_fixed_n_gaussians, without a Gaussian scene, and under a camera dict that carries 'tanfov_dev'.
         -> {'image' | 'image_fg' | 'image_bg' | 'depth' | 'alpha': [F, H, W, C]}."""
         frames = []
+        cull = self.cull_scene if cull_scene is None else bool(cull_scene)
+        if cull and self.gaussian_background is None:
+            raise ValueError("cull_scene=True culls a Gaussian scene background (background.GaussianBackground): this scene has none")
         avatars = [self.avatar] if self.avatars is None else list(self.avatars)
         for avatar in avatars:
             avatar.frozen_playback = bool(frozen_avatar)
@@ -202,7 +233,7 @@ class Scene(nn.Module):
         try:
             if self.gaussian_background is not None:
                 with torch.no_grad():                           # playback: the rows are written into preallocated buffers
-                    scene_frames = self._frames_with_scene(data, list(poses))
+                    scene_frames = self._frames_with_scene(data, list(poses), cull_scene=cull)
                 poses = []
             for pose in poses:
                 if self.avatars is None:

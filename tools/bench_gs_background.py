@@ -19,6 +19,14 @@ Per scene size:
   graph_replay_fps         player.GraphedAnimation replays
   pairs / overflow         what the rasterizer chain reports for one frame: block pairs after culling, the reference's tile-pair count, and
                            whether the frame overflowed its pair buffers (the chain was tuned for <= 3 10^5 Gaussians)
+With --cull (boundary B25, csrc/scene_cull.hip: the scene culled once per camera) the columns above stay as they are and these are added:
+  kept_gaussians, kept_share       the scene Gaussians GaussianBackground.culled keeps for the benchmark's camera
+  cull_ms                  device time of flags + compaction + gather (the three C entries on preallocated buffers, 20 calls in one
+                           graph, event-timed, median of 3): what a cache miss costs on the device; a miss also reads the count back once
+  merge_culled_ms          dwg_scene_merge per frame over the culled block (as merge_ms)
+  cull_rounds              eager F = 1 and eager F = 4 in frames/s with culling off and on, ALTERNATED in this process, three rounds:
+                           {column: [round 1, 2, 3]}; *_fps_cull_off / *_fps_cull_on are the medians and *_spread the largest max - min
+                           of the two (GraphedAnimation does not cull: graph_replay_fps above is the only replay figure)
 The last line is the whole table as JSON.
 """
 import argparse
@@ -103,6 +111,60 @@ def torch_reference_composition(avatar_out, bg, data, renderer):
     return merge_gaussians(avatar_out, scene)
 
 
+def cull_columns(scene, bg, data, poses, part, a, dev):
+    """The --cull columns of one scene size (see the module docstring)."""
+    from dreamwaltz_g_amd import _lib
+    from dreamwaltz_g_amd.background import CULL_CAMERA_FLOATS, CULL_MAX_ROWS, CullRowsC, _cull_camera_blocks
+    row, n, T, L = {}, bg.n_points, len(poses), _lib.lib()
+    with torch.inference_mode():
+        culled = bg.culled(data, a.res, a.res)
+        kept = culled.n_points
+        row["kept_gaussians"], row["kept_share"] = kept, round(kept / max(n, 1), 4)
+        block, cams = bg.activated(), _cull_camera_blocks(data, dev)
+        flags, index = torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        work = torch.empty(max(int(L.dwg_scene_cull_workspace_bytes(n)), 4), dtype=torch.uint8, device=dev)
+        src = [bg._positions, block['opacities'], block['scales'], block['quaternions'], block['colors']]
+        dst = [torch.empty((kept,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in src]
+        tables = (CullRowsC * CULL_MAX_ROWS)()
+        for r, s, d in zip(tables, src, dst):
+            r.src, r.dst, r.width = s.data_ptr(), d.data_ptr(), s[0].numel()
+        st = _lib.stream
+
+        def cull_kernels():
+            _lib.check(L.dwg_scene_cull_flags(n, _lib.ptr(bg._positions), _lib.ptr(block['scales']), 1, _lib.ptr(cams), CULL_CAMERA_FLOATS, a.res,
+                                              a.res, _lib.ptr(flags), st(dev)), "dwg_scene_cull_flags")
+            _lib.check(L.dwg_scene_cull_compact(n, _lib.ptr(flags), _lib.ptr(index), _lib.ptr(count), _lib.ptr(work), st(dev)), "dwg_scene_cull_compact")
+            _lib.check(L.dwg_scene_cull_gather(kept, _lib.ptr(index), n, len(src), tables, st(dev)), "dwg_scene_cull_gather")
+        cull_kernels()
+        assert int(count.item()) == kept and torch.equal(dst[0], culled._positions) and torch.equal(dst[4], culled.activated()['colors'])
+        row["cull_ms"] = round(statistics.median(graph_ms(cull_kernels) for _ in range(3)), 4)
+        out = tuple(torch.empty((int(part.positions.shape[0]) + kept, w), dtype=torch.float32, device=dev) for w in (3, 1, 3, 3, 4))
+        cam = data['c2w'][:, :3, 3]
+        merge = lambda: scene_merge([part], culled, cam, out=out)                                  # noqa: E731
+        merge()
+        row["merge_culled_ms"] = round(statistics.median(graph_ms(merge) for _ in range(3)), 4)
+        del out, dst, flags, index, work
+
+    def eager(F, cull):
+        def run(k):
+            with torch.inference_mode():
+                for s in range(0, k, F):
+                    scene.forward_frames(data, [poses[(s + f) % T] for f in range(F)], cull_scene=cull)
+        return run
+    rounds = {}
+    for _ in range(3):                                                                              # off and on alternate on the same box
+        for cull, tag in ((False, "off"), (True, "on")):
+            for F in (1, 4):
+                rounds.setdefault("eager_F%d_fps_cull_%s" % (F, tag), []).append(round(fps(eager(F, cull), a.frames, a.repeats), 1))
+    row["cull_rounds"] = rounds
+    for k, v in rounds.items():
+        row[k] = statistics.median(v)
+    for what in ("eager_F1_fps", "eager_F4_fps"):
+        row[what + "_cull_spread"] = round(max(max(rounds[what + "_cull_" + t]) - min(rounds[what + "_cull_" + t]) for t in ("off", "on")), 1)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gaussians", type=int, default=300000)
@@ -110,6 +172,7 @@ def main():
     ap.add_argument("--frames", type=int, default=48)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--res", type=int, default=1024)
+    ap.add_argument("--cull", action="store_true", help="add the columns of the per-camera scene cull (B25): culling off and on, alternated")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = configs.TrainConfig(); cfg.device = str(dev); cfg.render.bg_color = (0.5, 0.5, 0.5)
@@ -176,6 +239,8 @@ def main():
         row["graph_replay_fps"] = round(fps(lambda k: [pl.replay(poses[i % T]) for i in range(k)], a.frames, a.repeats), 1)
         row["graph_replay_complete"] = bool(pl.check())
         pl.close()
+        if a.cull:
+            row.update(cull_columns(scene, bg, data, poses, part, a, dev))
         rows.append(row)
         print("scene %8d  activation %7.3f ms  merge %7.3f ms (%6.1f GB/s, %4.1f %% of 8 TB/s)  sh4 merge %7.3f ms  TORCH REFERENCE composition "
               "%7.3f ms" % (n, row["activation_ms"], row["merge_ms"], row["merge_GBps"], 100 * row["merge_share_of_hbm_spec"], row["merge_sh4_ms"],
@@ -187,6 +252,12 @@ def main():
                                   row["TORCH_REFERENCE_eager_F1_fps"]), flush=True)
         print("               rasterizer, one frame: block pairs %d, reference tile pairs %d, segments %d, overflow flag %d"
               % (row["block_pairs"], row["reference_tile_pairs"], row["segments"], row["overflow"]), flush=True)
+        if a.cull:
+            print("               cull: kept %d (%.1f %%)  flags + compaction + gather %7.3f ms  merge over the culled block %7.3f ms"
+                  % (row["kept_gaussians"], 100 * row["kept_share"], row["cull_ms"], row["merge_culled_ms"]), flush=True)
+            for what in ("eager_F1_fps", "eager_F4_fps"):
+                print("               %-16s cull off %s  on %s frames/s (three alternating rounds; spread %.1f)"
+                      % (what, row["cull_rounds"][what + "_cull_off"], row["cull_rounds"][what + "_cull_on"], row[what + "_cull_spread"]), flush=True)
         del scene, bg, bg4, arrays
         torch.cuda.empty_cache()
     print(json.dumps(rows))
