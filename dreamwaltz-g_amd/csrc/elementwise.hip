@@ -830,6 +830,34 @@ __global__ __launch_bounds__(256) void k_vae_dx_unpack(long long npix, long long
         for (int e = 0; e < 3; e++) dst[e * hw] = x.get(e) * sc;
     }
 }
+// ---- the f32x VAE decoder's boundary converters (B26: AutoencoderKL.decode of core/guidance/vae.py:42-46), one launch each -----------------------
+// latents [B,C,h,w] fp32 (C <= 8) -> x [B,h,w,8] f32x: channels 0..C-1 = v * scale (1 / scaling_factor; one rounding as in `1 / s * latents`),
+// channels C..7 = 0 (post_quant_conv's padded input group)
+__global__ __launch_bounds__(256) void k_vae_latent_pack(long long npix, long long hw, int C, const float* __restrict__ lat, float scale,
+                                                         dwg_xs* __restrict__ x) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < npix; i += (long long)gridDim.x * 256) {
+        const long long b = i / hw, r = i - b * hw;
+        const float* src = lat + b * C * hw + r;
+        dwg_x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; e++) o.set(e, e < C ? src[e * hw] * scale : 0.f);
+        o.store(x + 8 * i);
+    }
+}
+// y [B,H,W,8] f32x (channels 0..2: conv_out) -> image [B,3,H,W] fp32: clamp(0.5 y + 0.5, 0, 1) (`(image / 2 + 0.5).clamp(0, 1)`; 0.5 y is exact,
+// one rounding), or y itself when raw.  fmaxf / fminf drop a NaN operand, so a NaN is passed through by hand: a non-finite decode stays visible.
+__global__ __launch_bounds__(256) void k_vae_image_unpack(long long npix, long long hw, const dwg_xs* __restrict__ y, int raw, float* __restrict__ out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < npix; i += (long long)gridDim.x * 256) {
+        const long long b = i / hw, r = i - b * hw;
+        const dwg_x8 x = dwg_x8::load(y + 8 * i);
+        float* dst = out + b * 3 * hw + r;
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+            const float v = x.get(e), s = 0.5f * v + 0.5f;
+            dst[e * hw] = raw ? v : (s != s ? s : fminf(fmaxf(s, 0.f), 1.f));
+        }
+    }
+}
 // Range telemetry of a stored f32x tensor (round 5): the format saturates at +-65504 instead of overflowing (dwg_x_split) and loses significand
 // bits once the hi half goes subnormal (|x| < 6.1e-5) -- silently, in the hot path.  This scan is the cold-path witness: it walks a tensor the
 // plan has written and counts  [0] hi halves AT +-65504 (a saturated value, or a legitimate one on the edge: equally worth a warning),
@@ -1269,6 +1297,26 @@ int dwg_vae_dx_unpack(int32_t B, int32_t H, int32_t W, const void* dx_xs, const 
     const long long hw = (long long)H * W, npix = (long long)B * hw;
     if (npix == 0) return DWG_OK;
     DWG_LAUNCH("vae_dx_unpack", k_vae_dx_unpack, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, npix, hw, (const dwg_xs*)dx_xs, inv, out_nchw);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_vae_latent_pack(int32_t B, int32_t C, int32_t H, int32_t W, const float* latents_nchw, float scale, void* x_xs, dwg_stream_t stream) {
+    if (B < 0 || C < 1 || C > 8 || H < 0 || W < 0 || !latents_nchw || !x_xs || ((uintptr_t)x_xs % 16)) return DWG_E_ARG;
+    const long long hw = (long long)H * W, npix = (long long)B * hw;
+    if (npix == 0) return DWG_OK;
+    DWG_LAUNCH("vae_latent_pack", k_vae_latent_pack, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, npix, hw, (int)C, latents_nchw, scale,
+               (dwg_xs*)x_xs);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_vae_image_unpack(int32_t B, int32_t H, int32_t W, const void* y_xs, int32_t raw, float* out_nchw, dwg_stream_t stream) {
+    if (B < 0 || H < 0 || W < 0 || !y_xs || !out_nchw || ((uintptr_t)y_xs % 16)) return DWG_E_ARG;
+    const long long hw = (long long)H * W, npix = (long long)B * hw;
+    if (npix == 0) return DWG_OK;
+    DWG_LAUNCH("vae_image_unpack", k_vae_image_unpack, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, npix, hw, (const dwg_xs*)y_xs, (int)raw,
+               out_nchw);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

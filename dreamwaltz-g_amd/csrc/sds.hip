@@ -58,6 +58,36 @@ __global__ __launch_bounds__(256) void k_sds_add_noise(int V, long long n4, cons
     }
 }
 
+// DDPMScheduler.step for epsilon prediction, 'fixed_small' variance, no sample clipping (include/dwg_sds.h has the formulas).  The per-view
+// coefficients are a dozen scalar operations, recomputed per thread; beta_t is formed as (ap - at) / ap, not 1 - at / ap: the difference of the
+// two table entries is exact where they are within a factor of two, the quotient near 1 would lose what the subtraction then magnifies.
+__global__ __launch_bounds__(256) void k_sds_ddpm_step(int V, long long n4, const float4* __restrict__ xt, const float4* __restrict__ eps,
+                                                       const float4* __restrict__ noise, const float* __restrict__ acp, int n_steps,
+                                                       const int64_t* __restrict__ t, const int64_t* __restrict__ t_prev, float4* __restrict__ x0_out,
+                                                       float4* __restrict__ prev_out) {
+    const long long total = (long long)V * n4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long v = i / n4;
+        const float at = acp_at(acp, n_steps, t, v);
+        const float ap = t_prev[v] >= 0 ? acp_at(acp, n_steps, t_prev, v) : 1.f;
+        const float bt = 1.f - at, bp = 1.f - ap, beta = (ap - at) / ap, alpha = at / ap;
+        const float rs = 1.f / sqrtf(at), sb = sqrtf(bt);
+        const float c0 = sqrtf(ap) * beta / bt, ct = sqrtf(alpha) * bp / bt;
+        const float sd = t[v] > 0 ? sqrtf(fmaxf(bp / bt * beta, 1e-20f)) : 0.f;
+        const float4 x = xt[i], e = eps[i];
+        const float4 o = make_float4((x.x - sb * e.x) * rs, (x.y - sb * e.y) * rs, (x.z - sb * e.z) * rs, (x.w - sb * e.w) * rs);
+        if (x0_out) x0_out[i] = o;
+        if (prev_out) {
+            float4 p = make_float4(c0 * o.x + ct * x.x, c0 * o.y + ct * x.y, c0 * o.z + ct * x.z, c0 * o.w + ct * x.w);
+            if (t[v] > 0) {
+                const float4 z = noise[i];
+                p.x += sd * z.x; p.y += sd * z.y; p.z += sd * z.z; p.w += sd * z.w;
+            }
+            prev_out[i] = p;
+        }
+    }
+}
+
 __device__ __forceinline__ float nan_to_num_f(float v) {
     if (v != v) return 0.f;
     if (v > FLT_MAX) return FLT_MAX;
@@ -121,6 +151,21 @@ int dwg_sds_add_noise(int32_t V, int64_t n, const float* latents, const float* n
     if (!latents || !noise || !alphas_cumprod || !timestep || !out || bad16(latents) || bad16(noise) || bad16(out)) return DWG_E_ARG;
     DWG_LAUNCH("sds_add_noise", k_sds_add_noise, dim3(blocks_for((long long)V * (n / 4))), dim3(256), 0, (hipStream_t)stream, V, (long long)(n / 4),
                (const float4*)latents, (const float4*)noise, alphas_cumprod, n_steps, timestep, (float4*)out);
+    DWG_RETURN_IF_LAUNCH_FAILED();
+    return DWG_OK;
+}
+
+int dwg_sds_ddpm_step(int32_t V, int64_t n, const float* sample, const float* noise_pred, const float* noise, const float* alphas_cumprod,
+                      int32_t n_steps, const int64_t* timestep, const int64_t* prev_timestep, float* pred_original_sample, float* prev_sample,
+                      dwg_stream_t stream) {
+    if (V < 0 || n < 0 || (n & 3) || n_steps < 1) return DWG_E_ARG;
+    if (V == 0 || n == 0 || (!pred_original_sample && !prev_sample)) return DWG_OK;
+    if (!sample || !noise_pred || !alphas_cumprod || !timestep || !prev_timestep || bad16(sample) || bad16(noise_pred)) return DWG_E_ARG;
+    if (prev_sample && (!noise || bad16(noise) || bad16(prev_sample))) return DWG_E_ARG;
+    if (pred_original_sample && bad16(pred_original_sample)) return DWG_E_ARG;
+    DWG_LAUNCH("sds_ddpm_step", k_sds_ddpm_step, dim3(blocks_for((long long)V * (n / 4))), dim3(256), 0, (hipStream_t)stream, V, (long long)(n / 4),
+               (const float4*)sample, (const float4*)noise_pred, (const float4*)noise, alphas_cumprod, n_steps, timestep, prev_timestep,
+               (float4*)pred_original_sample, (float4*)prev_sample);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

@@ -8,6 +8,9 @@
   ._predict(latents, text, cond_inputs)     /root/reference/core/guidance/controlnet.py:83-114 (reads self.timestep)
   .prepare_image / .prepare_condition       controlnet.py:33-72 (PIL -> LANCZOS resize -> float/255 -> NCHW -> repeat)
   .encode_images(images)  (differentiable)  /root/reference/core/guidance/vae.py:34-40
+  .decode_latents(latents, 'pt')            vae.py:42-46          } B26, opt-in (decoder=True): sd15.VAEDecoderPlan and
+  .get_noise_pred / .get_denoise_pred       basic.py:443-527      } dwg_sds_ddpm_step; losses z0 / z0_final / x0 / x0_final
+  latent_to_image(guidance, latent, ch)     core/trainer.py:59-68 } (basic.py:846-880, 896-898), grad_viz outputs (907-915)
   SpecifyGradient                           basic.py:213-226
   TimePrioritizedScheduler.get_timestep     /root/reference/core/guidance/time_prior.py:321-352 ('uniform' / 'constant' / 'linear')
 Attributes other code reads (basic.py:334-335,453): scheduler.scale_model_input, alphas_cumprod, vae_scale_factor,
@@ -97,13 +100,44 @@ def C(value, current_step=None, max_iteration=None) -> float:
     raise NotImplementedError("scheduled min/max timestep strings")
 
 
+DENOISING_LOSS_TYPES = ('z0', 'z0_final', 'x0', 'x0_final')        # basic.py:344-345: losses on a denoised prediction, not on the score
+
+
+def inference_timesteps(num_timesteps=50, num_train_timesteps=1000, steps_offset=1) -> List[int]:
+    """DDPMScheduler.set_timesteps ('leading' spacing, SD-1.5's scheduler config): arange(n) * (num_train_timesteps // n), reversed, plus
+    steps_offset -- 981, 961, ..., 1 for 50 steps.  A host list, largest first."""
+    n = int(num_timesteps)
+    if not 1 <= n <= num_train_timesteps:
+        raise ValueError("num_timesteps must be in 1..%d, got %r" % (num_train_timesteps, num_timesteps))
+    ratio = num_train_timesteps // n
+    return [(n - 1 - i) * ratio + int(steps_offset) for i in range(n)]
+
+
+def latent_to_image(guidance, latent: torch.Tensor, color_channel: int):
+    """core/trainer.py:59-68: a latent NeRF's render ([B,h,w,4] when color_channel == 3, else [B,4,h,w]) -> the image the VAE decodes it to,
+    in the same layout.  Latents larger than 128 are area-averaged down to 128 x 128 first, as there."""
+    if color_channel == 3:
+        latent = latent.permute(0, 3, 1, 2).contiguous()
+    if latent.shape[-2] > 128 or latent.shape[-1] > 128:
+        latent = F.interpolate(latent, (128, 128), mode='area')
+    image = guidance.decode_latents(latent)
+    if color_channel == 3:
+        image = image.permute(0, 2, 3, 1).contiguous()
+    return image
+
+
 class ControlNetScoreDistillation:
     def __init__(self, device, unet_cfg: Optional[sd15.UNetConfig] = None, vae_cfg: Optional[sd15.VAEConfig] = None,
                  unet_sd=None, controlnet_sd=None, vae_sd=None, image_hw=512, guidance_scale=None, min_timestep=None,
-                 max_timestep=None, seed=0, cfg: Optional[GuideConfig] = None, text_len=77, dtype="f32x", views=1, share_weights_with=None):
+                 max_timestep=None, seed=0, cfg: Optional[GuideConfig] = None, text_len=77, dtype="f32x", views=1, share_weights_with=None,
+                 decoder=False, vae_decoder_sd=None, steps_offset=1):
         """`views` > 1: ONE call distils that many rendered views at once (inputs [V,3,H,W]; the plans are built for a VAE batch of V and a
         denoiser batch of 2 V -- nothing in the reference to mirror, its call is batch 1: checklist Q11).  `share_weights_with`: another
-        guidance object of the same dtype whose kernel-layout weights this one's plans point at (no second copy in HBM)."""
+        guidance object of the same dtype whose kernel-layout weights this one's plans point at (no second copy in HBM).
+        `decoder=True` (B26) adds the native VAE decoder (sd15.VAEDecoderPlan, built on demand per (latent_hw, batch), all plans on one
+        `Weights` of `vae_decoder_sd` -- `post_quant_conv.*` / `decoder.*`; None: random weights at seed + 3) and with it decode_latents,
+        get_noise_pred, get_denoise_pred, the z0 / z0_final / x0 / x0_final losses and the grad_viz outputs.  Off (the default) the object
+        allocates and launches what it did before and each of those raises.  `steps_offset`: the inference scheduler's (SD-1.5: 1)."""
         self.device = torch.device(device)
         self.views = int(views)
         self.dtype_name = sd15.dtype_name(dtype)          # precision of the denoiser / VAE plans: "f32x" (default: the reference's fp32 GS-stage
@@ -112,6 +146,18 @@ class ControlNetScoreDistillation:
         self.cfg = cfg if cfg is not None else GuideConfig()
         self.unet_cfg = unet_cfg or sd15.UNetConfig()
         self.vae_cfg = vae_cfg or sd15.VAEConfig()
+        # BasicStableDiffusion.__init__ (basic.py:229-267, 344-345): what is not built is refused before any plan is
+        self.loss_type, self.weight_type = self.cfg.sds_loss_type, self.cfg.sds_weight_type
+        self.has_decoder = bool(decoder)
+        if self.loss_type == 'ism':
+            raise NotImplementedError("sds_loss_type 'ism' (interval score matching: a DDIM inversion per step, basic.py:665-776) is not built")
+        if self.loss_type in DENOISING_LOSS_TYPES and not self.has_decoder:
+            raise NotImplementedError("sds_loss_type %r is a denoising loss: it needs the scheduler step and the native VAE decoder -- construct "
+                                      "ControlNetScoreDistillation(..., decoder=True)" % (self.loss_type,))
+        if self.loss_type not in ('sds',) + DENOISING_LOSS_TYPES or self.weight_type not in ('sjc', 'dreamfusion', 'latent-nerf', 'ism'):
+            raise NotImplementedError("only the score-based 'sds' loss of the shipped recipes is on the hot path")
+        self.is_denoising_mode = self.loss_type in DENOISING_LOSS_TYPES
+        self.steps_offset = int(steps_offset)
         shared = share_weights_with
         if shared is not None and shared.dtype_name != self.dtype_name:
             raise ValueError("share_weights_with: plans of dtype %s cannot point at %s weights" % (self.dtype_name, shared.dtype_name))
@@ -122,6 +168,17 @@ class ControlNetScoreDistillation:
                 controlnet_sd = sd15.random_state_dict(sd15.controlnet_param_shapes(self.unet_cfg), seed=seed + 1)
             if vae_sd is None:
                 vae_sd = sd15.random_state_dict(sd15.vae_encoder_param_shapes(self.vae_cfg), seed=seed + 2)
+        self._decoder_weights, self._decoder_plans = None, {}
+        if self.has_decoder:
+            if vae_decoder_sd is None and shared is not None and getattr(shared, "_decoder_weights", None) is not None:
+                self._decoder_weights = shared._decoder_weights
+            else:
+                if vae_decoder_sd is None:
+                    vae_decoder_sd = sd15.random_state_dict(sd15.vae_decoder_param_shapes(self.vae_cfg), seed=seed + 3)
+                for key in sd15.vae_decoder_param_shapes(self.vae_cfg):
+                    if key not in vae_decoder_sd:
+                        raise KeyError("vae_decoder_sd lacks the decoder key %r" % key)
+                self._decoder_weights = sd15.Weights(vae_decoder_sd, self.device, self.dtype_name)      # (copies are made as plans ask for them)
         self.image_hw = image_hw
         down = 2 ** (len(self.vae_cfg.block_out_channels) - 1)
         self.latent_hw = image_hw // down
@@ -133,9 +190,6 @@ class ControlNetScoreDistillation:
         self.vae = sd15.VAEEncoderPlan(self.vae_cfg, vae_sd, self.device, image_hw=image_hw, dtype=self.dtype_name, batch=self.views,
                                        weights=shared.vae.weights if shared is not None else None)
         # BasicStableDiffusion.__init__ (basic.py:229-267)
-        self.loss_type, self.weight_type = self.cfg.sds_loss_type, self.cfg.sds_weight_type
-        if self.loss_type != 'sds' or self.weight_type not in ('sjc', 'dreamfusion', 'latent-nerf', 'ism'):
-            raise NotImplementedError("only the score-based 'sds' loss of the shipped recipes is on the hot path")
         self.initial_guidance_scale = self.cfg.guidance_scale if guidance_scale is None else guidance_scale
         self.guidance_adjust = self.cfg.guidance_adjust
         self.do_classifier_free_guidance = self.initial_guidance_scale > 1.0
@@ -185,10 +239,14 @@ class ControlNetScoreDistillation:
     def capture_graphs(self):
         for p in self.plans() + (self.denoiser.pre,):
             p.capture()
+        self._graphs_captured = True                # decoder plans (B26) built from here on are captured at their first use
+        for d in self._decoder_plans.values():
+            d.capture()
 
     def set_use_graphs(self, on: bool):
-        for p in self.plans() + (self.denoiser.pre,):
+        for p in self.plans() + (self.denoiser.pre,) + tuple(d.plan for d in self._decoder_plans.values()):
             p.use_graph = bool(on)
+        self._use_graphs = bool(on)
 
     # -- time_prior.py:292-352 ------------------------------------------------------------------------------------------
     @property
@@ -364,6 +422,129 @@ class ControlNetScoreDistillation:
         n = torch.randn(shape, device=self.device, generator=generator)
         return pn, t, n
 
+    # -- B26: the decoder side (vae.py:42-46, basic.py:443-527) -------------------------------------------------------------
+    def _need_decoder(self, what):
+        if not self.has_decoder:
+            raise RuntimeError("%s needs the native VAE decoder and scheduler step, which this guidance object was built without: construct "
+                               "ControlNetScoreDistillation(..., decoder=True)" % what)
+
+    def decoder_plan(self, latent_hw, batch):
+        """The decoder plan for [batch, C, latent_hw, latent_hw] latents, built (and captured) at its first use; every plan points at the one
+        `Weights` of this object."""
+        self._need_decoder("decoder_plan")
+        key = (int(latent_hw), int(batch))
+        plan = self._decoder_plans.get(key)
+        if plan is None:
+            plan = sd15.VAEDecoderPlan(self.vae_cfg, None, self.device, latent_hw=key[0], dtype=self.dtype_name, batch=key[1],
+                                       weights=self._decoder_weights)
+            if getattr(self, "_graphs_captured", False):
+                plan.capture()
+                plan.plan.use_graph = getattr(self, "_use_graphs", True)
+            self._decoder_plans[key] = plan
+        return plan
+
+    @torch.no_grad()
+    def decode_latents(self, latents, output_type='pt'):
+        """vae.py:42-46: latents [B,4,h,h] -> images [B,3,8h,8h] in [0,1] (VaeImageProcessor.postprocess 'pt')."""
+        self._need_decoder("decode_latents")
+        if output_type != 'pt':
+            raise NotImplementedError("decode_latents(output_type=%r): only 'pt' (a [B,3,H,W] tensor in [0,1]) is built" % (output_type,))
+        if not torch.is_tensor(latents) or latents.dim() != 4:
+            raise ValueError("decode_latents: latents must be a [B,C,h,h] tensor, got %r" % (getattr(latents, "shape", type(latents)),))
+        return self.decoder_plan(latents.shape[-1], latents.shape[0]).decode(latents)
+
+    @torch.no_grad()
+    def get_noise_pred(self, latents_noisy, text_embeddings, guidance_rescale: float = 0.0, timestep=None, **kwargs):
+        """basic.py:443-467: the classifier-free-combined prediction for latents [V,4,h,w].  `timestep` ([V] long; None: self.timestep, as in the
+        reference) predicts at another step of the chain without disturbing self.timestep."""
+        self._need_decoder("get_noise_pred")
+        if not self.do_classifier_free_guidance:
+            raise NotImplementedError("guidance_scale <= 1 (no classifier-free guidance): the plans are built for the CFG batch of 2")
+        if guidance_rescale > 0.0:
+            raise NotImplementedError("guidance_rescale")
+        latents_model_input = latents_noisy if self.denoiser.shared_prefix else torch.cat([latents_noisy] * 2, dim=0)
+        kept = self.timestep
+        if timestep is not None:
+            self.timestep = timestep
+        try:
+            latents_model_input = self.scheduler.scale_model_input(latents_model_input, self.timestep)
+            noise_pred = self._predict(latents_model_input, text_embeddings, **kwargs)
+        finally:
+            self.timestep = kept
+        noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
+        return noise_pred_uncond + self.guidance_scale * (noise_pred_text - noise_pred_uncond)
+
+    def inference_timesteps(self, num_timesteps=50):
+        return inference_timesteps(num_timesteps, self.num_train_timesteps, self.steps_offset)
+
+    def ddpm_step(self, sample, noise_pred, timestep, prev_timestep, noise=None, want_original=True, want_prev=True):
+        """One reverse step per view (include/dwg_sds.h dwg_sds_ddpm_step: DDPMScheduler.step, epsilon prediction, fixed_small variance, no
+        clipping), one launch, timesteps read on the device.  Returns (pred_original_sample, prev_sample), None for the one not wanted."""
+        x, e = sample.contiguous(), noise_pred.contiguous()
+        if not (_fused_ok(x, e) and x.shape == e.shape and x[0].numel() % 4 == 0):
+            raise ValueError("ddpm_step: sample and noise_pred must be fp32 CUDA tensors of one shape, 4 | elements per view")
+        t, tp = timestep.to(torch.long).contiguous(), prev_timestep.to(torch.long).contiguous()
+        if not (t.is_cuda and tp.is_cuda and t.numel() == x.shape[0] and tp.numel() == x.shape[0]):
+            raise ValueError("ddpm_step: one timestep and one previous timestep per view, on the device")
+        z = None
+        if want_prev:
+            if noise is None or noise.shape != x.shape or not _fused_ok(noise):
+                raise ValueError("ddpm_step: prev_sample needs the variance noise, an fp32 CUDA tensor of the sample's shape")
+            z = noise.contiguous()
+        x0 = torch.empty_like(x) if want_original else None
+        prev = torch.empty_like(x) if want_prev else None
+        _lib.check(_lib.lib().dwg_sds_ddpm_step(x.shape[0], x[0].numel(), _lib.ptr(x), _lib.ptr(e), _lib.ptr(z), _lib.ptr(self.alphas_cumprod),
+                                                int(self.alphas_cumprod.numel()), _lib.ptr(t), _lib.ptr(tp), _lib.ptr(x0), _lib.ptr(prev),
+                                                _lib.stream(x)), "dwg_sds_ddpm_step")
+        return x0, prev
+
+    @torch.no_grad()
+    def get_denoise_pred(self, latents_noisy, noise_pred, text_embeddings, iterative, num_timesteps=50, step_noise=None, generator=None, **kwargs):
+        """basic.py:469-527.  The training timestep of each view is moved to the inference grid by the reference's rule (the first grid step that
+        is not above it; the grid's first step when all are), one scheduler step from there gives latents_1orig / latents_1step, and with
+        `iterative` the rest of the grid is walked down to latents_final, each step predicted at ITS timestep (get_noise_pred's override).
+        `step_noise`: the variance noise, a sequence indexed by grid position (step_noise[j] [V,4,h,w] is used by the step taken at grid
+        step j); None: drawn on the device from `generator`, one draw per step with t > 0.  Views that start lower on the grid wait, unchanged,
+        until the walk reaches them: all views are predicted in one denoiser call per grid step."""
+        self._need_decoder("get_denoise_pred")
+        bs = latents_noisy.shape[0]
+        if bs != self.views:
+            raise ValueError("get_denoise_pred: the denoiser plan is built for %d view(s), got a batch of %d" % (self.views, bs))
+        grid_host = self.inference_timesteps(num_timesteps)
+        n, ratio = len(grid_host), self.num_train_timesteps // len(grid_host)
+        grid = torch.tensor(grid_host, device=self.device, dtype=torch.long)
+        large_enough_idxs = grid.expand([bs, -1]) > self.timestep[:bs].unsqueeze(-1)
+        idxs = (~large_enough_idxs).to(torch.int8).argmax(dim=1)      # first False; 0 when there is none (torch.min over booleans, basic.py:486)
+        t = grid[idxs]
+        fracs = list((t / self.num_train_timesteps).cpu().numpy())
+        idx_host = [int(i) for i in idxs.tolist()]
+
+        def noise_at(j):
+            if step_noise is not None:
+                return step_noise[j].to(self.device, torch.float32)
+            if grid_host[j] > 0:
+                return torch.randn(latents_noisy.shape, device=self.device, dtype=torch.float32, generator=generator)
+            return torch.zeros(latents_noisy.shape, device=self.device, dtype=torch.float32)      # (never read: the step at t = 0 adds no noise)
+
+        if len(set(idx_host)) == 1:
+            z = noise_at(idx_host[0])
+        elif step_noise is not None:
+            z = torch.cat([noise_at(j)[b:b + 1] for b, j in enumerate(idx_host)])
+        else:
+            z = torch.randn(latents_noisy.shape, device=self.device, dtype=torch.float32, generator=generator)
+        latents_1orig, latents_1step = self.ddpm_step(latents_noisy, noise_pred, t, t - ratio, z)
+        step_outputs = {"noise_levels": fracs, "latents_noisy": latents_noisy, "latents_1orig": latents_1orig, "latents_1step": latents_1step}
+        if iterative:
+            latents = latents_1step
+            for j in range(min(idx_host) + 1, n):
+                tj = torch.full([bs], grid_host[j], device=self.device, dtype=torch.long)
+                pred = self.get_noise_pred(latents_noisy=latents, text_embeddings=text_embeddings, timestep=tj, **kwargs)
+                _, nxt = self.ddpm_step(latents, pred, tj, tj - ratio, noise_at(j), want_original=False)
+                started = [i < j for i in idx_host]
+                latents = nxt if all(started) else torch.where(torch.tensor(started, device=self.device).view(-1, 1, 1, 1), nxt, latents)
+            step_outputs["latents_final"] = latents
+        return step_outputs
+
     def calc_gradients(self, latents_noisy, text_embeds_dict, noise, guidance_rescale: float = 0.0, train_step=None, max_iteration=None,
                        **kwargs):
         """basic.py:546-663, the 'sds' branch."""
@@ -420,6 +601,8 @@ class ControlNetScoreDistillation:
         """inputs [V,3,H,W] rendered image(s) in [0,1] (requires grad; V = self.views, 1 in the reference).  Returns the reference's result dict."""
         if inputs.size(0) != self.views:
             raise ValueError("this guidance object's plans are built for %d view(s) per call, got a batch of %d" % (self.views, inputs.size(0)))
+        if self.is_denoising_mode and inputs.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("sds_loss_type %r inside a captured step (step_graph): the scheduler grid is read on the host" % (self.loss_type,))
         if inputs.size(1) == 3:                                            # pixel-wise gradient operations (basic.py:795-817)
             if self.cfg.pgc_clip_rgb >= 0:
                 inputs.register_hook(build_pgc_hook_func(self.cfg.pgc_clip_rgb, self.cfg.pgc_suppress_type, kwargs.get('scaler')))
@@ -435,11 +618,37 @@ class ControlNetScoreDistillation:
                 noise = torch.randn(latents.shape, device=latents.device, dtype=latents.dtype, generator=generator)   # RNG draw #3
             latents_noisy = self.add_noise(latents, noise, self.timestep) if add_noise else latents
         outputs = {'latents': latents, 'timestep': self.timestep}
-        with torch.no_grad():
-            gradients, noise_pred, _ = self.calc_gradients(latents_noisy=latents_noisy, text_embeds_dict=text_embeds_dict, noise=noise,
-                                                           train_step=train_step, max_iteration=max_iteration, **kwargs)
-            sources = latents
-            targets = (sources - gradients).detach()
+        den_kw = {k: kwargs.pop(k) for k in ('num_timesteps', 'step_noise') if k in kwargs}      # get_denoise_pred's own (test / viz extensions)
+        if self.is_denoising_mode:                                         # basic.py:846-880, 896-898
+            with torch.no_grad():
+                text_keys = ('neg', 'text') if self.use_negative_text else ('null', 'text')
+                text_embeddings = self.prepare_text_embeddings(text_embeds_dict, text_keys)
+                noise_pred = self.get_noise_pred(latents_noisy=latents_noisy, text_embeddings=text_embeddings, **kwargs)
+                outputs.update(self.get_denoise_pred(latents_noisy=latents_noisy, noise_pred=noise_pred, text_embeddings=text_embeddings,
+                                                     iterative=(self.cfg.grad_viz or self.loss_type.endswith('_final')), generator=generator,
+                                                     **den_kw, **kwargs))
+                if self.loss_type == 'z0':
+                    sources, targets = latents, outputs['latents_1orig']
+                elif self.loss_type == 'z0_final':
+                    sources, targets = latents, outputs['latents_final']
+                elif self.loss_type == 'x0':
+                    sources, targets = inputs, self.decode_latents(outputs['latents_1orig'])
+                else:                                                      # 'x0_final'
+                    sources, targets = inputs, self.decode_latents(outputs['latents_final'])
+                gradients = (sources - targets).detach()
+            # "SpecifyGradient is not straightforward, use a reparameterization trick instead" (basic.py:897): d loss / d sources = (sources - targets) / B
+            diffusion_loss = 0.5 * F.mse_loss(sources, targets, reduction="sum") / sources.size(0)
+        else:
+            with torch.no_grad():
+                gradients, noise_pred, text_embeddings = self.calc_gradients(latents_noisy=latents_noisy, text_embeds_dict=text_embeds_dict, noise=noise,
+                                                                             train_step=train_step, max_iteration=max_iteration, **kwargs)
+                sources = latents
+                targets = (sources - gradients).detach()
+            diffusion_loss = SpecifyGradient.apply(sources, gradients)
         outputs['sources'], outputs['targets'], outputs['gradients'] = sources, targets, gradients
-        outputs['diffusion_loss'] = SpecifyGradient.apply(sources, gradients)
+        outputs['diffusion_loss'] = diffusion_loss
+        # basic.py:907-915.  An object built without the decoder keeps ignoring grad_viz, as it always has
+        if grad_viz and self.has_decoder and 'latents_final' not in outputs:
+            outputs.update(self.get_denoise_pred(latents_noisy=latents_noisy, noise_pred=noise_pred, text_embeddings=text_embeddings, iterative=True,
+                                                 generator=generator, **den_kw, **kwargs))
         return outputs

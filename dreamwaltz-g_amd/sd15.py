@@ -1,4 +1,4 @@
-"""SD-1.5 UNet + ControlNet + VAE-encoder graphs on the HIP kernels (boundary B4).
+"""SD-1.5 UNet + ControlNet + VAE-encoder (and, B26, VAE-decoder) graphs on the HIP kernels (boundary B4).
 
 The reference obtains these networks from `diffusers` (UNet2DConditionModel, ControlNetModel, AutoencoderKL.encoder; call
 sites /root/reference/core/guidance/controlnet.py:98-114, vae.py:34-40, basic.py:147,176,208).  diffusers is a third-party
@@ -244,6 +244,34 @@ def vae_encoder_param_shapes(cfg: VAEConfig) -> "OrderedDict[str, tuple]":
     sh["encoder.conv_out.weight"] = (2 * cfg.latent_channels, c, 3, 3); sh["encoder.conv_out.bias"] = (2 * cfg.latent_channels,)
     sh["quant_conv.weight"] = (2 * cfg.latent_channels, 2 * cfg.latent_channels, 1, 1)
     sh["quant_conv.bias"] = (2 * cfg.latent_channels,)
+    return sh
+
+
+def vae_decoder_param_shapes(cfg: VAEConfig) -> "OrderedDict[str, tuple]":
+    """diffusers' AutoencoderKL key names / shapes of `post_quant_conv` and `decoder.*` (SD-1.5: 20 + 49 490 179 parameters)."""
+    sh = OrderedDict()
+    boc = cfg.block_out_channels
+    lc = cfg.latent_channels
+    sh["post_quant_conv.weight"] = (lc, lc, 1, 1); sh["post_quant_conv.bias"] = (lc,)
+    c = boc[-1]
+    sh["decoder.conv_in.weight"] = (c, lc, 3, 3); sh["decoder.conv_in.bias"] = (c,)
+    _resnet_shapes(sh, "decoder.mid_block.resnets.0", c, c, 0)
+    a = "decoder.mid_block.attentions.0"
+    sh[a + ".group_norm.weight"] = (c,); sh[a + ".group_norm.bias"] = (c,)
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        sh["%s.%s.weight" % (a, n)] = (c, c); sh["%s.%s.bias" % (a, n)] = (c,)
+    _resnet_shapes(sh, "decoder.mid_block.resnets.1", c, c, 0)
+    rev = list(reversed(boc))
+    prev = rev[0]
+    for i, cout in enumerate(rev):
+        for j in range(cfg.layers_per_block + 1):
+            _resnet_shapes(sh, "decoder.up_blocks.%d.resnets.%d" % (i, j), prev, cout, 0)
+            prev = cout
+        if i != len(rev) - 1:
+            sh["decoder.up_blocks.%d.upsamplers.0.conv.weight" % i] = (cout, cout, 3, 3)
+            sh["decoder.up_blocks.%d.upsamplers.0.conv.bias" % i] = (cout,)
+    sh["decoder.conv_norm_out.weight"] = (boc[0],); sh["decoder.conv_norm_out.bias"] = (boc[0],)
+    sh["decoder.conv_out.weight"] = (cfg.in_channels, boc[0], 3, 3); sh["decoder.conv_out.bias"] = (cfg.in_channels,)
     return sh
 
 
@@ -502,6 +530,21 @@ class Weights:
             self.cache[key] = self._to_dev(wp)
         return self.cache[key]
 
+    def conv_pad8(self, name):
+        """(weight, bias) of a convolution whose OUTPUT channels are padded with zero rows to a whole group of 8 (weight [pad8(Cout),KH,KW,
+        pad8(Cin)], bias fp32 [pad8(Cout)]): the layer's result is then a plan buffer the next layer -- or an f32x converter -- reads as it
+        is, its padded channels exactly zero (the VAE decoder's post_quant_conv -> 4 and conv_out -> 3)."""
+        key = ("pad8", name)
+        if key not in self.cache:
+            w = self.sd[name + ".weight"].float()
+            cout, cin = w.shape[0], w.shape[1]
+            wp = torch.zeros(_pad8(cout), w.shape[2], w.shape[3], _pad8(cin))
+            wp[:cout, :, :, :cin] = w.permute(0, 2, 3, 1)
+            bp = torch.zeros(_pad8(cout))
+            bp[:cout] = self.sd[name + ".bias"].float()
+            self.cache[key] = (self._to_dev(wp), bp.to(self.device).contiguous())
+        return self.cache[key]
+
     def conv_dgrad_s2(self, name, py, px):
         """Tap subset of a 3x3 stride-2 convolution's weights that reaches the input pixels of parity (py, px), laid out as the
         weights [Cin_x, KH', KW', Cout_y] of the stride-1 convolution over the incoming gradient that produces them:
@@ -595,7 +638,9 @@ class Builder:
             Ho, Wo = out_hw
         y = self.p.buf(B, Ho, Wo, Cout, dtype=out_dtype)
         b = None
-        if bias_img is None and bias:
+        if torch.is_tensor(bias):      # the caller's own fp32 bias (Weights.conv_pad8: output channels padded to a whole group)
+            b = bias
+        elif bias_img is None and bias:
             b = self.w.f32(name + ".bias")
             if b.numel() < Cout:   # dgrad weights are channel padded
                 b = None
@@ -1161,9 +1206,10 @@ class VAEEncoderPlan:
         self.dx = d     # [1,H,W,8] bf16
 
     @staticmethod
-    def _attention(f: Builder, r: Builder, w: Weights, x, pre, tape):
-        """Single-head self-attention of the VAE mid block (d = C = 512, N = 4096): QK^T / softmax / PV as strided GEMMs +
-        row softmax, because its backward needs P."""
+    def _attention_forward(f: Builder, w: Weights, x, pre):
+        """Single-head self-attention of a VAE mid block (d = C = 512, N = 4096): QK^T / softmax / PV as strided GEMMs +
+        row softmax, because the encoder's backward needs P.  Returns (out [B,H,W,C], what that backward reads).  The decoder's mid block
+        (VAEDecoderPlan) is the same layer under `decoder.`: it records these launches and keeps nothing."""
         B, H, W, C = x.shape
         N = H * W
         scale = float(C) ** -0.5
@@ -1192,7 +1238,16 @@ class VAEEncoderPlan:
             f.p.add_gemm(gemm.gemm_raw(P, v, o, N, C, N, (N, 1), (1, C), C, batch=(B, 1), a_batch=(N * N, 0), b_batch=(N * C, 0),
                                        c_batch=(N * C, 0), name="vae_pv", run=False))
         out = f.linear(o, w.lin(pre + ".to_out.0"), bias=w.f32(pre + ".to_out.0.bias"), residual=x.view(B, N, C), tag="vae_out")
-        out = out.view(B, H, W, C)
+        return out.view(B, H, W, C), (st, q, k, v, P, kc)
+
+    @staticmethod
+    def _attention(f: Builder, r: Builder, w: Weights, x, pre, tape):
+        """The mid-block attention with its input-gradient backward appended to `tape`."""
+        B, H, W, C = x.shape
+        N = H * W
+        scale = float(C) ** -0.5
+        out, (st, q, k, v, P, kc) = VAEEncoderPlan._attention_forward(f, w, x, pre)
+        pp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
 
         def back(dout):
             dt = dout.view(B, N, C)
@@ -1291,3 +1346,92 @@ class VAEEncoderPlan:
         self.bwd.run()
         dx = self.bwd.load(self.dx)[..., :3].permute(0, 3, 1, 2)
         return dx * inv if inv is not None else dx * 2.0
+
+
+class VAEDecoderPlan:
+    """AutoencoderKL.decode: post_quant_conv + decoder, forward only (no tape, no kept statistics) -- what `decode_latents`
+    (core/guidance/vae.py:42-46) runs for every snapshot of a latent NeRF, every `grad_viz` picture and the targets of the x0 losses.
+    One chain without forks: post_quant_conv (1x1) -> conv_in -> mid block (resnet, single-head attention, resnet) -> the up blocks over
+    reversed(block_out_channels), `layers_per_block + 1` resnets each and a nearest-2x + 3x3 convolution after all but the last (the upsample
+    is the convolution's own gather: Builder.conv(upsample=2)) -> GroupNorm + SiLU -> conv_out.  Every norm has eps 1e-6.
+    latents [B,latent_channels,h,h] fp32 -> image [B,3,8h,8h] fp32 (for the SD-1.5 depth of four levels: 2^(levels - 1) h in general)."""
+
+    MIN_HW, MAX_HW = 8, 128
+
+    def __init__(self, cfg: VAEConfig, sd, device, latent_hw=64, dtype="f32x", batch=1, weights=None):
+        if cfg.in_channels != 3 or not 1 <= cfg.latent_channels <= 8:
+            raise NotImplementedError("VAEDecoderPlan writes 3-channel images from latents of at most 8 channels, got in_channels=%d latent_channels=%d"
+                                      % (cfg.in_channels, cfg.latent_channels))
+        if not self.MIN_HW <= int(latent_hw) <= self.MAX_HW:
+            raise ValueError("VAEDecoderPlan: latent_hw must be in %d..%d, got %r" % (self.MIN_HW, self.MAX_HW, latent_hw))
+        if int(batch) < 1:
+            raise ValueError("VAEDecoderPlan: batch must be at least 1, got %r" % (batch,))
+        have = weights.sd if weights is not None else sd
+        for key in vae_decoder_param_shapes(cfg):
+            if have is None or key not in have:
+                raise KeyError("VAEDecoderPlan: the state dict lacks the decoder key %r" % key)
+        self.cfg, self.device, self.hw, self.B = cfg, device, int(latent_hw), int(batch)
+        self.plan = Plan(device, dtype)
+        w = weights if weights is not None else Weights(sd, device, dtype)
+        self.weights = w            # kernel-layout weight tensors must outlive the plans that point at them
+        b = Builder(self.plan, w, cfg.groups, "vaed")
+        self.x = self.plan.buf(self.B, self.hw, self.hw, 8, zero=True)
+        wq, bq = w.conv_pad8("post_quant_conv")
+        h = b.conv(self.x, "post_quant_conv", pad=0, weight=wq, bias=bq)
+        h = b.conv(h, "decoder.conv_in")
+        h = self._resnet(b, h, "decoder.mid_block.resnets.0")
+        h, _ = VAEEncoderPlan._attention_forward(b, w, h, "decoder.mid_block.attentions.0")
+        h = self._resnet(b, h, "decoder.mid_block.resnets.1")
+        nb = len(cfg.block_out_channels)
+        for i in range(nb):
+            for j in range(cfg.layers_per_block + 1):
+                h = self._resnet(b, h, "decoder.up_blocks.%d.resnets.%d" % (i, j))
+            if i != nb - 1:
+                h = b.conv(h, "decoder.up_blocks.%d.upsamplers.0.conv" % i, upsample=2)
+        n = b.groupnorm(h, "decoder.conv_norm_out", 1e-6, True)
+        wo, bo = w.conv_pad8("decoder.conv_out")
+        self.y = b.conv(n, "decoder.conv_out", weight=wo, bias=bo)      # [B,H,W,8]: channels 0..2 the image, 3..7 zero
+        self.image_hw = int(self.y.shape[1])
+
+    @staticmethod
+    def _resnet(b: Builder, x, pre):
+        """ResnetBlock2D without a time embedding: norm1 + SiLU, conv1, norm2 + SiLU, conv2 (+ x, through a 1x1 conv_shortcut where the widths differ)."""
+        n1 = b.groupnorm(x, pre + ".norm1", 1e-6, True)
+        h1 = b.conv(n1, pre + ".conv1")
+        n2 = b.groupnorm(h1, pre + ".norm2", 1e-6, True)
+        sc = x if x.shape[-1] == h1.shape[-1] else b.conv(x, pre + ".conv_shortcut", pad=0)
+        return b.conv(n2, pre + ".conv2", residual=sc)
+
+    def capture(self):
+        self.plan.capture()
+
+    def decode(self, latents_nchw, raw=False):
+        """latents [B,latent_channels,h,h] fp32 on the plan's device -> [B,3,H,H] fp32: clamp(x / 2 + 0.5, 0, 1) (VaeImageProcessor.postprocess,
+        'pt'), or the decoder's unclamped x with raw=True.  The latents are multiplied by 1 / scaling_factor first, as decode_latents does."""
+        t = latents_nchw
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError("VAEDecoderPlan.decode: latents must be a [B,C,h,h] tensor, got %r" % (getattr(t, "shape", type(t)),))
+        if not t.is_cuda:
+            raise ValueError("VAEDecoderPlan.decode: latents must be on the plan's GPU, got a %s tensor" % t.device.type)
+        if t.shape[1] != self.cfg.latent_channels:
+            raise ValueError("VAEDecoderPlan.decode: latents must have %d channels (latent_channels), got %d" % (self.cfg.latent_channels, t.shape[1]))
+        if t.shape[2] != t.shape[3]:
+            raise ValueError("VAEDecoderPlan.decode: non-square latents %dx%d (the plan is built for square ones)" % (t.shape[2], t.shape[3]))
+        if t.shape[2] != self.hw:
+            raise ValueError("VAEDecoderPlan.decode: this plan is built for latent_hw %d, got %d" % (self.hw, t.shape[2]))
+        if t.shape[0] != self.B:
+            raise ValueError("VAEDecoderPlan.decode: this plan is built for a batch of %d, got %d" % (self.B, t.shape[0]))
+        scale = 1.0 / self.cfg.scaling_factor
+        t = t.detach().float().contiguous()
+        H = self.image_hw
+        if self.plan.is_x:
+            L, st = self.plan._lib, _lib.stream(self.device)
+            _lib.check(L.dwg_vae_latent_pack(self.B, int(t.shape[1]), self.hw, self.hw, _lib.ptr(t), scale, _lib.ptr(self.x), st), "dwg_vae_latent_pack")
+            self.plan.run()
+            out = torch.empty(self.B, 3, H, H, device=self.device, dtype=torch.float32)
+            _lib.check(L.dwg_vae_image_unpack(self.B, H, H, _lib.ptr(self.y), int(bool(raw)), _lib.ptr(out), st), "dwg_vae_image_unpack")
+            return out
+        self.plan.store(self.x, (scale * t).permute(0, 2, 3, 1))
+        self.plan.run()
+        img = self.plan.load(self.y)[..., :3].permute(0, 3, 1, 2).contiguous()
+        return img if raw else (img / 2 + 0.5).clamp(0, 1)

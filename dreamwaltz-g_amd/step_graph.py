@@ -48,6 +48,9 @@ class GraphedTrainStep:
         if getattr(trainer.model, "gaussian_background", None) is not None:
             raise NotImplementedError("GraphedTrainStep with a GaussianBackground: the Gaussian scene background is for playback and "
                                       "evaluation; no training step renders it")
+        if getattr(trainer.diffusion, "is_denoising_mode", False):
+            raise NotImplementedError("GraphedTrainStep with sds_loss_type %r: the denoising losses read the scheduler grid on the host and "
+                                      "cannot be captured into the step's graph" % (trainer.diffusion.loss_type,))
         self.device = next(iter(example_pose.values())).device
         if self.device.type != "cuda":
             raise RuntimeError("dreamwaltz_g_amd.step_graph runs on the GPU only (HIP kernels)")

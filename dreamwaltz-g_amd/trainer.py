@@ -21,6 +21,9 @@ from .text import TextAugmentation
 class SDSTrainer:
     def __init__(self, cfg, model, diffusion, optimizers, text_embeds_dict: Optional[dict] = None, use_controlnet: bool = True,
                  dist=None, world: int = 1, max_step: Optional[int] = None, densifiers: Optional[dict] = None):
+        if world > 1 and getattr(diffusion, "is_denoising_mode", False):
+            raise NotImplementedError("SDSTrainer with sds_loss_type %r is single rank (ranks: %d): the denoising losses walk the scheduler grid "
+                                      "on the host and are not part of the multi-rank step" % (diffusion.loss_type, world))
         self.cfg, self.model, self.diffusion, self.optimizers = cfg, model, diffusion, optimizers
         self.densifiers = densifiers                # {'avatar': GaussianDensifier} when cfg.render.use_densifier (trainer.py:600-603), else None
         self.text_embeds_dict = text_embeds_dict if text_embeds_dict is not None else {}

@@ -73,7 +73,8 @@ sit inside Trainer methods: /root/reference/core/trainer.py:446-453,529-530), so
                                              (diffusers pipeline, text encoder, schedulers); after __init__ the two hot methods of THAT object,
                                              `_predict` (controlnet.py:83-114) and `encode_images` (vae.py:34-40), are bound to the HIP plans
                                              built from the loaded modules' state_dict()s.  Everything else (get_text_embeds, __call__,
-                                             calc_gradients, tp_scheduler, pipe, decode_latents, isinstance checks) is the reference's own.
+                                             calc_gradients, tp_scheduler, pipe, decode_latents, isinstance checks) is the reference's own
+                                             (decode_latents: unless DWG_BIND_VAE_DECODER=1, below).
 
 Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's field network (B7) on the reference path
              DWG_BIND_NERF_TRAIN = 1                  also bind the NeRF stage's training render (B18, nerf_render.render_rays_train);
@@ -97,6 +98,10 @@ Environment: DWG_BIND_NERF = 0                        leave the NeRF stage's fie
                                                      pipeline in -- torch.float32 (its default, core/guidance/basic.py:233) -> f32x (fp32-grade
                                                      split precision on the 16-bit MFMA pipe), torch.float16 (`--guide.dtype fp16`,
                                                      basic.py:24-27) -> f16.  bf16 narrows the user's precision: only on request
+             DWG_BIND_VAE_DECODER = 1                also bind `decode_latents` (B26, vae.py:42-46: every snapshot and evaluation frame of a latent
+                                                     NeRF, the grad_viz pictures, the x0 losses' targets) to sd15.VAEDecoderPlan, fed from
+                                                     post_quant_conv.* / decoder.* of the loaded VAE; 'pt' outputs of device tensors only, anything
+                                                     else goes to the original method.  Unset or any other value: decode_latents is the reference's
              DWG_BIND_KEEP_MODULES = 1               keep the diffusers UNet / ControlNet on the GPU (default: moved to the CPU once their
                                                      weights live in the plans -- the text encoder and the VAE decoder stay where they were)
 """
@@ -547,8 +552,12 @@ def bind_guidance(ref, dtype=None, keep_modules=None):
     ucfg, vcfg = sd15.unet_config_from(getattr(unet, "config", None)), sd15.vae_config_from(getattr(vae, "config", None))
     f32 = lambda sd: {k: v.detach().float().cpu() for k, v in sd.items()}       # noqa: E731
     vsd = {k: v for k, v in f32(vae.state_dict()).items() if k.startswith(("encoder.", "quant_conv."))}
+    bind_decoder = os.environ.get("DWG_BIND_VAE_DECODER") == "1"
+    dec_kw = {}
+    if bind_decoder:                                        # B26: the decoder's plans read post_quant_conv.* / decoder.* of the same VAE
+        dec_kw = dict(decoder=True, vae_decoder_sd={k: v for k, v in f32(vae.state_dict()).items() if k.startswith(("decoder.", "post_quant_conv."))})
     hip = gd.ControlNetScoreDistillation(ref.device, unet_cfg=ucfg, vae_cfg=vcfg, unet_sd=f32(unet.state_dict()), controlnet_sd=f32(cnet.state_dict()),
-                                         vae_sd=vsd, image_hw=int(ref.default_image_size), cfg=ref.cfg, dtype=dtype)
+                                         vae_sd=vsd, image_hw=int(ref.default_image_size), cfg=ref.cfg, dtype=dtype, **dec_kw)
     if os.environ.get("DWG_BIND_EAGER") != "1":
         stream_ok = torch.cuda.current_stream(ref.device).cuda_stream != 0
         if stream_ok:
@@ -596,8 +605,15 @@ def bind_guidance(ref, dtype=None, keep_modules=None):
             return type(self).encode_images(self, images)
         return hip.encode_images(images)                   # normalise (2x-1) + encoder + posterior sample + scaling factor, differentiable
 
+    def decode_latents(self, latents, output_type='pt'):
+        if output_type != 'pt' or not isinstance(latents, torch.Tensor) or not latents.is_cuda:      # PIL / numpy outputs: the reference's own path
+            return type(self).decode_latents(self, latents, output_type)
+        return hip.decode_latents(latents.float())         # vae.py:42-46: 1 / scaling_factor, decode, postprocess 'pt'
+
     ref._predict = types.MethodType(_predict, ref)
     ref.encode_images = types.MethodType(encode_images, ref)
+    if bind_decoder:
+        ref.decode_latents = types.MethodType(decode_latents, ref)
     ref.hip = hip
     keep = keep_modules if keep_modules is not None else os.environ.get("DWG_BIND_KEEP_MODULES") == "1"
     if not keep:

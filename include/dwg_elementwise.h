@@ -119,6 +119,12 @@ int dwg_xfmt_unpack(int64_t n, const void* src, float* dst, dwg_stream_t stream)
 int dwg_vae_image_pack(int32_t B, int32_t H, int32_t W, const float* image_nchw, void* x_xs, dwg_stream_t stream);
 int dwg_vae_grad_prescale_pack(int32_t B, int32_t hw, const float* g_nchw, float target, void* dst_xs, float* inv_out, dwg_stream_t stream);
 int dwg_vae_dx_unpack(int32_t B, int32_t H, int32_t W, const void* dx_xs, const float* inv, float* out_nchw, dwg_stream_t stream);
+/* The f32x VAE decoder's boundary converters, one launch each (AutoencoderKL.decode as core/guidance/vae.py:42-46 calls it).
+ *   dwg_vae_latent_pack:   latents [B,C,h,w] fp32 (1 <= C <= 8) -> x [B,h,w,8] f32x, channels 0..C-1 = v * scale (scale = 1 / scaling_factor), C..7 = 0.
+ *   dwg_vae_image_unpack:  y [B,H,W,8] f32x, channels 0..2 -> image [B,3,H,W] fp32: min(max(0.5 y + 0.5, 0), 1), or y itself when raw != 0;
+ *                          a NaN stays a NaN in both forms. */
+int dwg_vae_latent_pack(int32_t B, int32_t C, int32_t H, int32_t W, const float* latents_nchw, float scale, void* x_xs, dwg_stream_t stream);
+int dwg_vae_image_unpack(int32_t B, int32_t H, int32_t W, const void* y_xs, int32_t raw, float* out_nchw, dwg_stream_t stream);
 /* Range telemetry of a stored f32x tensor (cold path; the hot path saturates and goes subnormal silently): ADDS into counters5 (device,
  * zeroed by the caller)  [0] hi halves at +-65504 (saturated, or on the edge),  [1] non-zero values whose hi half is subnormal or zero
  * (|x| < 6.1e-5: fewer than 22 significand bits),  [2] non-finite values,  [3] max |x| as fp32 bits (atomic max),  [4] elements seen.

@@ -24,7 +24,19 @@ int dwg_sds_posterior_sample_backward(int32_t V, int64_t n, const float* moments
 /* out[v] = sqrt(a) latents[v] + sqrt(1 - a) noise[v], a = alphas_cumprod[timestep[v]] (timestep: int64 on the device, 0 <= t < n_steps). */
 int dwg_sds_add_noise(int32_t V, int64_t n, const float* latents, const float* noise, const float* alphas_cumprod, int32_t n_steps,
                       const int64_t* timestep, float* out, dwg_stream_t stream);
-#define DWG_SDS_WEIGHT_NONE 0        /* 'sjc' / None */
+/* One reverse-diffusion step per view: diffusers' DDPMScheduler.step for prediction_type 'epsilon', variance_type 'fixed_small', no sample
+ * clipping (core/guidance/basic.py:469-527 get_denoise_pred).  t = timestep[v], p = prev_timestep[v] (int64 on the device: no host read), a the
+ * alphas_cumprod table, eps = noise_pred (already classifier-free combined):
+ *   a_t = a[t];  a_p = a[p] if p >= 0 else 1;  alpha = a_t / a_p;  beta = 1 - alpha
+ *   pred_original_sample = (sample - sqrt(1 - a_t) eps) / sqrt(a_t)
+ *   prev_sample = sqrt(a_p) beta / (1 - a_t) pred_original_sample + sqrt(alpha) (1 - a_p) / (1 - a_t) sample
+ *                 [+ sqrt(max((1 - a_p) / (1 - a_t) beta, 1e-20)) noise   if t > 0]
+ * These formulas are the definition (diffusers is not a dependency).  Either output may be NULL (both: nothing is launched); `noise` is read only
+ * for prev_sample and must then be given. */
+int dwg_sds_ddpm_step(int32_t V, int64_t n, const float* sample, const float* noise_pred, const float* noise, const float* alphas_cumprod,
+                      int32_t n_steps, const int64_t* timestep, const int64_t* prev_timestep, float* pred_original_sample, float* prev_sample,
+                      dwg_stream_t stream);
+#define DWG_SDS_WEIGHT_NONE 0       /* 'sjc' / None */
 #define DWG_SDS_WEIGHT_DREAMFUSION 1 /* 1 - a */
 #define DWG_SDS_WEIGHT_LATENT_NERF 2 /* (1 - a) sqrt(a) */
 #define DWG_SDS_WEIGHT_ISM 3         /* sqrt((1 - a) / a) */
