@@ -1,5 +1,6 @@
-// elementwise.hip -- small bandwidth-bound helpers around the GEMM primitive (activation backward + bias gradient,
-// fused multi-tensor Adam).  Each is a grid-stride kernel with 16-byte accesses where the layout allows.
+// elementwise.hip -- the helpers around the GEMM primitive (include/dwg_elementwise.h, all but the fused Adam: adam.hip): the per-Gaussian
+// MLPs' activation backward + bias gradient, weight gradient and whole-chain forward / backward; concat, add, cast and transpose of the
+// denoiser's activations; the f32x pack / unpack / range scan; the VAE's layouts.  Grid-stride, 16-byte accesses where the layout allows.
 #include "dwg_common.h"
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_elementwise.h"
@@ -71,66 +72,6 @@ __global__ __launch_bounds__(256) void k_act_bwd_colsum(int M, int N, int act, c
         float t = 0.f;
         for (int k = 0; k < rows_par; k++) t += part[k * tpr + tid];
         atomicAdd(&colsum[tid], t);
-    }
-}
-
-// Adam (torch.optim.Adam semantics, amsgrad=False, weight_decay=0, maximize=False):
-//   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
-// `hyper` != nullptr: the per-step scalars come from DEVICE memory -- hyper[0] = lr / (1 - b1^t), hyper[1] = sqrt(1 - b2^t), hyper[2] =
-// grad_scale -- so that the launch can sit inside a captured graph whose replays see the learning-rate schedule and the step count move.
-__global__ __launch_bounds__(256) void k_adam(size_t n, float* __restrict__ p, const float* __restrict__ g,
-                                              float* __restrict__ m, float* __restrict__ v, float lr, float b1, float b2,
-                                              float eps, float bc1, float bc2_sqrt, float grad_scale, const float* __restrict__ hyper) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * 256;
-    const size_t n4 = n / 4;
-    float4* p4 = reinterpret_cast<float4*>(p); const float4* g4 = reinterpret_cast<const float4*>(g);
-    float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v);
-    float step = lr / bc1;
-    if (hyper) { step = hyper[0]; bc2_sqrt = hyper[1]; grad_scale = hyper[2]; }
-    for (size_t k = i; k < n4; k += stride) {
-        float4 pp = p4[k], gg = g4[k], mm = m4[k], vv = v4[k];
-#define UPD(c) { float gr = gg.c * grad_scale; mm.c = b1 * mm.c + (1.f - b1) * gr; vv.c = b2 * vv.c + (1.f - b2) * gr * gr; \
-                 pp.c -= step * mm.c / (sqrtf(vv.c) / bc2_sqrt + eps); }
-        UPD(x) UPD(y) UPD(z) UPD(w)
-#undef UPD
-        p4[k] = pp; m4[k] = mm; v4[k] = vv;
-    }
-    for (size_t k = n4 * 4 + i; k < n; k += stride) {
-        float gr = g[k] * grad_scale;
-        float mm = b1 * m[k] + (1.f - b1) * gr, vv = b2 * v[k] + (1.f - b2) * gr * gr;
-        m[k] = mm; v[k] = vv;
-        p[k] -= step * mm / (sqrtf(vv) / bc2_sqrt + eps);
-    }
-}
-
-struct AdamGroups { dwg_adam_group g[DWG_ADAM_MAX_GROUPS]; };
-
-// k_adam for several parameter groups: blockIdx.y = group (groups shorter than the grid's x extent leave their surplus workgroups idle)
-__global__ __launch_bounds__(256) void k_adam_groups(AdamGroups G, const float* __restrict__ hyper) {
-    const dwg_adam_group a = G.g[blockIdx.y];
-    const size_t n = (size_t)a.n, n4 = n / 4;
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4 && n4 * 4 + i >= n) return;
-    const size_t stride = (size_t)gridDim.x * 256;
-    float* __restrict__ p = a.param; const float* __restrict__ g = a.grad; float* __restrict__ m = a.exp_avg; float* __restrict__ v = a.exp_avg_sq;
-    float4* p4 = reinterpret_cast<float4*>(p); const float4* g4 = reinterpret_cast<const float4*>(g);
-    float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v);
-    const float* h = hyper + 4 * (size_t)a.hyper_row;
-    const float step = h[0], bc2_sqrt = h[1], grad_scale = h[2], b1 = a.beta1, b2 = a.beta2, eps = a.eps;
-    for (size_t k = i; k < n4; k += stride) {
-        float4 pp = p4[k], gg = g4[k], mm = m4[k], vv = v4[k];
-#define UPD(c) { float gr = gg.c * grad_scale; mm.c = b1 * mm.c + (1.f - b1) * gr; vv.c = b2 * vv.c + (1.f - b2) * gr * gr; \
-                 pp.c -= step * mm.c / (sqrtf(vv.c) / bc2_sqrt + eps); }
-        UPD(x) UPD(y) UPD(z) UPD(w)
-#undef UPD
-        p4[k] = pp; m4[k] = mm; v4[k] = vv;
-    }
-    for (size_t k = n4 * 4 + i; k < n; k += stride) {
-        float gr = g[k] * grad_scale;
-        float mm = b1 * m[k] + (1.f - b1) * gr, vv = b2 * v[k] + (1.f - b2) * gr * gr;
-        m[k] = mm; v[k] = vv;
-        p[k] -= step * mm / (sqrtf(vv) / bc2_sqrt + eps);
     }
 }
 
@@ -1182,66 +1123,6 @@ int dwg_act_backward_colsum(int32_t M, int32_t N, int32_t act, const float* dy, 
     int rows_per_block = 128;      // ~800 workgroups at 1e5 rows: the pass is a pure stream, it needs the whole chip
     DWG_LAUNCH("act_bwd_colsum", k_act_bwd_colsum, dim3(dwg_cdiv(M, rows_per_block)), dim3(256), 0, (hipStream_t)stream, M, N,
                act, dy, y, dz, colsum, rows_per_block);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
-}
-
-int dwg_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
-                  float beta2, float eps, int32_t step, float grad_scale, dwg_stream_t stream) {
-    if (n < 0 || step < 1) return DWG_E_ARG;
-    if (n == 0) return DWG_OK;
-    if (!param || !grad || !exp_avg || !exp_avg_sq) return DWG_E_ARG;
-    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16) return DWG_E_ARG;
-    // The step's two scalars in DOUBLE from the fp32 hyper-parameters, rounded once -- the very statements FlatOptimizer.prepare_step makes
-    // on the host for the device-resident table of a captured step (dwg_adam_step_dev): an eager step and a replay of the captured one
-    // then run k_adam on identical bits (round 5: with the table gradient deterministic, this was the last difference between the two).
-    const float stepsize = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)));
-    const float bc1 = 1.f;
-    float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-    lr = stepsize;
-    size_t blocks = ((size_t)n / 4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    DWG_LAUNCH("adam_step", k_adam, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (size_t)n, param, grad, exp_avg,
-               exp_avg_sq, lr, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, (const float*)nullptr);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
-}
-
-int dwg_adam_step_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* hyper, float beta1,
-                      float beta2, float eps, dwg_stream_t stream) {
-    if (n < 0 || !hyper) return DWG_E_ARG;
-    if (n == 0) return DWG_OK;
-    if (!param || !grad || !exp_avg || !exp_avg_sq) return DWG_E_ARG;
-    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16) return DWG_E_ARG;
-    size_t blocks = ((size_t)n / 4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    DWG_LAUNCH("adam_step", k_adam, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (size_t)n, param, grad, exp_avg,
-               exp_avg_sq, 0.f, beta1, beta2, eps, 1.f, 1.f, 1.f, hyper);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
-}
-
-int dwg_adam_step_groups_dev(int32_t count, const dwg_adam_group* groups, const float* hyper, dwg_stream_t stream) {
-    if (count < 0 || count > DWG_ADAM_MAX_GROUPS || !hyper || (count > 0 && !groups)) return DWG_E_ARG;
-    AdamGroups G;
-    size_t blocks = 0;
-    int used = 0;
-    for (int i = 0; i < count; i++) {
-        const dwg_adam_group& a = groups[i];
-        if (a.n < 0 || a.hyper_row < 0) return DWG_E_ARG;
-        if (a.n == 0) continue;
-        if (!a.param || !a.grad || !a.exp_avg || !a.exp_avg_sq) return DWG_E_ARG;
-        if (((uintptr_t)a.param | (uintptr_t)a.grad | (uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq) % 16) return DWG_E_ARG;
-        G.g[used++] = a;
-        size_t b = ((size_t)a.n / 4 + 255) / 256;
-        if (b < 1) b = 1;
-        blocks = b > blocks ? b : blocks;
-    }
-    if (used == 0) return DWG_OK;
-    if (blocks > 2048) blocks = 2048;
-    DWG_LAUNCH("adam_step", k_adam_groups, dim3((unsigned)blocks, used), dim3(256), 0, (hipStream_t)stream, G, hyper);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

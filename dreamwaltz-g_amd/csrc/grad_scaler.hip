@@ -1,6 +1,7 @@
 // grad_scaler.hip -- the device-resident loss scaler of the stage-I step under optim.fp16 (boundary B21, include/dwg_grad_scaler.h):
 // the Inf / NaN scan of the flat gradient, the one-workgroup decision (skip flag, step counts, this step's Adam scalars with the unscale
-// folded in), the fused Adam that honours the skip flag, and the scale schedule.  Nothing here reads back to the host.
+// folded in) and the scale schedule.  The fused Adam that honours the skip flag (dwg_adam_step_groups_scaled_dev) is adam.hip's, with the
+// other Adam launches.  Nothing here reads back to the host.
 #include "dwg_common.h"
 #include "dwg_prof_internal.h"
 #include "../../include/dwg_grad_scaler.h"
@@ -52,38 +53,6 @@ __global__ __launch_bounds__(256) void k_scaler_prepare(int nslots, const int32_
     reinterpret_cast<float4*>(hyper)[g] = row;
 }
 
-struct AdamGroups { dwg_adam_group g[DWG_ADAM_MAX_GROUPS]; };
-
-// k_adam_groups (elementwise.hip) with the row's skip flag read first and the unscale in the row's gradient factor: the same statements
-// per element, so a taken step differs from the unscaled kernel's only through the value of grad_scale.
-__global__ __launch_bounds__(256) void k_adam_groups_scaled(AdamGroups G, const float* __restrict__ hyper) {
-    const dwg_adam_group a = G.g[blockIdx.y];
-    const float* h = hyper + 4 * (size_t)a.hyper_row;
-    if (h[3] != 0.f) return;
-    const size_t n = (size_t)a.n, n4 = n / 4;
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4 && n4 * 4 + i >= n) return;
-    const size_t stride = (size_t)gridDim.x * 256;
-    float* __restrict__ p = a.param; const float* __restrict__ g = a.grad; float* __restrict__ m = a.exp_avg; float* __restrict__ v = a.exp_avg_sq;
-    float4* p4 = reinterpret_cast<float4*>(p); const float4* g4 = reinterpret_cast<const float4*>(g);
-    float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v);
-    const float step = h[0], bc2_sqrt = h[1], grad_scale = h[2], b1 = a.beta1, b2 = a.beta2, eps = a.eps;
-    for (size_t k = i; k < n4; k += stride) {
-        float4 pp = p4[k], gg = g4[k], mm = m4[k], vv = v4[k];
-#define UPD(c) { float gr = gg.c * grad_scale; mm.c = b1 * mm.c + (1.f - b1) * gr; vv.c = b2 * vv.c + (1.f - b2) * gr * gr; \
-                 pp.c -= step * mm.c / (sqrtf(vv.c) / bc2_sqrt + eps); }
-        UPD(x) UPD(y) UPD(z) UPD(w)
-#undef UPD
-        p4[k] = pp; m4[k] = mm; v4[k] = vv;
-    }
-    for (size_t k = n4 * 4 + i; k < n; k += stride) {
-        float gr = g[k] * grad_scale;
-        float mm = b1 * m[k] + (1.f - b1) * gr, vv = b2 * v[k] + (1.f - b2) * gr * gr;
-        m[k] = mm; v[k] = vv;
-        p[k] -= step * mm / (sqrtf(vv) / bc2_sqrt + eps);
-    }
-}
-
 __global__ void k_scaler_update(dwg_scaler_state* __restrict__ state, double growth_factor, double backoff_factor, int32_t growth_interval) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     float scale = state->scale;
@@ -124,29 +93,6 @@ int dwg_scaler_prepare(int32_t nslots, const int32_t* slots, dwg_scaler_state* s
     for (int g = 0; g < groups; g++) { B.beta1[g] = beta1[g]; B.beta2[g] = beta2[g]; }
     DWG_LAUNCH("scaler_prepare", k_scaler_prepare, dim3(1), dim3(256), 0, (hipStream_t)stream, (int)nslots, slots, state, found, (int)groups,
                mask, lr, B, grad_scale, steps, hyper);
-    DWG_RETURN_IF_LAUNCH_FAILED();
-    return DWG_OK;
-}
-
-int dwg_adam_step_groups_scaled_dev(int32_t count, const dwg_adam_group* groups, const float* hyper, dwg_stream_t stream) {
-    if (count < 0 || count > DWG_ADAM_MAX_GROUPS || !hyper || (count > 0 && !groups)) return DWG_E_ARG;
-    AdamGroups G;
-    size_t blocks = 0;
-    int used = 0;
-    for (int i = 0; i < count; i++) {
-        const dwg_adam_group& a = groups[i];
-        if (a.n < 0 || a.hyper_row < 0) return DWG_E_ARG;
-        if (a.n == 0) continue;
-        if (!a.param || !a.grad || !a.exp_avg || !a.exp_avg_sq) return DWG_E_ARG;
-        if (((uintptr_t)a.param | (uintptr_t)a.grad | (uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq) % 16) return DWG_E_ARG;
-        G.g[used++] = a;
-        size_t b = ((size_t)a.n / 4 + 255) / 256;
-        if (b < 1) b = 1;
-        blocks = b > blocks ? b : blocks;
-    }
-    if (used == 0) return DWG_OK;
-    if (blocks > 2048) blocks = 2048;
-    DWG_LAUNCH("adam_step_scaled", k_adam_groups_scaled, dim3((unsigned)blocks, used), dim3(256), 0, (hipStream_t)stream, G, hyper);
     DWG_RETURN_IF_LAUNCH_FAILED();
     return DWG_OK;
 }

@@ -4,13 +4,12 @@
 //   scaler_nonfinite    an fp32 value is Inf or NaN (all exponent bits set); FLT_MAX and denormals are finite
 //   scaler_update       torch._amp_update_scale_ for one (scale, growth_tracker): backoff on a found Inf / NaN, growth after
 //                       growth_interval clean steps unless the grown scale would not be finite
-//   adam_hyper_row      the per-step scalars of one Adam group, the statements of dwg_adam_step (elementwise.hip) and
-//                       FlatOptimizer.prepare_step: fp32 hyper-parameters, double arithmetic, one rounding -- with the unscale folded into
-//                       the gradient factor: {lr / (1 - b1^t), sqrt(1 - b2^t), grad_scale / scale, 0}
+// The per-step scalars of an Adam group that k_scaler_prepare writes (adam_hyper_row) live with the optimizer's arithmetic in adam_math.h.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+#include "adam_math.h"
 
 #if defined(__HIPCC__)
 #define DWG_SCALER_HD __host__ __device__ __forceinline__
@@ -42,11 +41,4 @@ DWG_SCALER_HD void scaler_update(float* scale, int32_t* growth_tracker, int foun
     } else {
         *growth_tracker = successful;
     }
-}
-
-DWG_SCALER_HD void adam_hyper_row(float lr, float beta1, float beta2, int32_t t, float grad_scale, float scale, float* row) {
-    row[0] = (float)((double)lr / (1.0 - pow((double)beta1, (double)t)));
-    row[1] = (float)sqrt(1.0 - pow((double)beta2, (double)t));
-    row[2] = (float)((double)grad_scale / (double)scale);
-    row[3] = 0.f;
 }

@@ -10,7 +10,7 @@ The reference builds a dict of named optimizers (`avatar.get_optimizer(cfg)`, /r
 and the trainer loops `optimizer.zero_grad()`, `optimizer.update_learning_rate(...)` (when present), `scaler.step(optimizer)` over
 them (core/trainer.py:861-890).  Here every one of those objects is a VIEW of one flat fp32 parameter buffer with flat gradient /
 first-moment / second-moment buffers next to it: the multi-view step all-reduces ONE tensor over RCCL, and each view's `step()` is
-a fused Adam launch per learning-rate group (csrc/elementwise.hip k_adam through include/dwg_elementwise.h).
+a fused Adam launch per learning-rate group (csrc/adam.hip k_adam through include/dwg_elementwise.h).
 
 The stage-II learned MLP background brings its own optimizer, `MLPBackground.get_optimizer()` (core/system/background.py:86-89): Adan
 (core/optim/adan.py).  Here that is FlatAdan (boundary B23): flat buffers of its own and three launches a step (csrc/adan.hip through
@@ -110,6 +110,18 @@ class FlatBuffers:
 PARAM_EPOCH = [0]
 
 
+def _group_slices(buf: FlatBuffers, pg):
+    """(n, [param, grad, exp_avg, exp_avg_sq]): a param group's length and the addresses of its four slices of the flat buffers."""
+    off = pg["start"] * 4
+    return pg["end"] - pg["start"], [t.data_ptr() + off for t in (buf.flat, buf.grad, buf.m, buf.v)]
+
+
+def _group_c(buf: FlatBuffers, pg, row: int):
+    """The group as the grouped launches take it (dwg_adam_group), reading row `row` of the device hyper table."""
+    n, ptrs = _group_slices(buf, pg)
+    return _lib.AdamGroupC(*ptrs, n, float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), row)
+
+
 class FlatOptimizer:
     """One of the named optimizers, as a view [start, end) of the flat buffers: same surface the trainer uses on the reference's
     objects (param_groups, zero_grad, step, state_dict / load_state_dict, and update_learning_rate for 'avatar')."""
@@ -168,6 +180,12 @@ class FlatOptimizer:
         self.t += 1
         self.current_iteration += 1
         PARAM_EPOCH[0] += 1
+        for gi, pg in self._taking_part(participation):
+            pg["t"] = pg.get("t", 0) + 1
+            self._launch(pg)
+
+    def _taking_part(self, participation=None):
+        """Yields (group index, pg) of the groups this step updates, for step() and step_scaled().  Consumes `skip_once`."""
         for gi, pg in enumerate(self.param_groups):
             if pg.pop("skip_once", False):
                 # the densifier just replaced this group's parameter: torch.optim.Adam finds `grad is None` on the new Parameter and leaves
@@ -182,8 +200,7 @@ class FlatOptimizer:
                 # no parameter of this group took part in this step's backward: torch.optim.Adam sees `grad is None` and leaves the
                 # parameter, both moments and the step count untouched (no drift on stale momentum, no ageing of the bias correction)
                 continue
-            pg["t"] = pg.get("t", 0) + 1
-            self._launch(pg)
+            yield gi, pg
 
     # -- the same step in two halves, for a captured graph of the whole avatar-side step (step_graph.GraphedTrainStep) ----------------
     def prepare_step(self, hyper_host: torch.Tensor, base: int):
@@ -196,8 +213,8 @@ class FlatOptimizer:
         PARAM_EPOCH[0] += 1
         for k, pg in enumerate(self.param_groups):
             pg["t"] = pg.get("t", 0) + 1
-            # the statements of dwg_adam_step (csrc/elementwise.hip): fp32 hyper-parameters, double arithmetic, one rounding -- a replay of the
-            # captured step and an eager step then feed k_adam identical bits
+            # the statements of adam_hyper_row (csrc/adam_math.h), which dwg_adam_step uses: fp32 hyper-parameters, double arithmetic, one
+            # rounding -- a replay of the captured step and an eager step then feed k_adam identical bits
             b1, b2, lr = (struct.unpack("f", struct.pack("f", float(x)))[0] for x in (pg["betas"][0], pg["betas"][1], pg["lr"]))
             hyper_host[base + k, 0] = lr / (1.0 - b1 ** pg["t"])
             hyper_host[base + k, 1] = math.sqrt(1.0 - b2 ** pg["t"])
@@ -206,15 +223,12 @@ class FlatOptimizer:
 
     def launch_step(self, hyper_dev: torch.Tensor, base: int):
         """DEVICE half: one fused Adam launch per group reading its scalars from row base + k of the device hyper table (capturable)."""
-        b = self.buf
-        st = _lib.stream(b.flat.device)
+        st = _lib.stream(self.buf.flat.device)
         for k, pg in enumerate(self.param_groups):
-            n, o = pg["end"] - pg["start"], pg["start"] * 4
+            n, ptrs = _group_slices(self.buf, pg)
             if n <= 0:
                 continue
-            _lib.check(_lib.lib().dwg_adam_step_dev(n, ctypes.c_void_p(b.flat.data_ptr() + o), ctypes.c_void_p(b.grad.data_ptr() + o),
-                                                    ctypes.c_void_p(b.m.data_ptr() + o), ctypes.c_void_p(b.v.data_ptr() + o),
-                                                    ctypes.c_void_p(hyper_dev.data_ptr() + (base + k) * 16), float(pg["betas"][0]),
+            _lib.check(_lib.lib().dwg_adam_step_dev(n, *ptrs, ctypes.c_void_p(hyper_dev.data_ptr() + (base + k) * 16), float(pg["betas"][0]),
                                                     float(pg["betas"][1]), float(pg["eps"]), st), "dwg_adam_step_dev")
         return len(self.param_groups)
 
@@ -266,20 +280,9 @@ class FlatOptimizer:
             return
         b = self.buf
         mask, groups = 0, []
-        for gi, pg in enumerate(self.param_groups):
-            if pg.pop("skip_once", False):
-                continue
-            if pg["end"] <= pg["start"]:
-                continue
-            if participation is not None:
-                if not participation[gi]:
-                    continue
-            elif self.buf.tracking and pg.get('params') and not any(getattr(p, "_dwg_touched", False) for p in pg['params']):
-                continue
-            n, off = pg["end"] - pg["start"], pg["start"] * 4
+        for gi, pg in self._taking_part(participation):
             mask |= 1 << gi
-            groups.append(_lib.AdamGroupC(b.flat.data_ptr() + off, b.grad.data_ptr() + off, b.m.data_ptr() + off, b.v.data_ptr() + off, n,
-                                          float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), gi))
+            groups.append(_group_c(b, pg, gi))
         d = self._device_state()
         L = _lib.lib()
         st = _lib.stream(b.flat.device)
@@ -298,14 +301,10 @@ class FlatOptimizer:
                        "dwg_adam_step_groups_scaled_dev")
 
     def _launch(self, pg):
-        """The fused Adam launch of one group over its slice of the flat buffers (csrc/elementwise.hip k_adam)."""
-        b = self.buf
-        n, o = pg["end"] - pg["start"], pg["start"] * 4
-        st = _lib.stream(b.flat.device)
-        _lib.check(_lib.lib().dwg_adam_step(n, ctypes.c_void_p(b.flat.data_ptr() + o), ctypes.c_void_p(b.grad.data_ptr() + o),
-                                            ctypes.c_void_p(b.m.data_ptr() + o), ctypes.c_void_p(b.v.data_ptr() + o), float(pg["lr"]),
-                                            float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), int(pg["t"]), float(self.grad_scale), st),
-                   "dwg_adam_step")
+        """The fused Adam launch of one group over its slice of the flat buffers (csrc/adam.hip k_adam)."""
+        n, ptrs = _group_slices(self.buf, pg)
+        _lib.check(_lib.lib().dwg_adam_step(n, *ptrs, float(pg["lr"]), float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]),
+                                            int(pg["t"]), float(self.grad_scale), _lib.stream(self.buf.flat.device)), "dwg_adam_step")
 
     def state_dict(self):
         """Same information a torch Adam state_dict carries, flat: step count, per-group hyper-parameters and the two moments.  After
@@ -345,13 +344,9 @@ class FlatOptimizerDict(dict):
         b = self.buffers
         groups, base = [], 0
         for o in self.values():
-            for k, pg in enumerate(o.param_groups):
-                n, off = pg["end"] - pg["start"], pg["start"] * 4
-                if n > 0:
-                    groups.append(_lib.AdamGroupC(b.flat.data_ptr() + off, b.grad.data_ptr() + off, b.m.data_ptr() + off, b.v.data_ptr() + off, n,
-                                                  float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), base + k))
+            groups += [_group_c(b, pg, base + k) for k, pg in enumerate(o.param_groups) if pg["end"] > pg["start"]]
             base += len(o.param_groups)
-        if len(groups) > 16:
+        if len(groups) > _lib.ADAM_MAX_GROUPS:
             base = 0
             for o in self.values():
                 base += o.launch_step(hyper_dev, base)

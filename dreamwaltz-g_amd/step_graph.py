@@ -14,7 +14,7 @@ warm-up steps, as player.GraphedAnimation does; a step that needs more pairs is 
 it, `recapture()` grows the capacity), the binning order of the rasterizer (results do not depend on it).  What moves per replay without
 being captured: the pose (static device buffers, refreshed by an asynchronous copy before the launch), the optimizers' per-step scalars
 (learning-rate schedule, bias corrections: `FlatOptimizer.prepare_step` writes them to a pinned table, one copy puts them where
-`dwg_adam_step_dev` reads them) and -- round 5, `example_camera` -- the CAMERA: the reference samples a new one every step
+`dwg_adam_step_dev` / `dwg_adam_step_groups_dev`, csrc/adam.hip, read them) and -- round 5, `example_camera` -- the CAMERA: the reference samples a new one every step
 (/root/reference/data/camera/__init__.py:124-165, core/trainer.py:840-860), so extrinsic / projection / c2w and the field of view live in the
 same device block as the pose (the rasterizer reads the field of view through a pointer: dwg_raster_settings::tanfov) and `step(pose,
 camera)` refreshes them with the pose's copy.  Without `example_camera` the camera is the fixed one of the benchmark configurations.  The densifier and multi-view / multi-rank steps are not captured (they change shapes / need the host).

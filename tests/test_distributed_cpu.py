@@ -67,7 +67,7 @@ def test_flat_gradient_allreduce_gloo_world2():
 # here, so the scene is a small differentiable stand-in and the fused Adam launch is replaced by the same arithmetic in torch.
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def _cpu_adam_launch(self, pg):
-    """csrc/elementwise.hip k_adam restated in torch (FlatOptimizer._launch): one group's slice of the flat buffers."""
+    """csrc/adam.hip k_adam (csrc/adam_math.h adam_update) restated in torch (FlatOptimizer._launch): one group's slice of the flat buffers."""
     b = self.buf
     s = slice(pg["start"], pg["end"])
     g = b.grad[s] * self.grad_scale

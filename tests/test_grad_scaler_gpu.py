@@ -1,4 +1,4 @@
-"""GPU tests of the device-resident loss scaler (boundary B21, csrc/grad_scaler.hip): the Inf / NaN scan, the scaled fused Adam against
+"""GPU tests of the device-resident loss scaler (boundary B21, csrc/grad_scaler.hip; the scaled fused Adam is csrc/adam.hip's): the Inf / NaN scan, the scaled fused Adam against
 torch.optim.Adam + torch.amp.GradScaler('cuda'), participation, and the gradient hooks with a FlatGradScaler.
 
 Bounds: the skip decision, scale and growth tracker are exact; parameters after a taken step rtol 2e-5 / atol 2e-6 (the project's Adam
